@@ -11,17 +11,24 @@ bwa-flow_amd/tools/synth.cpp with seed STREAM_SEED + g; its chains are made by
 the device's own SeqsToChains (bwagpu_seqs2chains, bit-exact with the
 reference's mem_chain -> mem_chain_flt -> mem_flt_chained_seeds) against the
 genome's bwa index (bench_data/e2e, built once per box by the reference's
-bwa_idx_build).  The reference then checks the workload before any timing:
-its own SeqsToChains must give the same chains, and its own mem_chain2aln
-gives every batch's expected regions (oracle/_ref/libbwaref.so on the host
-cores: also the CPU baseline).  One step = one batch through the stage (chain
+bwa_idx_build, in build()).  With --full the reference then checks the
+workload before any timing: its own SeqsToChains must give the same chains,
+and its own mem_chain2aln gives every batch's expected regions
+(oracle/_ref/libbwaref.so on the host cores: also the CPU baseline).
+One step = one batch through the stage (chain
 windows, seed order, containment tests, left/right ksw_extend2 with band
 retries, seedcov, regions); step i runs stream batch i mod D (D = min(steps,
 --stream-batches), default 30 = 1M pairs) with every batch resident in HBM
-before timing (far more than the 256 MB MALL holds), and after the timed
-region EVERY step's output is checked bit for bit against the reference's.
+before timing (far more than the 256 MB MALL holds), and with --full, after
+the timed region, EVERY step's output is checked bit for bit against the
+reference's.
 
-Side figures: "two_batch_fixture" (round 5's headline: the two
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times
+the N steps, writes the last step's outputs with --dump-outputs DIR
+(dump_outputs) and prints the result line; --full adds the parity check, the
+roofline runs, the CPU baselines and the side figures below.
+
+Side figures (--full): "two_batch_fixture" (round 5's headline: the two
 reference-seeded batches of tests/golden/c2_refseed.npz cycled over the same
 steps), "hw_queues_4" (that figure again in a child process with HIP's default
 GPU_MAX_HW_QUEUES = 4), the PCIe-inclusive host-buffer path, the drop-in
@@ -886,20 +893,17 @@ def shard_ids(rank: int, world: int, per_rank: int) -> list[int]:
 
 def ensure_bwa_index(local_rank: int, world: int) -> str | None:
     """the golden genome's bwa index under bench_data/e2e (ref.fa.bwt/.sa/.pac/
-    .ann/.amb): kept when its stamp matches, else built by the reference's own
-    bwa_idx_build (oracle/_ref/sam_harness index: ~30-60 s, once per box) — the
-    index bwa-flow's SeqsToChains reads.  Local rank 0 builds, the others wait.
+    .ann/.amb), the index bwa-flow's SeqsToChains reads: build() makes it with
+    the reference's own bwa_idx_build (workload.build_bwa_index: oracle/_ref/
+    sam_harness index, ~30-60 s, once per box); made here when build() has not.
+    Local rank 0 builds, the others wait.
     -> the index prefix, or None when it cannot be had"""
     pre = os.path.join(E2E_DIR, "ref.fa")
-    h = os.path.join(REPO, "oracle", "_ref", "sam_harness")
-    have = os.path.exists(pre + ".bwt") and os.path.exists(pre + ".sa")
-    if not have and local_rank == 0 and os.access(h, os.X_OK):
-        import subprocess
-        os.makedirs(E2E_DIR, exist_ok=True)
+    if local_rank == 0:
         t0 = time.perf_counter()
-        r = subprocess.run([h, "index", E2E_DIR, os.devnull, "7", "0", "150", "10000000", "1", "46709983"],
-                           cwd=REPO, capture_output=True, text=True, timeout=900)
-        log(f"[bench] bwa index of the golden genome: rc={r.returncode}, {time.perf_counter() - t0:.1f} s")
+        r = workload.build_bwa_index()
+        if r is not None:
+            log(f"[bench] bwa index of the golden genome: rc={r.returncode}, {time.perf_counter() - t0:.1f} s")
     if world > 1:
         dist.barrier()
     return pre if os.path.exists(pre + ".bwt") and os.path.exists(pre + ".sa") else None
@@ -972,7 +976,8 @@ class Workload:
 
     def __init__(self, **kw):
         self.fixture = None      # [RefBatch] of tests/golden/c2_refseed.npz (c2_* workloads)
-        self.ref_answers = None  # reference_answers() of the stream (c2_stream)
+        self.ref_answers = None  # reference_answers() of the stream (c2_stream with --full)
+        self.stream = False      # the batches are the c2_stream workload's
         self.__dict__.update(kw)
 
 
@@ -1000,20 +1005,27 @@ def load_workload(args, rank, world, dev, local: int = 0) -> Workload:
             n_use = max(1, min(args.stream_batches, args.steps))
             gids = shard_ids(rank, world, n_use)
             batches, t_gen = stream_batches(dev, opt, ref, pac_t, prefix, gids)
+            data = (FIXTURE_DATA + f"; a stream of {world * n_use} distinct ChainsRecords ({n_use} per GPU: global "
+                    f"batches rank + {world} k), reads from tools/synth.cpp (seed {STREAM_SEED} + batch), chains from "
+                    "the device's own SeqsToChains (bwagpu_seqs2chains) against the reference's bwa index")
+            extras = dict(stream_batches_per_gpu=n_use, stream_batches_total=world * n_use,
+                          stream_reads_per_gpu=sum(b.n_reads for b in batches))
+            if not getattr(args, "full", False):
+                # a plain run: the stream as the device chained it; the reference's check of the
+                # chains and its expected regions take the host cores ~10 s (--full)
+                extras.update(chain_source="device SeqsToChains", **batch_stats(batches, None),
+                              setup_s={"reads_and_device_chains": round(t_gen, 2)})
+                return Workload(opt=opt, ref=ref, pac_t=pac_t, batches=batches, checks=None, data=data,
+                                extras=extras, fixture=refbatches, stream=True, gids=gids)
             t0 = time.perf_counter()
             ans = reference_answers(opt, ref, batches, prefix)
             t_ref = time.perf_counter() - t0
-            data = (FIXTURE_DATA + f"; a stream of {world * n_use} distinct ChainsRecords ({n_use} per GPU: global "
-                    f"batches rank + {world} k), reads from tools/synth.cpp (seed {STREAM_SEED} + batch), chains from "
-                    "the device's own SeqsToChains (bwagpu_seqs2chains) against the reference's bwa index, checked "
-                    "equal to the REFERENCE's own mem_chain/mem_chain_flt/mem_flt_chained_seeds before timing")
-            extras = dict(chain_source="device SeqsToChains, checked against the reference's", **batch_stats(
-                batches, ans["checks"]), stream_batches_per_gpu=n_use, stream_batches_total=world * n_use,
-                          stream_reads_per_gpu=sum(b.n_reads for b in batches),
-                          chains_identical_to_reference=ans["chains_identical"],
+            data += ", checked equal to the REFERENCE's own mem_chain/mem_chain_flt/mem_flt_chained_seeds before timing"
+            extras.update(chain_source="device SeqsToChains, checked against the reference's", **batch_stats(
+                batches, ans["checks"]), chains_identical_to_reference=ans["chains_identical"],
                           setup_s={"reads_and_device_chains": round(t_gen, 2), "reference_check": round(t_ref, 2)})
             return Workload(opt=opt, ref=ref, pac_t=pac_t, batches=batches, checks=ans["checks"], data=data,
-                            extras=extras, fixture=refbatches, ref_answers=ans, gids=gids)
+                            extras=extras, fixture=refbatches, ref_answers=ans, stream=True, gids=gids)
         if args.workload == "c2_stream":
             log("[bench] no bwa index of the golden genome: the fixture's two batches are the workload")
         batches = [rb.batch for rb in refbatches]
@@ -1127,7 +1139,7 @@ def hw_queues_4_figure(steps: int, warmup: int, ext_form: int) -> dict:
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", "c2_refseed", "--steps", str(steps),
-                        "--warmup", str(warmup), "--ext-form", str(ext_form), "--headline-only"],
+                        "--warmup", str(warmup), "--ext-form", str(ext_form), "--full", "--headline-only"],
                        cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
     if r.returncode != 0:
         return {"error": f"rc={r.returncode} {r.stderr[-300:]}"}
@@ -1139,11 +1151,39 @@ def hw_queues_4_figure(steps: int, warmup: int, ext_form: int) -> dict:
 
 def headline_line(args, world, W, eng, dbs, slots, streams, stream, sptr, elapsed, total_reads, cells, cells_all,
                   ext_ms, ext_launches, ext_busy_ms, parity) -> dict:
-    """rank 0's JSON line: the headline, its roofline (the dominant kernel, VALU
-    bound: packed 16-bit peak, the int32 figure beside it) and the HBM view"""
+    """rank 0's JSON line: the headline and, with --full (runs of their own after
+    the timed region), its roofline (the dominant kernel, VALU bound: packed
+    16-bit peak, the int32 figure beside it) and the HBM view"""
     dev = dbs[0].dev
     nb = len(dbs)
     batches = [d.b for d in dbs]
+    value = total_reads / elapsed / 1e6
+    wl_text = ("STAGE-ONLY (the SW-extend stage, ChainsToRegions: mem_chain2aln + ksw_extend2, on the GPU; seeding, "
+               "pairing and SAM are not in this number: end_to_end_align is the whole pipeline) C2: 2x150 bp pairs vs "
+               "a chr21-sized reference, ChainsRecords of 66,668 reads, inputs resident in HBM; " +
+               (f"a stream of {nb} distinct batches per GPU ({sum(b.n_reads for b in batches)} reads), each timed "
+                f"step a different batch until the stream is used up" if W.stream else
+                f"{nb} distinct reference-seeded batches cycled"))
+    line = {
+        "metric": METRIC, "value": round(value, 4), "unit": "Mreads/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "int32", "data": W.data,
+        "config": {"workload": wl_text if args.workload != "synth" else
+                   "STAGE-ONLY C2 (synth chains): SW-extend stage on GPU, inputs resident in HBM",
+                   "reads_per_batch": int(np.mean([b.n_reads for b in batches])), "distinct_batches": nb,
+                   "distinct_batches_timed": min(nb, args.steps),
+                   "batch_bases": args.batch_bases, "read_len": 150 if args.workload != "synth" else args.read_len,
+                   "parallelism": f"dp{world}", "streams": len(streams),
+                   "sharding": (f"rank r runs global stream batches r, r+{world}, ... (disjoint shards)"
+                                if W.stream else "every rank runs the same batches"), **W.extras},
+        "gcups": round(cells_all / elapsed / 1e9, 3),
+        "row_bound": bool(eng.row_bound(-1)),
+        "stage_only": True,
+        # every timed step's output against the reference's regions (--full; None: not checked)
+        "parity_all_steps": parity,
+    }
+    if not args.full:
+        return line
     # ---- launch-sequence duration (HIP events on the launch stream), outside the timed region
     per = []
     for i in range(min(nb, 8)):
@@ -1219,33 +1259,10 @@ def headline_line(args, world, W, eng, dbs, slots, streams, stream, sptr, elapse
     iso_ms = [sum(x) for x in iso]
     frac_iso = (float(np.sum(cells_batch[:n_iso])) * OPS_PER_CELL / (float(np.sum(iso_ms)) * 1e-3) / 1e12 /
                 PK16_PEAK_TOPS if iso and sum(iso_ms) > 0 else None)
-    value = total_reads / elapsed / 1e6
-    stream_wl = W.ref_answers is not None
-    wl_text = ("STAGE-ONLY (the SW-extend stage, ChainsToRegions: mem_chain2aln + ksw_extend2, on the GPU; seeding, "
-               "pairing and SAM are not in this number: end_to_end_align is the whole pipeline) C2: 2x150 bp pairs vs "
-               "a chr21-sized reference, ChainsRecords of 66,668 reads, inputs resident in HBM; " +
-               (f"a stream of {nb} distinct batches per GPU ({sum(b.n_reads for b in batches)} reads), each timed "
-                f"step a different batch until the stream is used up" if stream_wl else
-                f"{nb} distinct reference-seeded batches cycled"))
-    return {
-        "metric": METRIC, "value": round(value, 4), "unit": "Mreads/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "int32", "data": W.data,
-        "config": {"workload": wl_text if args.workload != "synth" else
-                   "STAGE-ONLY C2 (synth chains): SW-extend stage on GPU, inputs resident in HBM",
-                   "reads_per_batch": int(np.mean([b.n_reads for b in batches])), "distinct_batches": nb,
-                   "distinct_batches_timed": min(nb, args.steps),
-                   "batch_bases": args.batch_bases, "read_len": 150 if args.workload != "synth" else args.read_len,
-                   "parallelism": f"dp{world}", "streams": len(streams),
-                   "sharding": (f"rank r runs global stream batches r, r+{world}, ... (disjoint shards)"
-                                if stream_wl else "every rank runs the same batches"), **W.extras},
-        "gcups": round(cells_all / elapsed / 1e9, 3),
+    line.update({
         # the same over the cells the reference's ksw_extend2 evaluates (the row
         # bound ends calls early: those rows' cells are never computed)
         "gcups_reference_cells": round(cells_ref_step * args.steps * world / elapsed / 1e9, 3),
-        "row_bound": bool(eng.row_bound(-1)),
-        "stage_only": True,
-        "parity_all_steps": parity,
         "roofline": {"bound": "valu", "kernel": DOMINANT_KERNEL,
                      # the kernel computes in packed 16-bit halves (v_pk_*: two DP cells per
                      # lane-op, issued at ~4 cycles per wave-instruction like every 3-input /
@@ -1282,7 +1299,34 @@ def headline_line(args, world, W, eng, dbs, slots, streams, stream, sptr, elapse
                          "unit": "GB/s", "frac": round(alg_bytes / launch_s / 1e9 / HBM_PEAK_GBS, 6),
                          "alg_bytes_per_launch_sequence": round(alg_bytes), "launch_sequence_ms": round(launch_s * 1e3, 4),
                          "kernel": "whole SW-stage launch sequence (all kernels of one batch)"},
-    }
+    })
+    return line
+
+
+DUMP_MAX_BYTES = 48 << 20  # of regions.npy (region_counts.npy is 8 B per read beside it)
+
+
+def dump_outputs(path: str, d: DevBatch, slot: int, rank: int, world: int) -> None:
+    """--dump-outputs: what the last timed step handed its caller, as float64
+    .npy files under `path` (every value is exact in float64):
+      region_counts.npy  [n_reads]       regions of each read of the step's batch
+      regions.npy        [n_regions, 20] the mem_alnreg_t records in read order, one
+                         column per field of abi.ALNREG_DTYPE in its order, the
+                         64-bit hash as two columns (high, low 32 bits)
+    A batch whose regions.npy would pass DUMP_MAX_BYTES keeps a fixed seeded
+    sample of its rows (in order).  Ranks past the first add _rank<r> to the names."""
+    regs, n = d.results(slot)
+    c = compact(d.b, regs, n)
+    cols = [c[f].astype(np.float64) for f in abi.ALNREG_DTYPE.names if f != "hash"]
+    cols += [(c["hash"] >> np.uint64(32)).astype(np.float64), (c["hash"] & np.uint64(0xFFFFFFFF)).astype(np.float64)]
+    rows = np.stack(cols, axis=1) if len(c) else np.zeros((0, len(cols)), np.float64)
+    keep = DUMP_MAX_BYTES // (8 * len(cols))
+    if len(rows) > keep:
+        rows = rows[np.sort(np.random.default_rng(0).choice(len(rows), keep, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 and rank else ""
+    np.save(os.path.join(path, f"region_counts{tag}.npy"), np.asarray(n, np.float64))
+    np.save(os.path.join(path, f"regions{tag}.npy"), rows)
 
 
 def main():
@@ -1309,7 +1353,13 @@ def main():
     ap.add_argument("--no-regime", action="store_true", help="skip the C3/C5 GRCh38-regime legs")
     ap.add_argument("--no-e2e", action="store_true", help="skip the whole-pipeline end-to-end align leg")
     ap.add_argument("--no-hwq4", action="store_true", help="skip the GPU_MAX_HW_QUEUES=4 side figure")
-    ap.add_argument("--headline-only", action="store_true", help="the headline line only (no side legs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: every timed step checked against the reference's "
+                         "regions, the roofline runs, the CPU baselines and the side legs (each has a --no-* switch); "
+                         "without it: set-up, warm-up, the timed steps, --dump-outputs, the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned to its caller as DIR/<name>.npy")
+    ap.add_argument("--headline-only", action="store_true", help="with --full: the headline line only (no side legs)")
     ap.add_argument("--e2e-pairs", type=int, default=300_000)
     ap.add_argument("--no-prof", action="store_true", help="no HIP events around the dominant kernel (A/B of their cost)")
     ap.add_argument("--ext-form", type=int, default=0, choices=(0, 1, 2),
@@ -1320,7 +1370,8 @@ def main():
                          "one stream per stage worker): batch i+1's launches overlap batch i's tail; 3 since the row "
                          "bound (2 / 3 / 4: 45.7-46.3 / 48.0-51.2 / 42.8-43.8 Mreads/s, gpurun_out/r6z)")
     args = ap.parse_args()
-    if args.headline_only:
+    if args.headline_only or not args.full:
+        args.headline_only = True
         args.no_cpu = args.no_host_path = args.no_cigar = args.no_seeding = args.no_regime = True
         args.no_e2e = args.no_hwq4 = True
 
@@ -1362,7 +1413,7 @@ def main():
     sptr = stream.cuda_stream
     # warm-up: on the fixture's batches when there are any, so that the timed
     # stream batches start cold (not in the MALL)
-    wdbs = [DevBatch(rb.batch, dev) for rb in W.fixture] if W.fixture and W.ref_answers else dbs
+    wdbs = [DevBatch(rb.batch, dev) for rb in W.fixture] if W.fixture and W.stream else dbs
     for i in range(args.warmup):
         wdbs[i % len(wdbs)].run(eng, streams[i % len(streams)].cuda_stream, 0, stats=False)
     torch.cuda.synchronize()
@@ -1378,6 +1429,9 @@ def main():
     # the dominant kernel's busy time: the union of its launch intervals (the
     # caller streams' launches overlap; their summed durations can exceed the wall)
     ext_busy_ms = busy_ms(T.get("ext_iv", []))
+    if args.dump_outputs:
+        last = args.steps - 1
+        dump_outputs(args.dump_outputs, dbs[last % nb], slots[last], rank, world)
 
     # per-step counters (cells/rows/calls) of the timed steps
     cells = rows = calls = 0
@@ -1393,7 +1447,8 @@ def main():
     cells_all = float(ctot[0].item())
 
     # bit-exact check of EVERY timed step's output against the reference's regions
-    parity = steps_parity(dbs, slots, args.steps, world, dev) if checks else None
+    # (--full: the reference's regions of a stream batch come from a run of the reference)
+    parity = steps_parity(dbs, slots, args.steps, world, dev) if checks and args.full else None
 
     result = None
     if rank == 0:
@@ -1402,7 +1457,6 @@ def main():
         # the host's enqueue of the timed steps' launches (~30 per batch), per step: near
         # ms_per_step would mean the stage is launch-bound on this host
         result["host_enqueue_ms_per_step"] = round(T["enqueue_s"] * 1e3 / args.steps, 4)
-    regs0, n0 = dbs[0].results(0)
     fix_checks = W.fixture if W.fixture else checks
     if rank == 0 and world == 1 and W.fixture and W.ref_answers and not args.headline_only:
         try:  # a side line: a failure here must not cost the headline line
@@ -1426,7 +1480,7 @@ def main():
     cigar = None
     if rank == 0 and world == 1 and not args.no_cigar:
         try:  # a side line: a failure here must not cost the headline line
-            cs, jobs0, gout0 = cigar_stage(eng, dbs[0].b, regs0, n0)
+            cs, jobs0, gout0 = cigar_stage(eng, dbs[0].b, *dbs[0].results(0))
             result["cigar_stage"] = cs
             cigar = (jobs0, gout0)
         except Exception as e:

@@ -10,7 +10,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/$T
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-B="$GRAFT_REPO_ROOT/bench.py --no-cpu --no-cigar --no-host-path --no-e2e --no-regime --no-seeding --steps 5 --warmup 1 $*"
+B="$OLDPWD/bench.py --full --no-cpu --no-cigar --no-host-path --no-e2e --no-regime --no-seeding --steps 5 --warmup 1 $*"
 timeout -s KILL 120 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY -d $OUT/pmc_a -o a --output-format csv -- python3 $B > $OUT/a.json 2> $OUT/a.err || { tail $OUT/a.err; exit 1; }
 timeout -s KILL 120 rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_INSTS_BRANCH SQ_ACTIVE_INST_SCA SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -d $OUT/pmc_b -o b --output-format csv -- python3 $B > $OUT/b.json 2> $OUT/b.err || { tail $OUT/b.err; exit 2; }
 if [ "$W" = all ]; then

@@ -16,7 +16,7 @@ timeout -k 10 900 python -u -m pytest tests/ -m gpu -x -v --timeout 300 --timeou
 tail -1 $OUT/gpu_tests.log
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { tail $OUT/smoke.log; exit 2; }
 tail -1 $OUT/smoke.log
-timeout -k 10 900 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 3; }
+timeout -k 10 900 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 3; }
 python3 -c "import json;d=json.load(open('$OUT/bench.json'));print(d['value'],d['ms_per_step'],d['parity_all_steps'])"
 [ "$2" = "nop" ] || { bash tools_dev/gpu_trace.sh $T/trace || exit 4; bash tools_dev/gpu_pmc4.sh $T/pmc all || exit 5; }
 echo done > $OUT/rc.txt

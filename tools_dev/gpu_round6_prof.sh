@@ -15,6 +15,6 @@ bash tools_dev/gpu_pmc4.sh $T/pmc all --headline-only --stream-batches 8 || exit
 if [ "$2" != nofull ]; then
   export TMPDIR=/tmp
   cd /tmp
-  timeout -k 10 900 rocprofv3 --kernel-trace --stats -d $OUT/full -o run --output-format csv -- python3 $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 5 > $OUT/full.json 2> $OUT/full.err || { tail $OUT/full.err; exit 6; }
+  timeout -k 10 900 rocprofv3 --kernel-trace --stats -d $OUT/full -o run --output-format csv -- python3 $OLDPWD/bench.py --full --steps 20 --warmup 5 > $OUT/full.json 2> $OUT/full.err || { tail $OUT/full.err; exit 6; }
 fi
 echo done > $OUT/rc_prof.txt
