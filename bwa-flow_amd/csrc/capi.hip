@@ -181,13 +181,13 @@ struct Slot {
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
   DevBuf d_in, d_win, d_srt, d_prog, d_desc, d_out, d_n, d_stats, d_lists, d_counts;
   DevBuf d_cread, d_ext, d_tasks, d_ctr, d_regpos, d_skipf, d_heavy, d_redo, d_rbits;  // speculative path
-  DevBuf d_schain, d_hinfo, d_mat, d_cov, d_colent, d_qh, d_longc, d_sorth, d_stasks, d_ftask, d_ftaskR;
+  DevBuf d_schain, d_hinfo, d_mat, d_cov, d_hflag, d_colent, d_qh, d_longc, d_sorth, d_stasks, d_ftask, d_ftaskR;
   SpecStreams spec;  // created on first use (choose_side)
   bool side_chosen = false;
   void release_scratch() {
     d_win.release(); d_srt.release(); d_prog.release(); d_desc.release(); d_lists.release(); d_counts.release();
     d_cread.release(); d_ext.release(); d_tasks.release(); d_ctr.release(); d_regpos.release(); d_skipf.release();
-    d_heavy.release(); d_redo.release(); d_rbits.release(); d_schain.release(); d_hinfo.release(); d_mat.release(); d_cov.release(); d_colent.release(); d_longc.release();
+    d_heavy.release(); d_redo.release(); d_rbits.release(); d_schain.release(); d_hinfo.release(); d_mat.release(); d_cov.release(); d_hflag.release(); d_colent.release(); d_longc.release();
     d_qh.release();
     d_sorth.release();
     d_stasks.release();
@@ -874,6 +874,7 @@ int enqueue_spec(bwagpu_ctx_t* ctx, Slot& s, const DevBatch& db, int lq_max, bwa
   HIPC(s.d_schain.ensure(sizeof(int32_t) * ns), "hipMalloc(seedchain)");
   HIPC(s.d_hinfo.ensure(sizeof(int4) * nr), "hipMalloc(hinfo)");
   HIPC(s.d_cov.ensure(sizeof(int32_t) * ns), "hipMalloc(cov)");
+  HIPC(s.d_hflag.ensure(sizeof(int32_t) * ns), "hipMalloc(hflag)");
   HIPC(s.d_colent.ensure(sizeof(int32_t) * ns), "hipMalloc(colent)");
   HIPC(s.d_longc.ensure(sizeof(int32_t) * nc), "hipMalloc(longc)");
   HIPC(s.d_qh.ensure(sizeof(int32_t) * kQHWords), "hipMalloc(qh)");
@@ -903,6 +904,7 @@ int enqueue_spec(bwagpu_ctx_t* ctx, Slot& s, const DevBatch& db, int lq_max, bwa
   a.mat = s.d_mat.as<uint64_t>();
   a.mat_words = (int64_t)(s.d_mat.cap / sizeof(uint64_t));
   a.cov = s.d_cov.as<int32_t>();
+  a.hflag = s.d_hflag.as<int32_t>();
   a.colent = s.d_colent.as<int32_t>();
   a.longc = s.d_longc.as<int32_t>();
   a.qh = s.d_qh.as<int32_t>();

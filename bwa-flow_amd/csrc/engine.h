@@ -218,7 +218,9 @@ struct SpecArgs {
   int32_t* longc;             // chains with more than kOrderLane seeds
   uint64_t* mat;              // heavy-read pair matrices: C[ns][nw] then O[ns][nw] per read
   int64_t mat_words;          // capacity of mat
-  int32_t* cov;               // per seed slot: seedcov of its region (heavy reads)
+  int32_t* cov;               // per seed slot: seedcov of its region (heavy reads; -1: no region at the emulate pass)
+  int32_t* hflag;             // per seed slot of a matrix read (spec_pairs_kernel): bit 0 its chain is
+                              // processed, bit 1 it has a result, bit 2 pad_ != 0
   int32_t* qh;                // kQHWords: sharded queue heads of the extension task lists
   int32_t* sorth;             // kSortWords, zeroed per batch: per (round, bin < 2) key histograms / cursors
   int2* stasks;               // the C = 3 / 4 lists sorted by key (same offsets as tasks), for the pair kernel

@@ -2443,7 +2443,8 @@ __global__ void __launch_bounds__(kBlock) spec_select_light(DevOpt o, DevRef ref
 //   spec_scan_kernel  — one wave per read: the sequential decisions on bit
 //     sets (lane w holds word w of the extended / skipped / pending sets), then
 //     every extended seed's record lane-parallel at its rank.
-__global__ void __launch_bounds__(kBlock) spec_pairs_kernel(DevOpt o, DevBatch b, SpecArgs a, int with_cov) {
+template <int MODE>
+__global__ void __launch_bounds__(kBlock) spec_pairs_kernel(DevOpt o, DevBatch b, SpecArgs a) {
   sel_prio();
   __shared__ int32_t MG[kMglN];
   for (int x = threadIdx.x; x < kMglN; x += kBlock) MG[x] = max_gap_len(o, x);
@@ -2451,55 +2452,95 @@ __global__ void __launch_bounds__(kBlock) spec_pairs_kernel(DevOpt o, DevBatch b
   const int r = (int)(threadIdx.x & 63);
   const int ncol = uni(__hip_atomic_load(&a.ctr[SPC_HCOLS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
   const int nwv = (int)gridDim.x * (kBlock / 64);
-  for (int x = (int)blockIdx.x * (kBlock / 64) + uni((int)(threadIdx.x >> 6)); x < ncol; x += nwv) {
-    const int t = uni(a.colent[x]);
-    const int4 hi = a.hinfo[t];
+  int x = (int)blockIdx.x * (kBlock / 64) + uni((int)(threadIdx.x >> 6));
+  if (x >= ncol) return;
+  // the next column's list entry is fetched under this column's words: two of
+  // the four dependent loads in front of a column's first pair test
+  int4 hi = a.hinfo[uni(a.colent[x])];
+  for (; x < ncol; x += nwv) {
+    const int tn = uni(a.colent[min(x + nwv, ncol - 1)]);
     const int rd = uni(hi.x), woff = uni(hi.y), col = uni(hi.z), ns = uni(hi.w);
     const int k = x - col, nw = (ns + 63) >> 6;
+    const int nlow = (k + 63) >> 6;  // row k of C and O: the words of the seeds before k
     const ReadDesc d = uniform_desc(a.rdesc[rd]);
     const int rep_lim = (int)floor(.1 * d.lq) + 1;  // s->len - p->seedlen0 > .1 * l_query, bwamem.c:685
     const bwagpu_seed_t s = uni_seed(a.prog[d.s0 + k]);
     const int ck = uni(a.seedchain[d.s0 + k]);
     const int len95 = uni((int)ceil(s.len * .95));  // t->len < s->len * .95 <=> t->len < ceil(...)
     const SeedExt ek = a.ext[d.s0 + k];
-    const bool k_done = uni(ek.calls) != 0;
+    // seedcov depends on k's own region alone: once, in the first pass that
+    // sees the region (the emulate pass marks the others with -1)
+    const bool k_cov = uni(ek.calls) != 0 && (MODE == SEL_EMULATE || uni(a.cov[d.s0 + k]) < 0);
     const int64_t krb = uni64(ek.rb), kre = uni64(ek.re);
     const int kqb = uni(ek.qb), kqe = uni(ek.qe);
+    const int4 hin = a.hinfo[tn];
+    // what the scan's per-word sets need of seed k, in one word (the scan read
+    // prog, seedchain -> win and ext per seed: two dependent gathers per word)
+    const ChainWin wk = a.win[ck];
+    if (r == 0)
+      a.hflag[d.s0 + k] = (uni64(wk.hi) >= uni64(wk.lo) ? 1 : 0) | (uni(ek.calls) != 0 ? 2 : 0) | (s.pad_ != 0 ? 4 : 0);
     int cov = 0;
-    for (int w = 0; w < nw; ++w) {
-      const int j = 64 * w + r, jj = min(j, ns - 1);
-      const bwagpu_seed_t sj = a.prog[d.s0 + jj];
-      const int cj = a.seedchain[d.s0 + jj];
-      const SeedExt ej = a.ext[d.s0 + jj];
+    // word w + 1's gathers are issued before word w's ballots
+    bwagpu_seed_t sj{};
+    int cj = 0;
+    SeedExt ej{};
+    if (nlow > 0) {
+      const int jj = min(r, ns - 1);
+      sj = a.prog[d.s0 + jj];
+      cj = a.seedchain[d.s0 + jj];
+      ej = a.ext[d.s0 + jj];
+    }
+    for (int w = 0; w < nlow; ++w) {
+      const bwagpu_seed_t sc = sj;
+      const int cc = cj;
+      const SeedExt ec = ej;
+      if (w + 1 < nlow) {
+        const int jj = min(64 * (w + 1) + r, ns - 1);
+        sj = a.prog[d.s0 + jj];
+        cj = a.seedchain[d.s0 + jj];
+        ej = a.ext[d.s0 + jj];
+      }
+      const int j = 64 * w + r;
       RegRec p;
-      p.rb = ej.rb;
-      p.re = ej.re;
-      p.qb = ej.qb;
-      p.qe = ej.qe;
-      p.w = ej.w;
-      p.seedlen0 = sj.len;
-      const bool inside = j < k && ej.calls != 0 &&
+      p.rb = ec.rb;
+      p.re = ec.re;
+      p.qb = ec.qb;
+      p.qe = ec.qe;
+      p.w = ec.w;
+      p.seedlen0 = sc.len;
+      const bool inside = j < k && ec.calls != 0 &&
                           !(s.rbeg < p.rb || s.rbeg + s.len > p.re || s.qbeg < p.qb || s.qbeg + s.len > p.qe) &&
-                          !(s.len - sj.len >= rep_lim);
+                          !(s.len - sc.len >= rep_lim);
       uint64_t cm = __builtin_amdgcn_ballot_w64(inside);
       if (cm) cm = __builtin_amdgcn_ballot_w64(inside && seed_near(MG, s, p));
-      const bool a1 = s.qbeg <= sj.qbeg && s.qbeg + s.len - sj.qbeg >= s.len >> 2 &&
-                      (int64_t)(sj.qbeg - s.qbeg) != sj.rbeg - s.rbeg;
-      const bool b1 = sj.qbeg <= s.qbeg && sj.qbeg + sj.len - s.qbeg >= s.len >> 2 &&
-                      (int64_t)(s.qbeg - sj.qbeg) != s.rbeg - sj.rbeg;
-      const uint64_t om = __builtin_amdgcn_ballot_w64(j < k && cj == ck && sj.pad_ == 0 && sj.len >= len95 && (a1 || b1));
-      if (r == 0 && 64 * w < k) {
-        a.mat[woff + tri_off(k) + w] = cm;
-        a.mat[woff + tri_off(ns) + tri_off(k) + w] = om;
+      if (r == 0) a.mat[woff + tri_off(k) + w] = cm;
+      if (MODE == SEL_EMULATE) {  // O depends on no extension result: the final pass keeps it
+        const bool a1 = s.qbeg <= sc.qbeg && s.qbeg + s.len - sc.qbeg >= s.len >> 2 &&
+                        (int64_t)(sc.qbeg - s.qbeg) != sc.rbeg - s.rbeg;
+        const bool b1 = sc.qbeg <= s.qbeg && sc.qbeg + sc.len - s.qbeg >= s.len >> 2 &&
+                        (int64_t)(s.qbeg - sc.qbeg) != s.rbeg - sc.rbeg;
+        const uint64_t om =
+            __builtin_amdgcn_ballot_w64(j < k && cc == ck && sc.pad_ == 0 && sc.len >= len95 && (a1 || b1));
+        if (r == 0) a.mat[woff + tri_off(ns) + tri_off(k) + w] = om;
       }
-      if (with_cov && k_done)
-        cov += (j < ns && cj == ck && sj.qbeg >= kqb && sj.qbeg + sj.len <= kqe && sj.rbeg >= krb &&
-                sj.rbeg + sj.len <= kre) ? sj.len : 0;
+      if (k_cov)
+        cov += (j < ns && cc == ck && sc.qbeg >= kqb && sc.qbeg + sc.len <= kqe && sc.rbeg >= krb &&
+                sc.rbeg + sc.len <= kre) ? sc.len : 0;
     }
-    if (with_cov) {
+    if (k_cov) {  // the rest of the row, for seedcov alone
+      for (int w = nlow; w < nw; ++w) {
+        const int j = 64 * w + r, jj = min(j, ns - 1);
+        const bwagpu_seed_t sc = a.prog[d.s0 + jj];
+        const int cc = a.seedchain[d.s0 + jj];
+        cov += (j < ns && cc == ck && sc.qbeg >= kqb && sc.qbeg + sc.len <= kqe && sc.rbeg >= krb &&
+                sc.rbeg + sc.len <= kre) ? sc.len : 0;
+      }
       cov = (int)grp_sum64(cov, 64);
       if (r == 0) a.cov[d.s0 + k] = cov;
+    } else if (MODE == SEL_EMULATE) {
+      if (r == 0) a.cov[d.s0 + k] = -1;
     }
+    hi = hin;
   }
 }
 
@@ -2599,13 +2640,11 @@ __global__ void __launch_bounds__(64) spec_scan_kernel(DevOpt o, DevRef ref, Dev
     // per-word sets: lane w holds word w
     uint64_t present_w = 0, computed_w = 0, skip_w = 0;
     for (int w = 0; w < nw; ++w) {
-      const int j = 64 * w + r, jj = min(j, ns - 1);
-      const bwagpu_seed_t sj = a.prog[d.s0 + jj];
-      const ChainWin cw = a.win[a.seedchain[d.s0 + jj]];
-      const bool pres = j < ns && cw.hi >= cw.lo;  // seeds of a flagged chain are never processed
-      const uint64_t pm = __builtin_amdgcn_ballot_w64(pres);
-      const uint64_t cm = __builtin_amdgcn_ballot_w64(pres && a.ext[d.s0 + jj].calls != 0);
-      const uint64_t km = __builtin_amdgcn_ballot_w64(j < ns && sj.pad_ != 0);
+      const int j = 64 * w + r;
+      const int f = j < ns ? a.hflag[d.s0 + j] : 0;  // spec_pairs_kernel<MODE>, this pass
+      const uint64_t pm = __builtin_amdgcn_ballot_w64(f & 1);  // seeds of a flagged chain are never processed
+      const uint64_t cm = __builtin_amdgcn_ballot_w64((f & 3) == 3);
+      const uint64_t km = __builtin_amdgcn_ballot_w64(f & 4);
       present_w = r == w ? pm : present_w;
       computed_w = r == w ? cm : computed_w;
       skip_w = r == w ? km : skip_w;
@@ -2647,14 +2686,71 @@ __global__ void __launch_bounds__(64) spec_scan_kernel(DevOpt o, DevRef ref, Dev
           oin = r > 0 ? O[row + bw] : 0;
         }
       }
-      const uint64_t cbm = __builtin_amdgcn_ballot_w64(valid && cb);
-      uint64_t obm = __builtin_amdgcn_ballot_w64(valid && ob);
-      const uint64_t cbcm = __builtin_amdgcn_ballot_w64(valid && cbc), oum = __builtin_amdgcn_ballot_w64(valid && ou);
       const uint64_t pres = lane64(present_w, bw);
       uint64_t comp = lane64(computed_w, bw), skp = lane64(skip_w, bw), ext = 0, pend = 0, spend = 0;
       uint64_t uncb = 0;  // this block's seeds of uncertain decision
       const int nb = min(64, ns - kb);
-      for (int i = 0; i < nb; ++i) {
+      // The in-block word lane-parallel: seed kb + r's decision depends only on
+      // the decisions of the lanes below r (cin and oin hold bits < r) and of
+      // the earlier blocks, so every lane decides from the current masks and
+      // the masks are exchanged by ballot until none changes.  After t rounds
+      // the lanes below t are final: at most nb + 1 rounds, and the fixed point
+      // is the serial loop's result.  (The serial loop cost ~230 ns per seed,
+      // four lane reads and the branches: DESIGN.md §3 round 7.)  A block where
+      // the final pass meets an extended seed without a result (`lack`) runs
+      // the serial loop below from its start: it extends inline or defers.
+      bool resolved = false;
+      {
+        const uint64_t skp0 = skp;
+        const bool prs = (pres >> r) & 1, cmp = (comp >> r) & 1;
+        const bool cb_k = valid && cb, ob_k = valid && ob, cbc_k = valid && cbc, ou_k = valid && ou;
+        uint64_t e = 0, sk = skp0, pn = 0, sp = 0, un = 0, lack = 0;
+        for (int it = 0; it <= nb + 1; ++it) {
+          bool is_skip = false, is_ext = false, is_pend = false, is_spend = false, is_unc = false, is_lack = false;
+          if (prs) {
+            if ((cb_k || (cin & e)) && !ob_k && !(oin & ~sk)) {  // skipped: srt[k] = 0 (bwamem.c:709)
+              is_skip = true;
+              if (strict && (!(cbc_k || (cin & e & ~un)) || ou_k || (oin & un))) {
+                is_unc = true;
+                is_spend = !cmp;
+              }
+            } else if (!cmp) {
+              if (MODE == SEL_EMULATE) is_pend = is_unc = true;  // a round-B task; its region stays unknown
+              else is_lack = true;
+            } else {
+              is_ext = true;
+              is_unc = strict && (fp < k || (pn & lt_mask));  // a pending seed's region may hold it
+            }
+          }
+          const uint64_t e1 = __builtin_amdgcn_ballot_w64(is_ext), sk1 = skp0 | __builtin_amdgcn_ballot_w64(is_skip);
+          uint64_t pn1 = 0, sp1 = 0, un1 = 0, lack1 = 0;
+          if (MODE == SEL_EMULATE) {
+            pn1 = __builtin_amdgcn_ballot_w64(is_pend);
+            if (strict) {
+              sp1 = __builtin_amdgcn_ballot_w64(is_spend);
+              un1 = __builtin_amdgcn_ballot_w64(is_unc);
+            }
+          } else {
+            lack1 = __builtin_amdgcn_ballot_w64(is_lack);
+          }
+          const bool same = e1 == e && sk1 == sk && pn1 == pn && sp1 == sp && un1 == un && lack1 == lack;
+          e = e1, sk = sk1, pn = pn1, sp = sp1, un = un1, lack = lack1;
+          if (same) {
+            resolved = lack == 0;
+            break;
+          }
+        }
+        if (resolved) {
+          ext = e, skp = sk, pend = pn, spend = sp;
+          uncb = strict ? un : pn;
+          if (pn) fp = min(fp, kb + (int)__builtin_ctzll(pn));
+        }
+      }
+      const uint64_t cbm = resolved ? 0 : __builtin_amdgcn_ballot_w64(valid && cb);
+      uint64_t obm = resolved ? 0 : __builtin_amdgcn_ballot_w64(valid && ob);
+      const uint64_t cbcm = resolved ? 0 : __builtin_amdgcn_ballot_w64(valid && cbc);
+      const uint64_t oum = resolved ? 0 : __builtin_amdgcn_ballot_w64(valid && ou);
+      for (int i = 0; i < (resolved ? 0 : nb); ++i) {
         const uint64_t bit = 1ull << i;
         if (!(pres & bit)) continue;
         if ((cbm & bit) || (lane64(cin, i) & ext)) {
@@ -2703,13 +2799,21 @@ __global__ void __launch_bounds__(64) spec_scan_kernel(DevOpt o, DevRef ref, Dev
     int nreg = 0;
     if constexpr (MODE == SEL_EMULATE) {
       const int list = kSpecBins + spec_bin(d.lq);
-      for (int w = 0; w < nw; ++w) {
-        const uint64_t pw = (uint64_t)__builtin_amdgcn_readlane((uint32_t)(pend_w >> 32), w) << 32 |
-                            (uint32_t)__builtin_amdgcn_readlane((uint32_t)pend_w, w);
-        const int j = 64 * w + r;
-        const bool pnd = (pw >> r) & 1;
-        const int p = wave_append(&a.ctr[SPC_CNT + list], pnd);
-        if (p >= 0) a.tasks[spec_list_off(list, b.n_chains, b.n_seeds) + p] = make_int2(d.s0 + j, a.seedchain[d.s0 + j]);
+      // the read's round-B tasks take one stretch of the list: one atomic per
+      // read, not one dependent atomic per word
+      const int tot = (int)grp_sum64(r < nw ? (int)__popcll(pend_w) : 0, 64);
+      if (tot) {
+        int off = 0;
+        if (r == 0) off = atomicAdd(&a.ctr[SPC_CNT + list], tot);
+        off = __builtin_amdgcn_readfirstlane(off);
+        for (int w = 0; w < nw; ++w) {
+          const uint64_t pw = lane64(pend_w, w);
+          const int j = 64 * w + r;
+          if ((pw >> r) & 1)
+            a.tasks[spec_list_off(list, b.n_chains, b.n_seeds) + off + (int)__popcll(pw & lt_mask)] =
+                make_int2(d.s0 + j, a.seedchain[d.s0 + j]);
+          off += (int)__popcll(pw);
+        }
       }
     } else {
       if (miss >= 0) {
@@ -2775,8 +2879,8 @@ static void launch_select(const DevOpt& o, const DevRef& ref, const DevBatch& b,
     hipLaunchKernelGGL((spec_select_light<MODE>), dim3(nb), dim3(kBlock), lds, st, o, ref, b, a, tb_bytes);
   }
   if (MODE != SEL_REDO) {  // heavy reads with pair matrices: all pairs at once, then one scan per read
-    const int nb = resident_blocks(spec_pairs_kernel, 0);
-    hipLaunchKernelGGL(spec_pairs_kernel, dim3(nb), dim3(kBlock), 0, hs, o, b, a, MODE == SEL_FINAL ? 1 : 0);
+    const int nb = resident_blocks(spec_pairs_kernel<MODE>, 0);
+    hipLaunchKernelGGL((spec_pairs_kernel<MODE>), dim3(nb), dim3(kBlock), 0, hs, o, b, a);
     hipLaunchKernelGGL((spec_scan_kernel<MODE>), dim3(kScanGrid), dim3(64), (size_t)kScanLds + 2 * (size_t)tb_bytes, hs, o,
                        ref, b, a, tb_bytes);
   }
