@@ -23,6 +23,8 @@
 
 #include "align2.h"
 #include "reg2aln.h"
+#include "regpost.h"
+#include "regpost_host.h"
 #include "seed.h"
 #include "chain.h"
 #include "engine.h"
@@ -367,6 +369,13 @@ struct bwagpu_ctx {
   Slot ch_slot;  // chain2aln scratch of bwagpu_seqs2regions
   ChainStreams ch_cs{};  // created on first use
   bool has_alt = false;
+  // region post-processing (bwagpu_regs_post*, bwagpu_set_regs_post): mem_opt_t.b,
+  // the switch's options / flags / next batch's id0, the host entry's buffers
+  int opt_b = 0;
+  bwagpu_postopt_t post_opt{};
+  int32_t post_flags = 0;
+  int64_t post_id0 = 0;
+  DevBuf rp_regs, rp_seq, rp_soff, rp_roff, rp_n, rp_stats;
   // the FPGA wire format (bwagpu_sw_stream)
   DevBuf st_buf, st_start, st_q, st_tasks, st_lists, st_seen, st_ctr, st_out;
   // bwt_extend calls tier 1 spends on a read before tier 2 (one wave per read)
@@ -497,6 +506,7 @@ int create_common(int device, const bwagpu_opt_t* opt, const bwagpu_bns_t* bns, 
     return BWAGPU_E_INVAL;
   }
   ctx->device = device;
+  ctx->opt_b = opt->b;
   ctx->ext_form = set_ext_form(-1);
   *made = ctx;
   HIPC(hipSetDevice(device), "hipSetDevice");
@@ -586,7 +596,8 @@ void destroy_ctx(bwagpu_ctx_t* ctx) {
                     &ctx->ch_ord, &ctx->ch_chains, &ctx->ch_nodes, &ctx->ch_ochains, &ctx->ch_oslist, &ctx->ch_bins, &ctx->ch_dbg, &ctx->ch_swoff, &ctx->ch_swtasks, &ctx->ch_swt,
                     &ctx->ch_swskip, &ctx->ch_swres, &ctx->ch_swscr, &ctx->ch_ocoff, &ctx->ch_osoff, &ctx->ch_rco,
                     &ctx->ch_cso, &ctx->ch_rid, &ctx->ch_cfrac, &ctx->ch_out, &ctx->ch_seeds, &ctx->ch_regoff,
-                    &ctx->ch_regc})
+                    &ctx->ch_regc, &ctx->rp_regs, &ctx->rp_seq, &ctx->rp_soff, &ctx->rp_roff, &ctx->rp_n,
+                    &ctx->rp_stats})
     b->release();
   for (HostBuf* b : {&ctx->sdh_in, &ctx->chh_tot, &ctx->chh_rco, &ctx->chh_cso, &ctx->chh_chains, &ctx->chh_seeds, &ctx->chh_regs,
                      &ctx->chh_n})
@@ -988,6 +999,31 @@ int enqueue_chain2aln(bwagpu_ctx_t* ctx, Slot& s, const DevBatch& db, int lq_max
 
 }  // namespace
 
+namespace {
+// the post-processing pass over read spans in device memory (regpost.hip)
+int enqueue_regpost(bwagpu_ctx_t* ctx, const bwagpu_postopt_t& po, int32_t flags, int64_t id0, int32_t n_reads,
+                    const int64_t* seq_off, const uint8_t* seq, const int64_t* reg_off, const int32_t* rco,
+                    const int32_t* cso, bwagpu_alnreg_t* regs, int32_t* n, int64_t* stats, hipStream_t st) {
+  RegPostArgs a{};
+  a.n_reads = n_reads;
+  a.flags = flags;
+  a.id0 = id0;
+  a.po = po;
+  a.opt_b = ctx->opt_b;
+  a.seq_off = seq_off;
+  a.seq = seq;
+  a.reg_off = reg_off;
+  a.rco = rco;
+  a.cso = cso;
+  a.regs = regs;
+  a.n = n;
+  a.alt = ctx->has_alt ? ctx->ch_alt.as<uint8_t>() : nullptr;
+  a.stats = stats;
+  HIPC(launch_regpost(ctx->opt, ctx->ref, a, st), "regpost launch");
+  return BWAGPU_OK;
+}
+}  // namespace
+
 extern "C" {
 
 int bwagpu_abi_version(void) { return BWAGPU_ABI_VERSION; }
@@ -1140,6 +1176,16 @@ int bwagpu_chain2aln_submit(bwagpu_ctx_t* ctx, int slot, const bwagpu_batch_t* b
     (void)hipStreamSynchronize(st);
     return rc;
   }
+  if (ctx->post_flags && b->n_reads) {  // bwagpu_set_regs_post: in place on the slot layout, before the dense copy
+    rc = enqueue_regpost(ctx, ctx->post_opt, ctx->post_flags, ctx->post_id0, b->n_reads, db.seq_off, db.seq, nullptr,
+                         db.read_chain_off, db.chain_seed_off, s.d_out.as<bwagpu_alnreg_t>(), s.d_n.as<int32_t>(),
+                         s.d_stats.as<int64_t>(), st);
+    if (rc) {
+      (void)hipStreamSynchronize(st);
+      return rc;
+    }
+    ctx->post_id0 += b->n_reads;
+  }
   HIPC(hipEventRecord(s.ev2, st), "event");
   // the results: per-read offsets, then the regions densely into pinned memory
   // (the device writes them over PCIe: only the sum of n is moved, not the
@@ -1221,6 +1267,7 @@ int bwagpu_chain2aln_wait(bwagpu_ctx_t* ctx, int slot, bwagpu_alnreg_t* out_regs
   // regions are valid, the flagged ones were skipped (the caller's error path)
   if (out_n && s.n_reads) memcpy(out_n, s.h_n.p, sizeof(int32_t) * (size_t)s.n_reads);
   if (out_regs && s.n_seeds) expand_slots(s, out_regs);
+  if (st[ST_ERR] & ERR_POST) return fail(ctx, BWAGPU_E_UNSUPPORTED, "a patch candidate's window exceeds 4096 bases");
   if (st[ST_ERR] & ERR_RID)
     return fail(ctx, BWAGPU_E_RESULTS, "a chain's first seed is not inside contig chain_rid (bwamem.c:669 assert)");
   return BWAGPU_OK;
@@ -2639,6 +2686,13 @@ extern "C" int bwagpu_seqs2regions(bwagpu_ctx_t* ctx, const bwagpu_seedopt_t* so
   if ((rc = enqueue_chain2aln(ctx, s, db, lq, s.d_out.as<bwagpu_alnreg_t>(), s.d_n.as<int32_t>(),
                               s.d_stats.as<int64_t>(), st)))
     return rc;
+  if (ctx->post_flags) {  // bwagpu_set_regs_post: before the counts are scanned and the regions compacted
+    if ((rc = enqueue_regpost(ctx, ctx->post_opt, ctx->post_flags, ctx->post_id0, n_reads, db.seq_off, db.seq, nullptr,
+                              db.read_chain_off, db.chain_seed_off, s.d_out.as<bwagpu_alnreg_t>(),
+                              s.d_n.as<int32_t>(), s.d_stats.as<int64_t>(), st)))
+      return rc;
+    ctx->post_id0 += n_reads;
+  }
   HIPC(ctx->ch_regoff.ensure(sizeof(int64_t) * (nr + 1)), "hipMalloc");
   HIPC(launch_scan_i32(s.d_n.as<int32_t>(), ctx->ch_regoff.as<int64_t>(), n_reads, st), "scan launch");
   int64_t* tot = ctx->chh_tot.as<int64_t>();
@@ -2661,7 +2715,104 @@ extern "C" int bwagpu_seqs2regions(bwagpu_ctx_t* ctx, const bwagpu_seedopt_t* so
   *regs = ctx->chh_regs.as<const bwagpu_alnreg_t>();
   *n_regs = nreg;
   if (tot[6] & ERR_LEN) return fail(ctx, BWAGPU_E_UNSUPPORTED, "read longer than BWAGPU_MAX_READ_LEN");
+  if (tot[6] & ERR_POST) return fail(ctx, BWAGPU_E_UNSUPPORTED, "a patch candidate's window exceeds 4096 bases");
   if (tot[6] & ERR_RID)
     return fail(ctx, BWAGPU_E_RESULTS, "a chain's first seed is not inside contig chain_rid (bwamem.c:669 assert)");
+  return BWAGPU_OK;
+}
+
+// ------------------------------------------------------------------ region post-processing
+extern "C" int bwagpu_set_regs_post(bwagpu_ctx_t* ctx, const bwagpu_postopt_t* popt, int32_t flags,
+                                    int64_t id0_of_next_batch) {
+  if (!ctx) return BWAGPU_E_INVAL;
+  const int32_t all = BWAGPU_POST_DEDUP_PATCH | BWAGPU_POST_MARK_ALT | BWAGPU_POST_PRIMARY;
+  if (flags < 0 || (flags & ~all)) return fail(ctx, BWAGPU_E_INVAL, "unknown flag");
+  if (flags & BWAGPU_POST_PRIMARY) return fail(ctx, BWAGPU_E_UNSUPPORTED, "BWAGPU_POST_PRIMARY is not implemented");
+  if (flags && !post_opt_ok(popt)) return fail(ctx, BWAGPU_E_INVAL, "bad bwagpu_postopt_t");
+  if (popt) ctx->post_opt = *popt;
+  ctx->post_flags = flags;
+  ctx->post_id0 = id0_of_next_batch;
+  return BWAGPU_OK;
+}
+
+extern "C" int bwagpu_regs_post_device(bwagpu_ctx_t* ctx, const bwagpu_postopt_t* popt, int32_t flags, int64_t id0,
+                                       const bwagpu_batch_t* b, const int64_t* dev_reg_off, bwagpu_alnreg_t* dev_regs,
+                                       int32_t* dev_n, void* stream) {
+  if (!ctx || !b) return BWAGPU_E_INVAL;
+  const int32_t all = BWAGPU_POST_DEDUP_PATCH | BWAGPU_POST_MARK_ALT | BWAGPU_POST_PRIMARY;
+  if (flags < 0 || (flags & ~all)) return fail(ctx, BWAGPU_E_INVAL, "unknown flag");
+  if (flags & BWAGPU_POST_PRIMARY) return fail(ctx, BWAGPU_E_UNSUPPORTED, "BWAGPU_POST_PRIMARY is not implemented");
+  if (!post_opt_ok(popt)) return fail(ctx, BWAGPU_E_INVAL, "bad bwagpu_postopt_t");
+  if (b->n_reads < 0) return fail(ctx, BWAGPU_E_INVAL, "negative read count");
+  if (b->n_reads == 0 || flags == 0) return BWAGPU_OK;
+  if (!dev_regs || !dev_n || !b->seq_off || !b->seq || (!dev_reg_off && (!b->read_chain_off || !b->chain_seed_off)))
+    return fail(ctx, BWAGPU_E_INVAL, "NULL array");
+  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
+  hipStream_t st = (hipStream_t)stream;
+  if (!st) HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
+  return enqueue_regpost(ctx, *popt, flags, id0, b->n_reads, b->seq_off, b->seq, dev_reg_off, b->read_chain_off,
+                         b->chain_seed_off, dev_regs, dev_n, nullptr, st);
+}
+
+extern "C" int bwagpu_regs_post(bwagpu_ctx_t* ctx, const bwagpu_postopt_t* popt, int32_t flags, int64_t id0,
+                                int32_t n_reads, const int64_t* seq_off, const uint8_t* seq, const int64_t* reg_off,
+                                bwagpu_alnreg_t* regs, int32_t* n) {
+  if (!ctx) return BWAGPU_E_INVAL;
+  PostPlan plan;
+  const char* why = "";
+  int rc = post_check(popt, flags, n_reads, seq_off, seq, reg_off, regs, n, &plan, &why);
+  if (rc) return fail(ctx, rc, why);
+  if (n_reads == 0 || flags == 0 || plan.n_regs == 0) return BWAGPU_OK;
+  const size_t nr = (size_t)n_reads;
+  const size_t span = (size_t)(plan.hi - plan.lo), nseq = (size_t)(plan.seq_hi - plan.seq_lo);
+  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
+  hipStream_t st = nullptr;
+  HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
+  HIPC(ctx->rp_regs.ensure(sizeof(bwagpu_alnreg_t) * span), "hipMalloc");
+  HIPC(ctx->rp_seq.ensure(nseq + 1), "hipMalloc");
+  HIPC(ctx->rp_soff.ensure(sizeof(int64_t) * (nr + 1)), "hipMalloc");
+  HIPC(ctx->rp_roff.ensure(sizeof(int64_t) * nr), "hipMalloc");
+  HIPC(ctx->rp_n.ensure(sizeof(int32_t) * nr), "hipMalloc");
+  HIPC(ctx->rp_stats.ensure(sizeof(int64_t) * ST_N), "hipMalloc");
+  // offsets relative to what is copied: regs[lo ..), seq[seq_lo ..)
+  std::vector<int64_t> soff(nr + 1), roff(nr);
+  for (size_t r = 0; r <= nr; ++r) soff[r] = seq_off[r] - plan.seq_lo;
+  for (size_t r = 0; r < nr; ++r) roff[r] = n[r] ? reg_off[r] - plan.lo : 0;
+  HIPC(hipMemcpyAsync(ctx->rp_regs.p, regs + plan.lo, sizeof(bwagpu_alnreg_t) * span, hipMemcpyHostToDevice, st), "H2D");
+  if (nseq) HIPC(hipMemcpyAsync(ctx->rp_seq.p, seq + plan.seq_lo, nseq, hipMemcpyHostToDevice, st), "H2D");
+  HIPC(hipMemcpyAsync(ctx->rp_soff.p, soff.data(), sizeof(int64_t) * (nr + 1), hipMemcpyHostToDevice, st), "H2D");
+  HIPC(hipMemcpyAsync(ctx->rp_roff.p, roff.data(), sizeof(int64_t) * nr, hipMemcpyHostToDevice, st), "H2D");
+  HIPC(hipMemcpyAsync(ctx->rp_n.p, n, sizeof(int32_t) * nr, hipMemcpyHostToDevice, st), "H2D");
+  HIPC(hipMemsetAsync(ctx->rp_stats.p, 0, sizeof(int64_t) * ST_N, st), "memset");
+  HIPC(hipStreamSynchronize(st), "H2D");  // soff / roff are pageable locals
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  HIPC(hipEventCreate(&e0), "event");
+  HIPC(hipEventCreate(&e1), "event");
+  HIPC(hipEventRecord(e0, st), "event");
+  rc = enqueue_regpost(ctx, *popt, flags, id0, n_reads, ctx->rp_soff.as<int64_t>(), ctx->rp_seq.as<uint8_t>(),
+                       ctx->rp_roff.as<int64_t>(), nullptr, nullptr, ctx->rp_regs.as<bwagpu_alnreg_t>(),
+                       ctx->rp_n.as<int32_t>(), ctx->rp_stats.as<int64_t>(), st);
+  if (rc) {
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return rc;
+  }
+  HIPC(hipEventRecord(e1, st), "event");
+  int64_t hst[ST_N] = {};
+  HIPC(hipMemcpyAsync(regs + plan.lo, ctx->rp_regs.p, sizeof(bwagpu_alnreg_t) * span, hipMemcpyDeviceToHost, st), "D2H");
+  HIPC(hipMemcpyAsync(n, ctx->rp_n.p, sizeof(int32_t) * nr, hipMemcpyDeviceToHost, st), "D2H");
+  HIPC(hipMemcpyAsync(hst, ctx->rp_stats.p, sizeof(hst), hipMemcpyDeviceToHost, st), "D2H");
+  HIPC(hipStreamSynchronize(st), "regpost execution");
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, e0, e1);
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  Slot& s0 = ctx->slot[0];
+  s0.last = bwagpu_stats_t{};
+  s0.last.kernel_ms = ms;
+  s0.last.ext_calls = hst[ST_CALLS];
+  s0.last.h2d_bytes = (int64_t)(sizeof(bwagpu_alnreg_t) * span + nseq + sizeof(int64_t) * (2 * nr + 1) + sizeof(int32_t) * nr);
+  s0.last.d2h_bytes = (int64_t)(sizeof(bwagpu_alnreg_t) * span + sizeof(int32_t) * nr);
+  if (hst[ST_ERR] & ERR_POST) return fail(ctx, BWAGPU_E_UNSUPPORTED, "a patch candidate's window exceeds 4096 bases");
   return BWAGPU_OK;
 }

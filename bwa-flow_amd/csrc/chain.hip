@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include "chain.h"
+#include "ksort_dev.h"
 
 namespace bwagpu {
 namespace {
@@ -308,105 +309,6 @@ __device__ int intv2rid(const ChainArgs& a, int64_t rb, int64_t re) {  // bntseq
 struct ByW {
   __device__ bool operator()(int64_t x, int64_t y) const { return (x >> 32) > (y >> 32); }
 };
-template <class I, class LT>
-__device__ void c_insert(I* a, int s, int t, LT lt) {  // [s, t)
-  for (int i = s + 1; i < t; ++i)
-    for (int j = i; j > s && lt(a[j], a[j - 1]); --j) {
-      const int64_t x = a[j];
-      a[j] = a[j - 1];
-      a[j - 1] = x;
-    }
-}
-template <class I, class LT>
-__device__ void c_comb(I* a, int s, int n, LT lt) {  // a[s, s+n)
-  const double shrink = 1.2473309501039786540366528676643;
-  int gap = n;
-  bool swapped;
-  do {
-    if (gap > 2) {
-      gap = (int)(gap / shrink);
-      if (gap == 9 || gap == 10) gap = 11;
-    }
-    swapped = false;
-    for (int i = s; i < s + n - gap; ++i)
-      if (lt(a[i + gap], a[i])) {
-        const int64_t x = a[i];
-        a[i] = a[i + gap];
-        a[i + gap] = x;
-        swapped = true;
-      }
-  } while (swapped || gap > 2);
-  if (gap != 1) c_insert(a, s, s + n, lt);
-}
-template <class I, class LT>
-__device__ void c_introsort(int n, I* a, LT lt) {
-  if (n < 1) return;
-  if (n == 2) {
-    if (lt(a[1], a[0])) {
-      const int64_t x = a[0];
-      a[0] = a[1];
-      a[1] = x;
-    }
-    return;
-  }
-  int d = 2;
-  while ((1 << d) < n) ++d;
-  struct Frame {
-    int l, r, d;
-  } stack[64];
-  int top = 0, s = 0, t = n - 1;
-  d <<= 1;
-  for (;;) {
-    if (s < t) {
-      if (--d == 0) {
-        c_comb(a, s, t - s + 1, lt);
-        t = s;
-        continue;
-      }
-      int i = s, j = t, k = i + ((j - i) >> 1) + 1;
-      if (lt(a[k], a[i])) {
-        if (lt(a[k], a[j])) k = j;
-      } else {
-        k = lt(a[j], a[i]) ? i : j;
-      }
-      const int64_t rp = a[k];
-      if (k != t) {
-        a[k] = a[t];
-        a[t] = rp;
-      }
-      for (;;) {
-        do ++i; while (lt(a[i], rp));
-        do --j; while (i <= j && lt(rp, a[j]));
-        if (j <= i) break;
-        const int64_t x = a[i];
-        a[i] = a[j];
-        a[j] = x;
-      }
-      {
-        const int64_t x = a[i];
-        a[i] = a[t];
-        a[t] = x;
-      }
-      if (i - s > t - i) {
-        if (i - s > 16) stack[top++] = Frame{s, i - 1, d};
-        s = t - i > 16 ? i + 1 : t;
-      } else {
-        if (t - i > 16) stack[top++] = Frame{i + 1, t, d};
-        t = i - s > 16 ? i - 1 : s;
-      }
-    } else {
-      if (top == 0) {
-        c_insert(a, 0, n, lt);
-        return;
-      }
-      --top;
-      s = stack[top].l;
-      t = stack[top].r;
-      d = stack[top].d;
-    }
-  }
-}
-
 // ---- one read on one wave: mem_chain's loop, the kbtree traversal,
 // mem_chain_flt, the chains out.  Every lane runs the same sequential code
 // on the same data (wave-uniform: LDS reads broadcast, every lane stores the

@@ -113,6 +113,20 @@ class ChainsC(C.Structure):
                 ("seeds", C.c_void_p)]
 
 
+class PostOpt(C.Structure):
+    """bwagpu_postopt_t: mem_opt_t's fields of mem_sort_dedup_patch / mem_mark_primary_se"""
+    _fields_ = [("max_chain_gap", C.c_int32), ("mask_level_redun", C.c_float), ("mask_level", C.c_float),
+                ("pad_", C.c_int32)]
+
+
+POST_DEDUP_PATCH, POST_MARK_ALT, POST_PRIMARY = 1, 2, 4
+
+
+def default_postopt() -> PostOpt:
+    """mem_opt_init's defaults (bwa/bwamem.c:62-72)"""
+    return PostOpt(10000, 0.95, 0.50, 0)
+
+
 def default_chainopt() -> dict:
     """mem_opt_init's chaining defaults (bwa/bwamem.c:62-72)"""
     return dict(max_occ=500, max_chain_gap=10000, min_chain_weight=0, max_chain_extend=1 << 30, mask_level=0.5,
@@ -167,6 +181,11 @@ PROTOS = {
                                       C.POINTER(ChainsC)]),
     "bwagpu_seqs2regions": (C.c_int, [_VP, C.POINTER(SeedOpt), C.POINTER(ChainOpt), C.c_int32, _VP, _VP, _VP,
                                        C.POINTER(_VP), C.POINTER(C.c_int64)]),
+    "bwagpu_regs_post": (C.c_int, [_VP, C.POINTER(PostOpt), C.c_int32, C.c_int64, C.c_int32, _VP, _VP, _VP, _VP,
+                                    _VP]),
+    "bwagpu_regs_post_device": (C.c_int, [_VP, C.POINTER(PostOpt), C.c_int32, C.c_int64, C.POINTER(BatchC), _VP,
+                                           _VP, _VP, _VP]),
+    "bwagpu_set_regs_post": (C.c_int, [_VP, C.POINTER(PostOpt), C.c_int32, C.c_int64]),
 }
 
 _lib = None

@@ -401,6 +401,41 @@ class Engine:
             (C.c_char * (k * abi.ALNREG_DTYPE.itemsize)).from_address(regs.value), abi.ALNREG_DTYPE)
         return cnt[:n], (out.copy() if copy else out)
 
+    def regs_post(self, seq_off, seq, reg_off, regs, n, flags: int, id0: int = 0, popt: abi.PostOpt | None = None):
+        """RegionsToSam::compute's per-read head (src/Pipeline.cpp:560-575) on the device:
+        mem_sort_dedup_patch and the is_alt flag by flags (abi.POST_DEDUP_PATCH | abi.POST_MARK_ALT;
+        abi.POST_PRIMARY is reserved and refused).
+        Read r's n[r] regions at regs[reg_off[r]:] -> (regs, n) copies with the surviving
+        regions at the front of every span"""
+        seq_off = np.ascontiguousarray(seq_off, np.int64)
+        seq = np.ascontiguousarray(seq, np.uint8)
+        reg_off = np.ascontiguousarray(reg_off, np.int64)
+        regs = np.array(regs, abi.ALNREG_DTYPE, order="C")
+        n = np.array(n, np.int32, order="C")
+        nr = len(seq_off) - 1
+        if len(reg_off) < nr or len(n) < nr:
+            raise ValueError("regs_post: reg_off / n shorter than the batch")
+        po = abi.default_postopt() if popt is None else popt
+        self._check(self.lib.bwagpu_regs_post(self.ctx, C.byref(po), int(flags), int(id0), nr, _ptr(seq_off),
+                                              _ptr(seq), _ptr(reg_off), _ptr(regs), _ptr(n)), "regs_post")
+        return regs, n
+
+    def regs_post_device(self, dev_batch: abi.BatchC, dev_reg_off: int | None, dev_regs: int, dev_n: int,
+                         flags: int, id0: int = 0, popt: abi.PostOpt | None = None, stream: int | None = None):
+        """the same in place on device memory, asynchronous on stream (pointers as ints);
+        dev_reg_off=None: the slot layout bwagpu_chain2aln_device writes"""
+        po = abi.default_postopt() if popt is None else popt
+        self._check(self.lib.bwagpu_regs_post_device(self.ctx, C.byref(po), int(flags), int(id0), C.byref(dev_batch),
+                                                     C.c_void_p(dev_reg_off) if dev_reg_off else None,
+                                                     C.c_void_p(dev_regs), C.c_void_p(dev_n),
+                                                     C.c_void_p(stream) if stream else None), "regs_post_device")
+
+    def set_regs_post(self, flags: int, id0: int = 0, popt: abi.PostOpt | None = None):
+        """the switch (bwagpu_set_regs_post): flags != 0 makes chain2aln / submit+wait /
+        seqs2regions return post-processed regions; id0 = the next batch's first read id"""
+        po = abi.default_postopt() if popt is None else popt
+        self._check(self.lib.bwagpu_set_regs_post(self.ctx, C.byref(po), int(flags), int(id0)), "set_regs_post")
+
     def prof_start(self, max_launches: int):
         """time the next max_launches launches of the dominant extension kernel"""
         self._check(self.lib.bwagpu_prof_start(self.ctx, max_launches), "prof_start")

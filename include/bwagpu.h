@@ -61,6 +61,11 @@
  *   bwagpu_seqs2regions
  *       SeqsToChains + ChainsToRegions (src/Pipeline.cpp:110-121, 503-544) as
  *       one device call: reads in, mem_alnreg_v out.
+ *   bwagpu_regs_post / bwagpu_regs_post_device / bwagpu_set_regs_post
+ *       the per-read head of RegionsToSam::compute (src/Pipeline.cpp:560-575,
+ *       612): mem_sort_dedup_patch with mem_patch_reg (bwa/bwamem.c:415-498),
+ *       and the is_alt flag (Pipeline.cpp:570-574) for every read of a batch
+ *       (mem_mark_primary_se, Pipeline.cpp:612, stays on the host).
  *   bwagpu_last_error
  *       the what() of fpgaHangError / fpgaResultsError / std::runtime_error
  *       (src/util.h:16-32, OpenCLEnv.h:21-31).
@@ -486,6 +491,61 @@ int bwagpu_seqs2chains(bwagpu_ctx_t *ctx, const bwagpu_seedopt_t *sopt, const bw
 int bwagpu_seqs2regions(bwagpu_ctx_t *ctx, const bwagpu_seedopt_t *sopt, const bwagpu_chainopt_t *copt,
                         int32_t n_reads, const int64_t *seq_off, const uint8_t *seq, int32_t *out_n,
                         const bwagpu_alnreg_t **regs, int64_t *n_regs);
+
+/* ---- region post-processing: the head of RegionsToSam::compute on the device ---- */
+
+#define BWAGPU_POST_DEDUP_PATCH 1 /* mem_sort_dedup_patch (bwamem.c:446-498)                    */
+#define BWAGPU_POST_MARK_ALT    2 /* is_alt (Pipeline.cpp:570-574); needs bwagpu_set_alt; NULL
+                                     table = no ALT                                            */
+#define BWAGPU_POST_PRIMARY     4 /* mem_mark_primary_se (bwamem.c:530-567), id = id0 + read index:
+                                     reserved, every entry refuses it with BWAGPU_E_UNSUPPORTED */
+
+/* mem_opt_t's fields the pass reads besides the context's bwagpu_opt_t
+   (bwa/bwamem.h:38-52; defaults 10000, 0.95f, 0.50f, bwamem.c:62-72) */
+typedef struct {
+  int32_t max_chain_gap;
+  float mask_level_redun;
+  float mask_level;
+  int32_t pad_;
+} bwagpu_postopt_t;
+
+/* RegionsToSam::compute's loop over a batch (src/Pipeline.cpp:560-575): read r's n[r] regions at regs[reg_off[r] ..) are
+   replaced by the surviving ones at the front of that span, in the reference's
+   order and with every byte of every record as the reference leaves it
+   (n_comp and is_alt included); n[r] is updated.  id0 belongs to the reserved
+   BWAGPU_POST_PRIMARY and is not read.  Reads: nt4 bases at seq[seq_off[r] ..
+   seq_off[r+1]), at most BWAGPU_MAX_READ_LEN (a longer read returns
+   BWAGPU_E_UNSUPPORTED before any launch).  Negative counts, spans that
+   overlap and a region whose qb/qe lie outside its read return
+   BWAGPU_E_INVAL, also before any launch.  A pair that passes
+   mem_patch_reg's gates (bwamem.c:421-432) with b->re - a->rb over 4096 is
+   not evaluated: BWAGPU_E_UNSUPPORTED after the pass (mem_chain2aln's regions
+   stay far below).  Host buffers; blocking.  bwagpu_last_stats(ctx, 0):
+   kernel_ms of the pass, ext_calls = the patch DPs (bwa_gen_cigar2 calls that
+   reached ksw_global2). */
+int bwagpu_regs_post(bwagpu_ctx_t *ctx, const bwagpu_postopt_t *popt, int32_t flags, int64_t id0, int32_t n_reads,
+                     const int64_t *seq_off, const uint8_t *seq, const int64_t *reg_off, bwagpu_alnreg_t *regs,
+                     int32_t *n);
+/* The same on device memory, asynchronous on stream (hipStream_t, NULL = the
+   context's slot-0 stream): directly on what bwagpu_chain2aln_device wrote, on
+   the same stream.  dev_batch: host struct of device pointers (n_reads,
+   seq_off, seq; with dev_reg_off == NULL also read_chain_off and
+   chain_seed_off: read r's span then starts at
+   chain_seed_off[read_chain_off[r]], the slot layout).  dev_reg_off: int64 per
+   read.  Nothing is validated on the device path except what keeps the kernel
+   inside its buffers: a patch candidate outside its read (or over the 4096
+   window) is skipped. */
+int bwagpu_regs_post_device(bwagpu_ctx_t *ctx, const bwagpu_postopt_t *popt, int32_t flags, int64_t id0,
+                            const bwagpu_batch_t *dev_batch, const int64_t *dev_reg_off, bwagpu_alnreg_t *dev_regs,
+                            int32_t *dev_n, void *stream);
+/* The switch: with flags != 0, bwagpu_chain2aln_submit/_wait (and so
+   bwagpu_chain2aln, _results, _results_dense) and bwagpu_seqs2regions run the
+   pass on the device before the results leave it; the dense output is
+   compacted after the pass, so only surviving regions cross PCIe.  The next
+   batch takes id0_of_next_batch as its id0, every later one the previous id0
+   plus the previous batch's n_reads (RegionsToSam's start_idx).  flags == 0
+   (the default; popt may be NULL then) restores the plain results. */
+int bwagpu_set_regs_post(bwagpu_ctx_t *ctx, const bwagpu_postopt_t *popt, int32_t flags, int64_t id0_of_next_batch);
 
 /* Tuning, test and profiling entry points (bwagpu_debug_*, bwagpu_prof_*,
    bwagpu_ctx_ext_form / _row_bound, bwagpu_streams_concurrent) are declared
