@@ -25,6 +25,8 @@
 #include "reg2aln.h"
 #include "regpost.h"
 #include "regpost_host.h"
+#include "rescue.h"
+#include "rescue_host.h"
 #include "seed.h"
 #include "chain.h"
 #include "engine.h"
@@ -376,6 +378,19 @@ struct bwagpu_ctx {
   int32_t post_flags = 0;
   int64_t post_id0 = 0;
   DevBuf rp_regs, rp_seq, rp_soff, rp_roff, rp_n, rp_stats;
+  // paired ends (bwagpu_pestat*, bwagpu_mate_rescue*): the lists and counters of
+  // mem_pestat; mate rescue's per-pair work arrays, query pool, per-round task
+  // lists / window pools / results, and the host entries' copies of their arguments
+  DevBuf pe_isize, pe_cnt, pe_pes, pe_regs, pe_roff, pe_n;
+  DevBuf rs_pair, rs_soff, rs_tab, rs_toff, rs_boff, rs_qpool, rs_ctr, rs_scr;
+  DevBuf rs_tasks[kRescueMaxRounds], rs_tpool[kRescueMaxRounds], rs_res[kRescueMaxRounds];
+  DevBuf rs_in, rs_seq, rs_seqoff, rs_roff, rs_n, rs_ooff, rs_out, rs_outn, rs_status, rs_nsw;
+  int32_t rescue_drop = 0;  // bwagpu_debug_rescue_drop
+  // bwagpu_debug_rescue_times: per round of the last call, events before the plan,
+  // after it, after align2 and after the replay
+  hipEvent_t rs_ev[4 * kRescueMaxRounds] = {};
+  int rs_ev_rounds = 0;
+  hipStream_t rs_ev_stream = nullptr;
   // the FPGA wire format (bwagpu_sw_stream)
   DevBuf st_buf, st_start, st_q, st_tasks, st_lists, st_seen, st_ctr, st_out;
   // bwt_extend calls tier 1 spends on a read before tier 2 (one wave per read)
@@ -597,8 +612,15 @@ void destroy_ctx(bwagpu_ctx_t* ctx) {
                     &ctx->ch_swskip, &ctx->ch_swres, &ctx->ch_swscr, &ctx->ch_ocoff, &ctx->ch_osoff, &ctx->ch_rco,
                     &ctx->ch_cso, &ctx->ch_rid, &ctx->ch_cfrac, &ctx->ch_out, &ctx->ch_seeds, &ctx->ch_regoff,
                     &ctx->ch_regc, &ctx->rp_regs, &ctx->rp_seq, &ctx->rp_soff, &ctx->rp_roff, &ctx->rp_n,
-                    &ctx->rp_stats})
+                    &ctx->rp_stats, &ctx->pe_isize, &ctx->pe_cnt, &ctx->pe_pes, &ctx->pe_regs, &ctx->pe_roff, &ctx->pe_n,
+                    &ctx->rs_pair, &ctx->rs_soff, &ctx->rs_tab, &ctx->rs_toff, &ctx->rs_boff, &ctx->rs_qpool,
+                    &ctx->rs_ctr, &ctx->rs_scr, &ctx->rs_in, &ctx->rs_seq, &ctx->rs_seqoff, &ctx->rs_roff, &ctx->rs_n,
+                    &ctx->rs_ooff, &ctx->rs_out, &ctx->rs_outn, &ctx->rs_status, &ctx->rs_nsw})
     b->release();
+  for (hipEvent_t e : ctx->rs_ev)
+    if (e) (void)hipEventDestroy(e);
+  for (int k = 0; k < kRescueMaxRounds; ++k)
+    for (DevBuf* b : {&ctx->rs_tasks[k], &ctx->rs_tpool[k], &ctx->rs_res[k]}) b->release();
   for (HostBuf* b : {&ctx->sdh_in, &ctx->chh_tot, &ctx->chh_rco, &ctx->chh_cso, &ctx->chh_chains, &ctx->chh_seeds, &ctx->chh_regs,
                      &ctx->chh_n})
     b->release();
@@ -2814,5 +2836,332 @@ extern "C" int bwagpu_regs_post(bwagpu_ctx_t* ctx, const bwagpu_postopt_t* popt,
   s0.last.h2d_bytes = (int64_t)(sizeof(bwagpu_alnreg_t) * span + nseq + sizeof(int64_t) * (2 * nr + 1) + sizeof(int32_t) * nr);
   s0.last.d2h_bytes = (int64_t)(sizeof(bwagpu_alnreg_t) * span + sizeof(int32_t) * nr);
   if (hst[ST_ERR] & ERR_POST) return fail(ctx, BWAGPU_E_UNSUPPORTED, "a patch candidate's window exceeds 4096 bases");
+  return BWAGPU_OK;
+}
+
+// ------------------------------------------------------------------ paired ends: mem_pestat, mate rescue
+namespace {
+
+// mem_pestat over spans in device memory (rescue.hip); pes: 4 records in device memory
+int enqueue_pestat(bwagpu_ctx_t* ctx, const bwagpu_pairopt_t& po, int32_t n_reads, const int64_t* reg_off,
+                   const bwagpu_alnreg_t* regs, const int32_t* n, bwagpu_pestat_t* pes, hipStream_t st) {
+  PestatArgs a{};
+  a.n_pairs = n_reads >> 1;
+  a.cap = 1;
+  while (a.cap < a.n_pairs) a.cap <<= 1;
+  a.po = po;
+  a.reg_off = reg_off;
+  a.regs = regs;
+  a.n = n;
+  HIPC(ctx->pe_isize.ensure(sizeof(uint64_t) * 4 * (size_t)a.cap), "hipMalloc");
+  HIPC(ctx->pe_cnt.ensure(sizeof(int32_t) * 4), "hipMalloc");
+  HIPC(hipMemsetAsync(ctx->pe_cnt.p, 0, sizeof(int32_t) * 4, st), "memset");
+  a.isize = ctx->pe_isize.as<uint64_t>();
+  a.cnt = ctx->pe_cnt.as<int32_t>();
+  a.pes = pes;
+  HIPC(launch_pestat(ctx->opt, ctx->ref, a, st), "pestat launch");
+  return BWAGPU_OK;
+}
+
+struct RescueRun {
+  int rounds = 0;
+  int64_t tasks = 0;  // ksw_align2 tasks computed over all rounds
+  float ms = 0;
+};
+
+// Mate rescue over device memory.  The counts of every round come to the host
+// (stream waits); the last round's replay is left running on st.
+int enqueue_rescue(bwagpu_ctx_t* ctx, const bwagpu_pairopt_t& po, const bwagpu_pestat_t* dev_pes, int32_t n_reads,
+                   int64_t seq_bytes, const int64_t* seq_off, const uint8_t* seq, const int64_t* reg_off,
+                   const bwagpu_alnreg_t* regs, const int32_t* n, const int64_t* out_off, bwagpu_alnreg_t* out_regs,
+                   int32_t* out_n, int32_t* status, int32_t* n_sw, hipStream_t st, RescueRun* run) {
+  const int32_t np = n_reads >> 1;
+  const size_t npz = (size_t)np;
+  RescueArgs a{};
+  a.n_pairs = np;
+  a.po = po;
+  a.pes = dev_pes;
+  a.seq_off = seq_off;
+  a.seq = seq;
+  a.reg_off = reg_off;
+  a.regs = regs;
+  a.n = n;
+  a.out_off = out_off;
+  a.out_regs = out_regs;
+  a.out_n = out_n;
+  a.status = status;
+  a.n_sw = n_sw;
+  // per pair: pstate | nb0 | nslot | ntask | tbytes
+  HIPC(ctx->rs_pair.ensure(sizeof(int32_t) * 5 * npz), "hipMalloc");
+  HIPC(ctx->rs_soff.ensure(sizeof(int64_t) * (npz + 1)), "hipMalloc");
+  HIPC(ctx->rs_toff.ensure(sizeof(int64_t) * (npz + 1)), "hipMalloc");
+  HIPC(ctx->rs_boff.ensure(sizeof(int64_t) * (npz + 1)), "hipMalloc");
+  HIPC(ctx->rs_qpool.ensure(2 * (size_t)seq_bytes + 64), "hipMalloc");
+  HIPC(ctx->rs_ctr.ensure(sizeof(int32_t) * RC_WORDS), "hipMalloc");
+  HIPC(ctx->chh_tot.ensure(sizeof(int64_t) * 16), "hipHostMalloc");
+  a.pstate = ctx->rs_pair.as<int32_t>();
+  a.nb0 = a.pstate + npz;
+  a.nslot = a.nb0 + npz;
+  a.ntask = a.nslot + npz;
+  a.tbytes = a.ntask + npz;
+  a.slot_off = ctx->rs_soff.as<int64_t>();
+  a.task_off = ctx->rs_toff.as<int64_t>();
+  a.tb_off = ctx->rs_boff.as<int64_t>();
+  a.qpool = ctx->rs_qpool.as<uint8_t>();
+  a.rc_base = seq_bytes;
+  a.ctr = ctx->rs_ctr.as<int32_t>();
+  int64_t* tot = ctx->chh_tot.as<int64_t>();
+  ctx->rs_ev_rounds = 0;
+  ctx->rs_ev_stream = st;
+  HIPC(launch_rescue_pool(a, st), "rescue_pool launch");
+  HIPC(launch_rescue_init(ctx->opt, a, st), "rescue_init launch");
+  HIPC(launch_scan_i32(a.nslot, ctx->rs_soff.as<int64_t>(), np, st), "scan launch");
+  HIPC(hipMemcpyAsync(tot + 8, ctx->rs_soff.as<int64_t>() + np, sizeof(int64_t), hipMemcpyDeviceToHost, st), "D2H");
+  HIPC(hipStreamSynchronize(st), "sync");
+  const int64_t S = tot[8];
+  HIPC(ctx->rs_tab.ensure(sizeof(int32_t) * (size_t)std::max<int64_t>(S, 1)), "hipMalloc");
+  HIPC(hipMemsetAsync(ctx->rs_tab.p, 0xff, sizeof(int32_t) * (size_t)std::max<int64_t>(S, 1), st), "memset");  // RS_NONE
+  a.tab = ctx->rs_tab.as<int32_t>();
+  HIPC(hipMemsetAsync(a.ctr, 0, sizeof(int32_t) * RC_WORDS, st), "memset");
+  for (int round = 0; round < po.max_rounds; ++round) {
+    a.round = round;
+    a.drop = round == 0 ? ctx->rescue_drop : 0;
+    HIPC(hipMemsetAsync(a.ctr + RC_PENDING, 0, sizeof(int32_t), st), "memset");
+    hipEvent_t* ev = ctx->rs_ev + 4 * round;
+    for (int k = 0; k < 4; ++k)
+      if (!ev[k]) HIPC(hipEventCreate(&ev[k]), "hipEventCreate");
+    HIPC(hipEventRecord(ev[0], st), "event");
+    HIPC(launch_rescue_plan(ctx->opt, ctx->ref, a, false, st), "rescue_plan launch");
+    HIPC(launch_scan_i32(a.ntask, ctx->rs_toff.as<int64_t>(), np, st), "scan launch");
+    HIPC(launch_scan_i32(a.tbytes, ctx->rs_boff.as<int64_t>(), np, st), "scan launch");
+    HIPC(hipMemcpyAsync(tot + 9, ctx->rs_toff.as<int64_t>() + np, sizeof(int64_t), hipMemcpyDeviceToHost, st), "D2H");
+    HIPC(hipMemcpyAsync(tot + 10, ctx->rs_boff.as<int64_t>() + np, sizeof(int64_t), hipMemcpyDeviceToHost, st), "D2H");
+    HIPC(hipStreamSynchronize(st), "sync");
+    const int64_t T = tot[9], B = tot[10];
+    if (T >= (int64_t)1 << kRescueIdxBits) return fail(ctx, BWAGPU_E_UNSUPPORTED, "too many rescue alignments in one batch");
+    if (T) {
+      HIPC(ctx->rs_tasks[round].ensure(sizeof(bwagpu_align2_task_t) * (size_t)T), "hipMalloc");
+      HIPC(ctx->rs_tpool[round].ensure((size_t)B + 64), "hipMalloc");
+      HIPC(ctx->rs_res[round].ensure(sizeof(bwagpu_kswr_t) * (size_t)T), "hipMalloc");
+      HIPC(ctx->rs_scr.ensure(8 * ((size_t)B + (size_t)T)), "hipMalloc");
+      a.tasks = ctx->rs_tasks[round].as<bwagpu_align2_task_t>();
+      a.tpool = ctx->rs_tpool[round].as<uint8_t>();
+      a.res[round] = ctx->rs_res[round].as<bwagpu_kswr_t>();
+      HIPC(launch_rescue_plan(ctx->opt, ctx->ref, a, true, st), "rescue_plan launch");
+      HIPC(hipEventRecord(ev[1], st), "event");
+      if (int rc = bwagpu_align2_device(ctx, (int32_t)T, a.tasks, a.qpool, a.tpool, ctx->rs_res[round].as<bwagpu_kswr_t>(),
+                                        ctx->rs_scr.p, st))
+        return rc;
+      run->tasks += T;
+    } else {
+      HIPC(hipEventRecord(ev[1], st), "event");
+    }
+    HIPC(hipEventRecord(ev[2], st), "event");
+    HIPC(launch_rescue_apply(ctx->opt, ctx->ref, a, st), "rescue_apply launch");
+    HIPC(hipEventRecord(ev[3], st), "event");
+    run->rounds = ctx->rs_ev_rounds = round + 1;
+    if (round + 1 == po.max_rounds) break;
+    HIPC(hipMemcpyAsync(tot + 11, a.ctr, sizeof(int32_t) * 2, hipMemcpyDeviceToHost, st), "D2H");
+    HIPC(hipStreamSynchronize(st), "sync");
+    if (reinterpret_cast<const int32_t*>(tot + 11)[RC_PENDING] == 0) break;
+  }
+  return BWAGPU_OK;
+}
+
+}  // namespace
+
+extern "C" int bwagpu_debug_rescue_drop(bwagpu_ctx_t* ctx, int32_t k) {
+  if (!ctx || k < 0) return BWAGPU_E_INVAL;
+  ctx->rescue_drop = k;
+  return BWAGPU_OK;
+}
+
+extern "C" int bwagpu_debug_rescue_times(bwagpu_ctx_t* ctx, double* out) {
+  if (!ctx || !out) return BWAGPU_E_INVAL;
+  out[0] = out[1] = out[2] = 0;
+  out[3] = ctx->rs_ev_rounds;
+  if (ctx->rs_ev_rounds == 0) return BWAGPU_OK;
+  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
+  HIPC(hipEventSynchronize(ctx->rs_ev[4 * (ctx->rs_ev_rounds - 1) + 3]), "event sync");
+  for (int r = 0; r < ctx->rs_ev_rounds; ++r)
+    for (int k = 0; k < 3; ++k) {
+      float ms = 0;
+      HIPC(hipEventElapsedTime(&ms, ctx->rs_ev[4 * r + k], ctx->rs_ev[4 * r + k + 1]), "event time");
+      out[k] += ms;
+    }
+  return BWAGPU_OK;
+}
+
+extern "C" int bwagpu_pestat_device(bwagpu_ctx_t* ctx, const bwagpu_pairopt_t* popt, int32_t n_reads,
+                                    const int64_t* dev_reg_off, const bwagpu_alnreg_t* dev_regs, const int32_t* dev_n,
+                                    bwagpu_pestat_t* dev_pes, void* stream) {
+  if (!ctx) return BWAGPU_E_INVAL;
+  if (!pair_opt_ok(popt)) return fail(ctx, BWAGPU_E_INVAL, "bad bwagpu_pairopt_t");
+  if (n_reads < 0) return fail(ctx, BWAGPU_E_INVAL, "negative read count");
+  if (!dev_pes || ((n_reads >> 1) && (!dev_reg_off || !dev_regs || !dev_n))) return fail(ctx, BWAGPU_E_INVAL, "NULL array");
+  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
+  hipStream_t st = (hipStream_t)stream;
+  if (!st) HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
+  return enqueue_pestat(ctx, *popt, n_reads, dev_reg_off, dev_regs, dev_n, dev_pes, st);
+}
+
+extern "C" int bwagpu_pestat(bwagpu_ctx_t* ctx, const bwagpu_pairopt_t* popt, int32_t n_reads, const int64_t* reg_off,
+                             const bwagpu_alnreg_t* regs, const int32_t* n, bwagpu_pestat_t* pes) {
+  if (!ctx) return BWAGPU_E_INVAL;
+  RescuePlan plan;
+  const char* why = "";
+  int rc = pestat_check(popt, n_reads, reg_off, regs, n, pes, &plan, &why);
+  if (rc) return fail(ctx, rc, why);
+  const size_t nr = (size_t)(n_reads & ~1), span = (size_t)(plan.hi - plan.lo);
+  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
+  hipStream_t st = nullptr;
+  HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
+  HIPC(ctx->pe_regs.ensure(sizeof(bwagpu_alnreg_t) * std::max<size_t>(span, 1)), "hipMalloc");
+  HIPC(ctx->pe_roff.ensure(sizeof(int64_t) * std::max<size_t>(nr, 1)), "hipMalloc");
+  HIPC(ctx->pe_n.ensure(sizeof(int32_t) * std::max<size_t>(nr, 1)), "hipMalloc");
+  HIPC(ctx->pe_pes.ensure(sizeof(bwagpu_pestat_t) * 4), "hipMalloc");
+  std::vector<int64_t> roff(nr);
+  for (size_t r = 0; r < nr; ++r) roff[r] = n[r] ? reg_off[r] - plan.lo : 0;
+  if (span) HIPC(hipMemcpyAsync(ctx->pe_regs.p, regs + plan.lo, sizeof(bwagpu_alnreg_t) * span, hipMemcpyHostToDevice, st), "H2D");
+  if (nr) {
+    HIPC(hipMemcpyAsync(ctx->pe_roff.p, roff.data(), sizeof(int64_t) * nr, hipMemcpyHostToDevice, st), "H2D");
+    HIPC(hipMemcpyAsync(ctx->pe_n.p, n, sizeof(int32_t) * nr, hipMemcpyHostToDevice, st), "H2D");
+  }
+  HIPC(hipStreamSynchronize(st), "H2D");  // roff is a pageable local
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  HIPC(hipEventCreate(&e0), "event");
+  HIPC(hipEventCreate(&e1), "event");
+  HIPC(hipEventRecord(e0, st), "event");
+  rc = enqueue_pestat(ctx, *popt, (int32_t)nr, ctx->pe_roff.as<int64_t>(), ctx->pe_regs.as<bwagpu_alnreg_t>(),
+                      ctx->pe_n.as<int32_t>(), ctx->pe_pes.as<bwagpu_pestat_t>(), st);
+  if (rc) {
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return rc;
+  }
+  HIPC(hipEventRecord(e1, st), "event");
+  HIPC(hipMemcpyAsync(pes, ctx->pe_pes.p, sizeof(bwagpu_pestat_t) * 4, hipMemcpyDeviceToHost, st), "D2H");
+  HIPC(hipStreamSynchronize(st), "pestat execution");
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, e0, e1);
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  Slot& s0 = ctx->slot[0];
+  s0.last = bwagpu_stats_t{};
+  s0.last.kernel_ms = ms;
+  return BWAGPU_OK;
+}
+
+extern "C" int bwagpu_mate_rescue_device(bwagpu_ctx_t* ctx, const bwagpu_pairopt_t* popt, const bwagpu_pestat_t* dev_pes,
+                                         const bwagpu_batch_t* b, const int64_t* dev_reg_off,
+                                         const bwagpu_alnreg_t* dev_regs, const int32_t* dev_n,
+                                         const int64_t* dev_out_off, bwagpu_alnreg_t* dev_out_regs, int32_t* dev_out_n,
+                                         int32_t* dev_status, int32_t* dev_n_sw, void* stream) {
+  if (!ctx || !b) return BWAGPU_E_INVAL;
+  if (!pair_opt_ok(popt)) return fail(ctx, BWAGPU_E_INVAL, "bad bwagpu_pairopt_t");
+  if (b->n_reads < 0) return fail(ctx, BWAGPU_E_INVAL, "negative read count");
+  if (b->n_reads & 1) return fail(ctx, BWAGPU_E_INVAL, "odd read count: reads 2i and 2i+1 are a pair");
+  if (!dev_pes) return fail(ctx, BWAGPU_E_INVAL, "NULL pes");
+  if (const char* why = align2_opt_unsupported(ctx->opt)) return fail(ctx, BWAGPU_E_UNSUPPORTED, why);
+  if (b->n_reads == 0) return BWAGPU_OK;
+  if (!b->seq_off || !b->seq || b->seq_bytes < 0 || !dev_reg_off || !dev_regs || !dev_n || !dev_out_off ||
+      !dev_out_regs || !dev_out_n || !dev_status || !dev_n_sw)
+    return fail(ctx, BWAGPU_E_INVAL, "NULL array");
+  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
+  hipStream_t st = (hipStream_t)stream;
+  if (!st) HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
+  bwagpu_pestat_t hp[4];  // the windows' size bound needs the ranges here
+  HIPC(hipMemcpyAsync(hp, dev_pes, sizeof(hp), hipMemcpyDeviceToHost, st), "D2H");
+  HIPC(hipStreamSynchronize(st), "sync");
+  const char* why = "";
+  if (int rc = pes_check(hp, &why)) return fail(ctx, rc, why);
+  RescueRun run;
+  int rc = enqueue_rescue(ctx, *popt, dev_pes, b->n_reads, b->seq_bytes, b->seq_off, b->seq, dev_reg_off, dev_regs,
+                          dev_n, dev_out_off, dev_out_regs, dev_out_n, dev_status, dev_n_sw, st, &run);
+  if (rc) return rc;
+  Slot& s0 = ctx->slot[0];
+  s0.last = bwagpu_stats_t{};
+  s0.last.ext_calls = run.tasks;
+  s0.last.rows = run.rounds;
+  return BWAGPU_OK;
+}
+
+extern "C" int bwagpu_mate_rescue(bwagpu_ctx_t* ctx, const bwagpu_pairopt_t* popt, const bwagpu_pestat_t* pes,
+                                  int32_t n_reads, const int64_t* seq_off, const uint8_t* seq, const int64_t* reg_off,
+                                  const bwagpu_alnreg_t* regs, const int32_t* n, const int64_t* out_off,
+                                  bwagpu_alnreg_t* out_regs, int32_t* out_n, int32_t* status, int32_t* n_sw) {
+  if (!ctx) return BWAGPU_E_INVAL;
+  RescuePlan plan;
+  const char* why = "";
+  int rc = rescue_check(popt, pes, n_reads, seq_off, seq, reg_off, regs, n, out_off, out_regs, out_n, status, n_sw,
+                        &plan, &why);
+  if (rc) return fail(ctx, rc, why);
+  if (const char* w = align2_opt_unsupported(ctx->opt)) return fail(ctx, BWAGPU_E_UNSUPPORTED, w);
+  if (n_reads == 0) return BWAGPU_OK;
+  const size_t nr = (size_t)n_reads, np = nr / 2;
+  const size_t span = (size_t)(plan.hi - plan.lo), ospan = (size_t)(plan.out_hi - plan.out_lo),
+               nseq = (size_t)(plan.seq_hi - plan.seq_lo);
+  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
+  hipStream_t st = nullptr;
+  HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
+  HIPC(ctx->rs_in.ensure(sizeof(bwagpu_alnreg_t) * std::max<size_t>(span, 1)), "hipMalloc");
+  HIPC(ctx->rs_out.ensure(sizeof(bwagpu_alnreg_t) * std::max<size_t>(ospan, 1)), "hipMalloc");
+  HIPC(ctx->rs_seq.ensure(nseq + 1), "hipMalloc");
+  HIPC(ctx->rs_seqoff.ensure(sizeof(int64_t) * (nr + 1)), "hipMalloc");
+  HIPC(ctx->rs_roff.ensure(sizeof(int64_t) * nr), "hipMalloc");
+  HIPC(ctx->rs_ooff.ensure(sizeof(int64_t) * (nr + 1)), "hipMalloc");
+  HIPC(ctx->rs_n.ensure(sizeof(int32_t) * nr), "hipMalloc");
+  HIPC(ctx->rs_outn.ensure(sizeof(int32_t) * nr), "hipMalloc");
+  HIPC(ctx->rs_status.ensure(sizeof(int32_t) * np), "hipMalloc");
+  HIPC(ctx->rs_nsw.ensure(sizeof(int32_t) * np), "hipMalloc");
+  HIPC(ctx->pe_pes.ensure(sizeof(bwagpu_pestat_t) * 4), "hipMalloc");
+  // offsets relative to what is copied
+  std::vector<int64_t> soff(nr + 1), roff(nr), ooff(nr + 1);
+  for (size_t r = 0; r <= nr; ++r) soff[r] = seq_off[r] - plan.seq_lo, ooff[r] = out_off[r] - plan.out_lo;
+  for (size_t r = 0; r < nr; ++r) roff[r] = n[r] ? reg_off[r] - plan.lo : 0;
+  if (span) HIPC(hipMemcpyAsync(ctx->rs_in.p, regs + plan.lo, sizeof(bwagpu_alnreg_t) * span, hipMemcpyHostToDevice, st), "H2D");
+  if (nseq) HIPC(hipMemcpyAsync(ctx->rs_seq.p, seq + plan.seq_lo, nseq, hipMemcpyHostToDevice, st), "H2D");
+  HIPC(hipMemcpyAsync(ctx->rs_seqoff.p, soff.data(), sizeof(int64_t) * (nr + 1), hipMemcpyHostToDevice, st), "H2D");
+  HIPC(hipMemcpyAsync(ctx->rs_roff.p, roff.data(), sizeof(int64_t) * nr, hipMemcpyHostToDevice, st), "H2D");
+  HIPC(hipMemcpyAsync(ctx->rs_ooff.p, ooff.data(), sizeof(int64_t) * (nr + 1), hipMemcpyHostToDevice, st), "H2D");
+  HIPC(hipMemcpyAsync(ctx->rs_n.p, n, sizeof(int32_t) * nr, hipMemcpyHostToDevice, st), "H2D");
+  HIPC(hipMemcpyAsync(ctx->pe_pes.p, pes, sizeof(bwagpu_pestat_t) * 4, hipMemcpyHostToDevice, st), "H2D");
+  HIPC(hipStreamSynchronize(st), "H2D");  // the offset vectors are pageable locals
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  HIPC(hipEventCreate(&e0), "event");
+  HIPC(hipEventCreate(&e1), "event");
+  HIPC(hipEventRecord(e0, st), "event");
+  RescueRun run;
+  rc = enqueue_rescue(ctx, *popt, ctx->pe_pes.as<bwagpu_pestat_t>(), n_reads, (int64_t)nseq, ctx->rs_seqoff.as<int64_t>(),
+                      ctx->rs_seq.as<uint8_t>(), ctx->rs_roff.as<int64_t>(), ctx->rs_in.as<bwagpu_alnreg_t>(),
+                      ctx->rs_n.as<int32_t>(), ctx->rs_ooff.as<int64_t>(), ctx->rs_out.as<bwagpu_alnreg_t>(),
+                      ctx->rs_outn.as<int32_t>(), ctx->rs_status.as<int32_t>(), ctx->rs_nsw.as<int32_t>(), st, &run);
+  if (rc) {
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return rc;
+  }
+  HIPC(hipEventRecord(e1, st), "event");
+  int32_t hctr[RC_WORDS] = {};
+  // only the regions of every span that the pass wrote: spans are copied back whole
+  if (ospan)
+    HIPC(hipMemcpyAsync(out_regs + plan.out_lo, ctx->rs_out.p, sizeof(bwagpu_alnreg_t) * ospan, hipMemcpyDeviceToHost, st), "D2H");
+  HIPC(hipMemcpyAsync(out_n, ctx->rs_outn.p, sizeof(int32_t) * nr, hipMemcpyDeviceToHost, st), "D2H");
+  HIPC(hipMemcpyAsync(status, ctx->rs_status.p, sizeof(int32_t) * np, hipMemcpyDeviceToHost, st), "D2H");
+  HIPC(hipMemcpyAsync(n_sw, ctx->rs_nsw.p, sizeof(int32_t) * np, hipMemcpyDeviceToHost, st), "D2H");
+  HIPC(hipMemcpyAsync(hctr, ctx->rs_ctr.p, sizeof(hctr), hipMemcpyDeviceToHost, st), "D2H");
+  HIPC(hipStreamSynchronize(st), "mate rescue execution");
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, e0, e1);
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  Slot& s0 = ctx->slot[0];
+  s0.last = bwagpu_stats_t{};
+  s0.last.kernel_ms = ms;
+  s0.last.ext_calls = run.tasks;
+  s0.last.rows = run.rounds;
+  s0.last.cells = hctr[RC_USED];
+  s0.last.h2d_bytes = (int64_t)(sizeof(bwagpu_alnreg_t) * span + nseq + sizeof(int64_t) * (3 * nr + 2) + sizeof(int32_t) * nr);
+  s0.last.d2h_bytes = (int64_t)(sizeof(bwagpu_alnreg_t) * ospan + sizeof(int32_t) * (nr + 2 * np));
   return BWAGPU_OK;
 }

@@ -33,40 +33,17 @@
 #include "global_dp.h"
 #include "ksort_dev.h"
 #include "regpost.h"
+#include "regwalk.h"
 #include "wave_ops.h"
 
 namespace bwagpu {
 
 namespace {
 
-using R = bwagpu_alnreg_t;
-static_assert(sizeof(R) == 88, "mem_alnreg_t layout");
-
 constexpr int kPostReadsPerWave = 8;
 constexpr int kPostLdsRegs = 32;  // records per wave held in LDS
 constexpr int kPostQCap = 1024;   // BWAGPU_MAX_READ_LEN + 1
 constexpr int kPostWaveLds = kPostLdsRegs * (int)sizeof(R) + kPostQCap + kPostRefCap;
-constexpr uint32_t kCompMask = 0x3fffffffu;
-
-__device__ __forceinline__ int alt_of(const R& x) { return (int)x.n_comp_is_alt >> 30; }  // int is_alt:2
-
-struct LtRe {  // alnreg_slt2, bwamem.c:400
-  __device__ bool operator()(const R& x, const R& y) const { return x.re < y.re; }
-};
-struct LtScore {  // alnreg_slt, bwamem.c:403
-  __device__ bool operator()(const R& x, const R& y) const {
-    return x.score > y.score || (x.score == y.score && (x.rb < y.rb || (x.rb == y.rb && x.qb < y.qb)));
-  }
-};
-// The records are reached through a generic pointer (flat accesses, LDS or HBM)
-// and copied with ds accesses; the two kinds reach LDS by different paths, so a
-// phase change waits for every outstanding access of both.
-__device__ __forceinline__ void post_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_s_waitcnt(0);  // vmcnt(0) expcnt(0) lgkmcnt(0)
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 struct PostCtx {
   int64_t qoff;   // the read's first base in RegPostArgs::seq
@@ -156,67 +133,10 @@ __device__ int patch_reg(const DevOpt& o, const DevRef& ref, const RegPostArgs& 
   return score;
 }
 
-// mem_sort_dedup_patch's body for n >= 2 (bwamem.c:450-497)
+// mem_sort_dedup_patch's body for n >= 2 (regwalk.h) with mem_patch_reg
 __device__ int sort_dedup_patch(const DevOpt& o, const DevRef& ref, const RegPostArgs& g, int n, R* a, PostCtx& c) {
-  const int gap = g.po.max_chain_gap;
-  const float red = g.po.mask_level_redun;
-  c_introsort(n, a, LtRe{});  // by the END position
-  for (int i = 0; i < n; ++i) a[i].n_comp_is_alt = (a[i].n_comp_is_alt & ~kCompMask) | 1u;
-  for (int i = 1; i < n; ++i) {
-    R* p = a + i;
-    if (uni(p->rid) != uni(a[i - 1].rid) || uni64(p->rb) >= uni64(a[i - 1].re) + gap) continue;
-    for (int j = i - 1; j >= 0; --j) {
-      R* q = a + j;
-      const int64_t prb = uni64(p->rb), qre = uni64(q->re);
-      if (!(uni(p->rid) == uni(q->rid) && prb < qre + gap)) break;
-      const int qqb = uni(q->qb), qqe = uni(q->qe);
-      if (qqe == qqb) continue;  // a[j] has been excluded
-      const int pqb = uni(p->qb), pqe = uni(p->qe);
-      const int64_t pre = uni64(p->re), qrb = uni64(q->rb);
-      const int64_t orr = qre - prb;
-      const int64_t oq = qqb < pqb ? qqe - pqb : pqe - qqb;
-      const int64_t mr = qre - qrb < pre - prb ? qre - qrb : pre - prb;
-      const int64_t mq = qqe - qqb < pqe - pqb ? qqe - qqb : pqe - pqb;
-      int score, w = 0;
-      if ((float)orr > red * (float)mr && (float)oq > red * (float)mq) {  // one of the hits is redundant
-        if (uni(p->score) < uni(q->score)) {
-          p->qe = pqb;
-          break;
-        } else {
-          q->qe = qqb;
-        }
-      } else if (qrb < prb && (score = patch_reg(o, ref, g, q, p, c, &w)) > 0) {  // merge q into p
-        const uint32_t pc = p->n_comp_is_alt, qc = q->n_comp_is_alt;
-        p->n_comp_is_alt = (pc & ~kCompMask) | (((pc & kCompMask) + (qc & kCompMask) + 1u) & kCompMask);
-        p->seedcov = max(p->seedcov, q->seedcov);
-        p->sub = max(p->sub, q->sub);
-        p->csub = max(p->csub, q->csub);
-        p->qb = qqb;
-        p->rb = qrb;
-        p->truesc = p->score = score;
-        p->w = w;
-        q->qb = qqe;
-      }
-    }
-  }
-  int m = 0;
-  for (int i = 0; i < n; ++i)  // exclude the marked hits
-    if (uni(a[i].qe) > uni(a[i].qb)) {
-      if (m != i) a[m] = a[i];
-      ++m;
-    }
-  n = m;
-  if (n == 0) return 0;
-  c_introsort(n, a, LtScore{});
-  for (int i = 1; i < n; ++i)  // mark identical hits
-    if (a[i].score == a[i - 1].score && a[i].rb == a[i - 1].rb && a[i].qb == a[i - 1].qb) a[i].qe = a[i].qb;
-  m = 1;
-  for (int i = 1; i < n; ++i)
-    if (uni(a[i].qe) > uni(a[i].qb)) {
-      if (m != i) a[m] = a[i];
-      ++m;
-    }
-  return m;
+  return sort_dedup_walk<true>(g.po.max_chain_gap, g.po.mask_level_redun, n, a,
+                               [&](const R* x, const R* y, int* w) { return patch_reg(o, ref, g, x, y, c, w); });
 }
 
 __device__ __forceinline__ void set_alt(const DevRef& ref, const RegPostArgs& g, R* p) {

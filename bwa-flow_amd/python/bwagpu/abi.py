@@ -127,6 +127,25 @@ def default_postopt() -> PostOpt:
     return PostOpt(10000, 0.95, 0.50, 0)
 
 
+class PairOpt(C.Structure):
+    """bwagpu_pairopt_t: mem_opt_t's fields of mem_pestat / mem_matesw, and the round cap of mate rescue"""
+    _fields_ = [("max_ins", C.c_int32), ("max_matesw", C.c_int32), ("pen_unpaired", C.c_int32),
+                ("min_seed_len", C.c_int32), ("max_chain_gap", C.c_int32), ("mask_level_redun", C.c_float),
+                ("mask_level", C.c_float), ("max_rounds", C.c_int32)]
+
+
+def default_pairopt() -> PairOpt:
+    """mem_opt_init's defaults (bwa/bwamem.c:48-84); three rounds"""
+    return PairOpt(10000, 50, 17, 19, 10000, 0.95, 0.50, 3)
+
+
+# bwagpu_pestat_t == mem_pestat_t (bwa/bwamem.h:82-86)
+PESTAT_DTYPE = np.dtype([("low", "<i4"), ("high", "<i4"), ("failed", "<i4"), ("pad", "<i4"), ("avg", "<f8"),
+                         ("std", "<f8")])
+assert PESTAT_DTYPE.itemsize == 32 and C.sizeof(PairOpt) == 32
+RESCUE_DONE, RESCUE_UNFINISHED, RESCUE_OVERFLOW, RESCUE_UNSUPPORTED = 0, 1, 2, 3
+
+
 def default_chainopt() -> dict:
     """mem_opt_init's chaining defaults (bwa/bwamem.c:62-72)"""
     return dict(max_occ=500, max_chain_gap=10000, min_chain_weight=0, max_chain_extend=1 << 30, mask_level=0.5,
@@ -186,6 +205,14 @@ PROTOS = {
     "bwagpu_regs_post_device": (C.c_int, [_VP, C.POINTER(PostOpt), C.c_int32, C.c_int64, C.POINTER(BatchC), _VP,
                                            _VP, _VP, _VP]),
     "bwagpu_set_regs_post": (C.c_int, [_VP, C.POINTER(PostOpt), C.c_int32, C.c_int64]),
+    "bwagpu_pestat": (C.c_int, [_VP, C.POINTER(PairOpt), C.c_int32, _VP, _VP, _VP, _VP]),
+    "bwagpu_pestat_device": (C.c_int, [_VP, C.POINTER(PairOpt), C.c_int32, _VP, _VP, _VP, _VP, _VP]),
+    "bwagpu_mate_rescue": (C.c_int, [_VP, C.POINTER(PairOpt), _VP, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                      _VP, _VP]),
+    "bwagpu_mate_rescue_device": (C.c_int, [_VP, C.POINTER(PairOpt), _VP, C.POINTER(BatchC), _VP, _VP, _VP, _VP, _VP,
+                                             _VP, _VP, _VP, _VP]),
+    "bwagpu_debug_rescue_drop": (C.c_int, [_VP, C.c_int32]),
+    "bwagpu_debug_rescue_times": (C.c_int, [_VP, _VP]),
 }
 
 _lib = None

@@ -436,6 +436,74 @@ class Engine:
         po = abi.default_postopt() if popt is None else popt
         self._check(self.lib.bwagpu_set_regs_post(self.ctx, C.byref(po), int(flags), int(id0)), "set_regs_post")
 
+    def pestat(self, reg_off, regs, n, popt: abi.PairOpt | None = None) -> np.ndarray:
+        """mem_pestat (bwa/bwamem_pair.c:49-112) over a batch of interleaved pairs (reads 2i, 2i+1):
+        read r's n[r] regions at regs[reg_off[r]:] -> pes[4] (abi.PESTAT_DTYPE), bit for bit the reference's"""
+        reg_off = np.ascontiguousarray(reg_off, np.int64)
+        regs = np.ascontiguousarray(regs, abi.ALNREG_DTYPE)
+        n = np.ascontiguousarray(n, np.int32)
+        if len(reg_off) != len(n):
+            raise ValueError("pestat: reg_off and n differ in length")
+        po = abi.default_pairopt() if popt is None else popt
+        pes = np.zeros(4, abi.PESTAT_DTYPE)
+        self._check(self.lib.bwagpu_pestat(self.ctx, C.byref(po), len(n), _ptr(reg_off), _ptr(regs), _ptr(n),
+                                           _ptr(pes)), "pestat")
+        return pes
+
+    def pestat_device(self, n_reads: int, dev_reg_off: int, dev_regs: int, dev_n: int, dev_pes: int,
+                      popt: abi.PairOpt | None = None, stream: int | None = None):
+        """the same on device memory, asynchronous on stream (pointers as ints); dev_pes: 4 x 32 bytes"""
+        po = abi.default_pairopt() if popt is None else popt
+        self._check(self.lib.bwagpu_pestat_device(self.ctx, C.byref(po), int(n_reads), C.c_void_p(dev_reg_off),
+                                                  C.c_void_p(dev_regs), C.c_void_p(dev_n), C.c_void_p(dev_pes),
+                                                  C.c_void_p(stream) if stream else None), "pestat_device")
+
+    def mate_rescue(self, pes, seq_off, seq, reg_off, regs, n, out_off, popt: abi.PairOpt | None = None):
+        """the rescue loop of mem_sam_pe (bwa/bwamem_pair.c:268-279, mem_matesw) for every pair of a batch.
+        Read r's result may hold out_off[r+1] - out_off[r] regions ->
+        (out_regs[out_off[-1]], out_n[n_reads], status[n_reads/2] abi.RESCUE_*, n_sw[n_reads/2])"""
+        pes = np.ascontiguousarray(pes, abi.PESTAT_DTYPE)
+        seq_off = np.ascontiguousarray(seq_off, np.int64)
+        seq = np.ascontiguousarray(seq, np.uint8)
+        reg_off = np.ascontiguousarray(reg_off, np.int64)
+        regs = np.ascontiguousarray(regs, abi.ALNREG_DTYPE)
+        n = np.ascontiguousarray(n, np.int32)
+        out_off = np.ascontiguousarray(out_off, np.int64)
+        nr = len(seq_off) - 1
+        if len(pes) != 4 or len(reg_off) < nr or len(n) < nr or len(out_off) != nr + 1:
+            raise ValueError("mate_rescue: pes / reg_off / n / out_off do not fit the batch")
+        po = abi.default_pairopt() if popt is None else popt
+        out = np.zeros(max(int(out_off[-1]), 1), abi.ALNREG_DTYPE)
+        out_n = np.zeros(max(nr, 1), np.int32)
+        status = np.zeros(max(nr // 2, 1), np.int32)
+        n_sw = np.zeros(max(nr // 2, 1), np.int32)
+        self._check(self.lib.bwagpu_mate_rescue(self.ctx, C.byref(po), _ptr(pes), nr, _ptr(seq_off), _ptr(seq),
+                                                _ptr(reg_off), _ptr(regs), _ptr(n), _ptr(out_off), _ptr(out),
+                                                _ptr(out_n), _ptr(status), _ptr(n_sw)), "mate_rescue")
+        return out, out_n[:nr], status[:nr // 2], n_sw[:nr // 2]
+
+    def mate_rescue_device(self, dev_pes: int, dev_batch: abi.BatchC, dev_reg_off: int, dev_regs: int, dev_n: int,
+                           dev_out_off: int, dev_out_regs: int, dev_out_n: int, dev_status: int, dev_n_sw: int,
+                           popt: abi.PairOpt | None = None, stream: int | None = None):
+        """the same on device memory, on stream (pointers as ints): directly after regs_post_device /
+        pestat_device on that stream; dev_batch needs n_reads, seq_bytes, seq_off, seq"""
+        po = abi.default_pairopt() if popt is None else popt
+        self._check(self.lib.bwagpu_mate_rescue_device(
+            self.ctx, C.byref(po), C.c_void_p(dev_pes), C.byref(dev_batch), C.c_void_p(dev_reg_off),
+            C.c_void_p(dev_regs), C.c_void_p(dev_n), C.c_void_p(dev_out_off), C.c_void_p(dev_out_regs),
+            C.c_void_p(dev_out_n), C.c_void_p(dev_status), C.c_void_p(dev_n_sw),
+            C.c_void_p(stream) if stream else None), "mate_rescue_device")
+
+    def debug_rescue_drop(self, k: int):
+        """tests: the first round's plan of later mate_rescue calls leaves every k-th task out (0 = off)"""
+        self._check(self.lib.bwagpu_debug_rescue_drop(self.ctx, int(k)), "debug_rescue_drop")
+
+    def debug_rescue_times(self) -> dict:
+        """the last mate_rescue* call by HIP events, summed over its rounds (waits for it)"""
+        out = np.zeros(4, np.float64)
+        self._check(self.lib.bwagpu_debug_rescue_times(self.ctx, _ptr(out)), "debug_rescue_times")
+        return dict(plan_ms=float(out[0]), align2_ms=float(out[1]), apply_ms=float(out[2]), rounds=int(out[3]))
+
     def prof_start(self, max_launches: int):
         """time the next max_launches launches of the dominant extension kernel"""
         self._check(self.lib.bwagpu_prof_start(self.ctx, max_launches), "prof_start")

@@ -66,6 +66,12 @@
  *       612): mem_sort_dedup_patch with mem_patch_reg (bwa/bwamem.c:415-498),
  *       and the is_alt flag (Pipeline.cpp:570-574) for every read of a batch
  *       (mem_mark_primary_se, Pipeline.cpp:612, stays on the host).
+ *   bwagpu_pestat / bwagpu_mate_rescue (and their _device forms)
+ *       what the reference does next with those regions: mem_pestat
+ *       (bwa/bwamem_pair.c:49-112; src/Pipeline.cpp:288-289, 578-579) and the
+ *       rescue loop at the top of mem_sam_pe (bwamem_pair.c:268-279) with
+ *       mem_matesw (:114-183).  What follows them (mem_mark_primary_se,
+ *       mem_pair, mapq and mem_reg2aln's bookkeeping) stays on the host.
  *   bwagpu_last_error
  *       the what() of fpgaHangError / fpgaResultsError / std::runtime_error
  *       (src/util.h:16-32, OpenCLEnv.h:21-31).
@@ -546,6 +552,86 @@ int bwagpu_regs_post_device(bwagpu_ctx_t *ctx, const bwagpu_postopt_t *popt, int
    plus the previous batch's n_reads (RegionsToSam's start_idx).  flags == 0
    (the default; popt may be NULL then) restores the plain results. */
 int bwagpu_set_regs_post(bwagpu_ctx_t *ctx, const bwagpu_postopt_t *popt, int32_t flags, int64_t id0_of_next_batch);
+
+/* ---- paired ends: mem_pestat and the mate rescue loop on the device ---- */
+
+/* mem_opt_t's fields the two passes read besides the context's bwagpu_opt_t
+   (defaults 10000, 50, 17, 19, 10000, 0.95f, 0.50f: bwamem.c:48-84), and the
+   number of plan / align / replay rounds one bwagpu_mate_rescue call may run
+   (1..8; 3 is plenty: a second round happens only when a dedup removed the
+   region that had made a call unnecessary) */
+typedef struct {
+  int32_t max_ins;
+  int32_t max_matesw;
+  int32_t pen_unpaired;
+  int32_t min_seed_len;
+  int32_t max_chain_gap;
+  float mask_level_redun;
+  float mask_level;
+  int32_t max_rounds;
+} bwagpu_pairopt_t;
+
+/* == mem_pestat_t (bwa/bwamem.h:82-86) */
+typedef struct {
+  int32_t low, high;
+  int32_t failed, pad_;
+  double avg, std;
+} bwagpu_pestat_t;
+
+/* mem_pestat over a batch (bwamem_pair.c:49-112): reads 2i and 2i+1 are pair
+   i (a trailing odd read is ignored, as n >> 1 does), read r's n[r] regions at
+   regs[reg_off[r] ..) as bwagpu_regs_post leaves them.  pes[4] equals the
+   reference's bit for bit, the doubles included.  Host buffers; blocking.
+   Negative counts return BWAGPU_E_INVAL before any launch. */
+int bwagpu_pestat(bwagpu_ctx_t *ctx, const bwagpu_pairopt_t *popt, int32_t n_reads, const int64_t *reg_off,
+                  const bwagpu_alnreg_t *regs, const int32_t *n, bwagpu_pestat_t *pes);
+/* The same on device memory, asynchronous on stream (hipStream_t, NULL = the
+   context's slot-0 stream); dev_pes: 4 records in device memory. */
+int bwagpu_pestat_device(bwagpu_ctx_t *ctx, const bwagpu_pairopt_t *popt, int32_t n_reads, const int64_t *dev_reg_off,
+                         const bwagpu_alnreg_t *dev_regs, const int32_t *dev_n, bwagpu_pestat_t *dev_pes,
+                         void *stream);
+
+#define BWAGPU_RESCUE_DONE        0 /* both reads' regions are the reference's a[0] / a[1] after
+                                       bwamem_pair.c:268-279, byte for byte and in order         */
+#define BWAGPU_RESCUE_UNFINISHED  1 /* max_rounds reached                                        */
+#define BWAGPU_RESCUE_OVERFLOW    2 /* a push did not fit the read's output span                 */
+#define BWAGPU_RESCUE_UNSUPPORTED 3 /* a read of the pair is longer than BWAGPU_MAX_READ_LEN (or
+                                       ksw_align2's 16-bit scores could saturate on it)          */
+
+/* The rescue loop of mem_sam_pe (bwamem_pair.c:268-279) for every pair of a
+   batch.  The input regions (regs, reg_off, n) are not modified.  Read r's
+   result goes to out_regs[out_off[r] ..) and may hold up to out_off[r+1] -
+   out_off[r] regions (at least n[r]; every region a call pushes needs room
+   before the dedup that follows may remove one); out_n[r] is its count.
+   status[n_reads/2] is BWAGPU_RESCUE_* per pair; with a non-zero status the
+   pair's output is a copy of its input, n_sw is -1 and the caller keeps the
+   CPU path for that pair.  n_sw[n_reads/2]: the sum of mem_matesw's return
+   values (ksw_align2 calls the reference makes for the pair).
+   Before any launch: odd n_reads, negative counts, a qb/qe outside its read,
+   a base over 4 or an output span smaller than its input return
+   BWAGPU_E_INVAL; options bwagpu_align2_batch refuses and a live orientation
+   with high - low over 2^20 return BWAGPU_E_UNSUPPORTED.  Host buffers;
+   blocking.  bwagpu_last_stats(ctx, 0): kernel_ms of the passes, ext_calls =
+   ksw_align2 tasks computed (0: no align2 launch), cells = tasks the replay
+   used, rows = rounds run. */
+int bwagpu_mate_rescue(bwagpu_ctx_t *ctx, const bwagpu_pairopt_t *popt, const bwagpu_pestat_t *pes, int32_t n_reads,
+                       const int64_t *seq_off, const uint8_t *seq, const int64_t *reg_off,
+                       const bwagpu_alnreg_t *regs, const int32_t *n, const int64_t *out_off,
+                       bwagpu_alnreg_t *out_regs, int32_t *out_n, int32_t *status, int32_t *n_sw);
+/* The same on device memory, on stream (hipStream_t, NULL = the context's
+   slot-0 stream): directly after bwagpu_regs_post_device / bwagpu_pestat_device
+   on the same stream.  dev_batch: host struct of device pointers (n_reads,
+   seq_bytes, seq_off, seq with seq_off[n_reads] <= seq_bytes).  The task
+   counts of every round come to the host (the call waits for the stream
+   there, as bwagpu_seqs2regions does); the last round's replay is left
+   running on the stream.  Nothing is validated on the device path except what
+   keeps the kernels inside their buffers: an output span smaller than its
+   input gives the pair BWAGPU_RESCUE_OVERFLOW with out_n = 0. */
+int bwagpu_mate_rescue_device(bwagpu_ctx_t *ctx, const bwagpu_pairopt_t *popt, const bwagpu_pestat_t *dev_pes,
+                              const bwagpu_batch_t *dev_batch, const int64_t *dev_reg_off,
+                              const bwagpu_alnreg_t *dev_regs, const int32_t *dev_n, const int64_t *dev_out_off,
+                              bwagpu_alnreg_t *dev_out_regs, int32_t *dev_out_n, int32_t *dev_status,
+                              int32_t *dev_n_sw, void *stream);
 
 /* Tuning, test and profiling entry points (bwagpu_debug_*, bwagpu_prof_*,
    bwagpu_ctx_ext_form / _row_bound, bwagpu_streams_concurrent) are declared

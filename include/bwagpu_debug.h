@@ -109,6 +109,17 @@ int bwagpu_debug_ext_kernel(bwagpu_ctx_t *ctx, int32_t lq_max);
    empty kernel on b.  Callers that drive several batches at once should give
    them concurrent streams (bench.py's caller_streams). */
 int bwagpu_streams_concurrent(void *a, void *b);
+/* tests: the first round's plan of every later bwagpu_mate_rescue* call leaves
+   every k-th ksw_align2 task out of the result table (0 = off), the only way
+   to reach the retry round and BWAGPU_RESCUE_UNFINISHED on demand.  Results do
+   not depend on it while max_rounds >= 2. */
+int bwagpu_debug_rescue_drop(bwagpu_ctx_t *ctx, int32_t k);
+/* timing (tools_dev/rescue_bench.py): the last bwagpu_mate_rescue* call of this
+   context by HIP events on its stream (waits for it), summed over its rounds:
+   out[0] ms from a round's start to the end of its plan (the counting pass,
+   the scans, the wait for the task count and the emitting pass), out[1] the
+   batched ksw_align2, out[2] the replay, out[3] the rounds run */
+int bwagpu_debug_rescue_times(bwagpu_ctx_t *ctx, double *out);
 int bwagpu_prof_intervals(bwagpu_ctx_t *ctx, double *start_ms, double *end_ms, int32_t max, int32_t *n);
 
 #ifdef __cplusplus
