@@ -27,6 +27,8 @@
 #include "regpost_host.h"
 #include "rescue.h"
 #include "rescue_host.h"
+#include "pairsel.h"
+#include "pairsel_host.h"
 #include "seed.h"
 #include "chain.h"
 #include "engine.h"
@@ -391,6 +393,11 @@ struct bwagpu_ctx {
   hipEvent_t rs_ev[4 * kRescueMaxRounds] = {};
   int rs_ev_rounds = 0;
   hipStream_t rs_ev_stream = nullptr;
+  // primary marking and pair selection (bwagpu_mark_primary*, bwagpu_pair_select*):
+  // the marking kernel's per-block scratch, the log table (filled once), the
+  // pairing tables of the last call, and the host entries' copies of their arguments
+  DevBuf ps_scratch, ps_log, ps_erfc, ps_regs, ps_roff, ps_n, ps_npri, ps_status, ps_instat, ps_sel, ps_mapq;
+  bool ps_log_ready = false;
   // the FPGA wire format (bwagpu_sw_stream)
   DevBuf st_buf, st_start, st_q, st_tasks, st_lists, st_seen, st_ctr, st_out;
   // bwt_extend calls tier 1 spends on a read before tier 2 (one wave per read)
@@ -615,7 +622,9 @@ void destroy_ctx(bwagpu_ctx_t* ctx) {
                     &ctx->rp_stats, &ctx->pe_isize, &ctx->pe_cnt, &ctx->pe_pes, &ctx->pe_regs, &ctx->pe_roff, &ctx->pe_n,
                     &ctx->rs_pair, &ctx->rs_soff, &ctx->rs_tab, &ctx->rs_toff, &ctx->rs_boff, &ctx->rs_qpool,
                     &ctx->rs_ctr, &ctx->rs_scr, &ctx->rs_in, &ctx->rs_seq, &ctx->rs_seqoff, &ctx->rs_roff, &ctx->rs_n,
-                    &ctx->rs_ooff, &ctx->rs_out, &ctx->rs_outn, &ctx->rs_status, &ctx->rs_nsw})
+                    &ctx->rs_ooff, &ctx->rs_out, &ctx->rs_outn, &ctx->rs_status, &ctx->rs_nsw, &ctx->ps_scratch,
+                    &ctx->ps_log, &ctx->ps_erfc, &ctx->ps_regs, &ctx->ps_roff, &ctx->ps_n, &ctx->ps_npri, &ctx->ps_status,
+                    &ctx->ps_instat, &ctx->ps_sel, &ctx->ps_mapq})
     b->release();
   for (hipEvent_t e : ctx->rs_ev)
     if (e) (void)hipEventDestroy(e);
@@ -3163,5 +3172,242 @@ extern "C" int bwagpu_mate_rescue(bwagpu_ctx_t* ctx, const bwagpu_pairopt_t* pop
   s0.last.cells = hctr[RC_USED];
   s0.last.h2d_bytes = (int64_t)(sizeof(bwagpu_alnreg_t) * span + nseq + sizeof(int64_t) * (3 * nr + 2) + sizeof(int32_t) * nr);
   s0.last.d2h_bytes = (int64_t)(sizeof(bwagpu_alnreg_t) * ospan + sizeof(int32_t) * (nr + 2 * np));
+  return BWAGPU_OK;
+}
+
+// ------------------------------------------------------------------ paired ends: primary marking, pair selection
+namespace {
+
+int sel_tmp(const bwagpu_ctx_t* ctx) {  // bwamem.c:505-507
+  int tmp = ctx->opt.a + ctx->opt_b;
+  tmp = std::max(tmp, ctx->opt.o_del + ctx->opt.e_del);
+  return std::max(tmp, ctx->opt.o_ins + ctx->opt.e_ins);
+}
+
+int enqueue_mark(bwagpu_ctx_t* ctx, const bwagpu_selopt_t& so, int64_t id0, int32_t n_reads, const int64_t* reg_off,
+                 bwagpu_alnreg_t* regs, const int32_t* n, int32_t* n_pri, int32_t* status, hipStream_t st) {
+  HIPC(ctx->ps_scratch.ensure(sizeof(bwagpu_alnreg_t) * (size_t)kSelCap * kSelMaxBlocks), "hipMalloc");
+  MarkArgs a{};
+  a.n_reads = n_reads;
+  a.tmp = sel_tmp(ctx);
+  a.mask_level = so.mask_level;
+  a.id0 = id0;
+  a.reg_off = reg_off;
+  a.regs = regs;
+  a.n = n;
+  a.n_pri = n_pri;
+  a.status = status;
+  a.scratch = ctx->ps_scratch.as<bwagpu_alnreg_t>();
+  HIPC(launch_mark_primary(a, st), "mark_primary launch");
+  return BWAGPU_OK;
+}
+
+// hpes: the four records on the host.  The tables go to the device before the
+// launch (the call waits for the copies: their sources are pageable).
+int enqueue_pairsel(bwagpu_ctx_t* ctx, const bwagpu_selopt_t& so, const bwagpu_pestat_t* hpes, int64_t pair_id0,
+                    int32_t n_reads, const int64_t* reg_off, bwagpu_alnreg_t* regs, const int32_t* n,
+                    const int32_t* n_pri, const int32_t* in_status, bwagpu_pairsel_t* sel, int32_t* out_mapq,
+                    hipStream_t st) {
+  if (!ctx->ps_log_ready) {
+    std::vector<double> lg((size_t)kSelLogN);
+    fill_log_table(lg.data(), kSelLogN);
+    HIPC(ctx->ps_log.ensure(sizeof(double) * (size_t)kSelLogN), "hipMalloc");
+    HIPC(hipMemcpyAsync(ctx->ps_log.p, lg.data(), sizeof(double) * (size_t)kSelLogN, hipMemcpyHostToDevice, st), "H2D");
+    HIPC(hipStreamSynchronize(st), "H2D");
+    ctx->ps_log_ready = true;
+  }
+  int64_t len[4], total = 0;
+  for (int r = 0; r < 4; ++r) total += len[r] = erfc_table_len(hpes[r]);
+  std::vector<double> tab((size_t)std::max<int64_t>(total, 1));
+  HIPC(ctx->ps_erfc.ensure(sizeof(double) * tab.size()), "hipMalloc");
+  PairSelArgs a{};
+  int64_t at = 0;
+  for (int r = 0; r < 4; ++r) {
+    a.pes[r] = hpes[r];
+    a.erfc_tab[r] = ctx->ps_erfc.as<double>() + at;
+    if (len[r]) fill_erfc_table(hpes[r], tab.data() + at);
+    at += len[r];
+  }
+  if (total) {
+    HIPC(hipMemcpyAsync(ctx->ps_erfc.p, tab.data(), sizeof(double) * (size_t)total, hipMemcpyHostToDevice, st), "H2D");
+    HIPC(hipStreamSynchronize(st), "H2D");
+  }
+  a.n_pairs = n_reads >> 1;
+  a.a = ctx->opt.a;
+  a.b = ctx->opt_b;
+  a.tmp = sel_tmp(ctx);
+  a.so = so;
+  a.pair_id0 = pair_id0;
+  a.log_tab = ctx->ps_log.as<double>();
+  a.log_n = kSelLogN;
+  a.reg_off = reg_off;
+  a.regs = regs;
+  a.n = n;
+  a.n_pri = n_pri;
+  a.in_status = in_status;
+  a.sel = sel;
+  a.out_mapq = out_mapq;
+  HIPC(launch_pair_select(ctx->ref, a, st), "pair_select launch");
+  return BWAGPU_OK;
+}
+
+}  // namespace
+
+extern "C" int bwagpu_mark_primary_device(bwagpu_ctx_t* ctx, const bwagpu_selopt_t* sopt, int64_t id0, int32_t n_reads,
+                                          const int64_t* dev_reg_off, bwagpu_alnreg_t* dev_regs, const int32_t* dev_n,
+                                          int32_t* dev_n_pri, int32_t* dev_status, void* stream) {
+  if (!ctx) return BWAGPU_E_INVAL;
+  if (!sel_opt_ok(sopt)) return fail(ctx, BWAGPU_E_INVAL, "bad bwagpu_selopt_t");
+  if (n_reads < 0) return fail(ctx, BWAGPU_E_INVAL, "negative read count");
+  if (n_reads == 0) return BWAGPU_OK;
+  if (!dev_reg_off || !dev_regs || !dev_n || !dev_n_pri || !dev_status) return fail(ctx, BWAGPU_E_INVAL, "NULL array");
+  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
+  hipStream_t st = (hipStream_t)stream;
+  if (!st) HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
+  return enqueue_mark(ctx, *sopt, id0, n_reads, dev_reg_off, dev_regs, dev_n, dev_n_pri, dev_status, st);
+}
+
+extern "C" int bwagpu_mark_primary(bwagpu_ctx_t* ctx, const bwagpu_selopt_t* sopt, int64_t id0, int32_t n_reads,
+                                   const int64_t* reg_off, bwagpu_alnreg_t* regs, const int32_t* n, int32_t* n_pri,
+                                   int32_t* status) {
+  if (!ctx) return BWAGPU_E_INVAL;
+  SelPlan plan;
+  const char* why = "";
+  int rc = mark_check(sopt, n_reads, reg_off, regs, n, n_pri, status, &plan, &why);
+  if (rc) return fail(ctx, rc, why);
+  if (n_reads == 0) return BWAGPU_OK;
+  const size_t nr = (size_t)n_reads, span = (size_t)(plan.hi - plan.lo);
+  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
+  hipStream_t st = nullptr;
+  HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
+  HIPC(ctx->ps_regs.ensure(sizeof(bwagpu_alnreg_t) * std::max<size_t>(span, 1)), "hipMalloc");
+  HIPC(ctx->ps_roff.ensure(sizeof(int64_t) * nr), "hipMalloc");
+  HIPC(ctx->ps_n.ensure(sizeof(int32_t) * nr), "hipMalloc");
+  HIPC(ctx->ps_npri.ensure(sizeof(int32_t) * nr), "hipMalloc");
+  HIPC(ctx->ps_status.ensure(sizeof(int32_t) * nr), "hipMalloc");
+  std::vector<int64_t> roff(nr);
+  for (size_t r = 0; r < nr; ++r) roff[r] = n[r] ? reg_off[r] - plan.lo : 0;
+  if (span) HIPC(hipMemcpyAsync(ctx->ps_regs.p, regs + plan.lo, sizeof(bwagpu_alnreg_t) * span, hipMemcpyHostToDevice, st), "H2D");
+  HIPC(hipMemcpyAsync(ctx->ps_roff.p, roff.data(), sizeof(int64_t) * nr, hipMemcpyHostToDevice, st), "H2D");
+  HIPC(hipMemcpyAsync(ctx->ps_n.p, n, sizeof(int32_t) * nr, hipMemcpyHostToDevice, st), "H2D");
+  HIPC(hipStreamSynchronize(st), "H2D");  // roff is a pageable local
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  HIPC(hipEventCreate(&e0), "event");
+  HIPC(hipEventCreate(&e1), "event");
+  HIPC(hipEventRecord(e0, st), "event");
+  rc = enqueue_mark(ctx, *sopt, id0, n_reads, ctx->ps_roff.as<int64_t>(), ctx->ps_regs.as<bwagpu_alnreg_t>(),
+                    ctx->ps_n.as<int32_t>(), ctx->ps_npri.as<int32_t>(), ctx->ps_status.as<int32_t>(), st);
+  if (rc) {
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return rc;
+  }
+  HIPC(hipEventRecord(e1, st), "event");
+  if (span) HIPC(hipMemcpyAsync(regs + plan.lo, ctx->ps_regs.p, sizeof(bwagpu_alnreg_t) * span, hipMemcpyDeviceToHost, st), "D2H");
+  HIPC(hipMemcpyAsync(n_pri, ctx->ps_npri.p, sizeof(int32_t) * nr, hipMemcpyDeviceToHost, st), "D2H");
+  HIPC(hipMemcpyAsync(status, ctx->ps_status.p, sizeof(int32_t) * nr, hipMemcpyDeviceToHost, st), "D2H");
+  HIPC(hipStreamSynchronize(st), "mark_primary execution");
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, e0, e1);
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  Slot& s0 = ctx->slot[0];
+  s0.last = bwagpu_stats_t{};
+  s0.last.kernel_ms = ms;
+  s0.last.h2d_bytes = (int64_t)(sizeof(bwagpu_alnreg_t) * span + sizeof(int64_t) * nr + sizeof(int32_t) * nr);
+  s0.last.d2h_bytes = (int64_t)(sizeof(bwagpu_alnreg_t) * span + sizeof(int32_t) * 2 * nr);
+  return BWAGPU_OK;
+}
+
+extern "C" int bwagpu_pair_select_device(bwagpu_ctx_t* ctx, const bwagpu_selopt_t* sopt, const bwagpu_pestat_t* dev_pes,
+                                         int64_t pair_id0, int32_t n_reads, const int64_t* dev_reg_off,
+                                         bwagpu_alnreg_t* dev_regs, const int32_t* dev_n, const int32_t* dev_n_pri,
+                                         const int32_t* dev_in_status, bwagpu_pairsel_t* dev_sel,
+                                         int32_t* dev_out_mapq, void* stream) {
+  if (!ctx) return BWAGPU_E_INVAL;
+  if (!sel_opt_ok(sopt)) return fail(ctx, BWAGPU_E_INVAL, "bad bwagpu_selopt_t");
+  if (sopt->flags & kSelRefused)
+    return fail(ctx, BWAGPU_E_UNSUPPORTED,
+                "MEM_F_ALL, MEM_F_NO_MULTI, MEM_F_PRIMARY5 and MEM_F_KEEP_SUPP_MAPQ are not implemented");
+  if (n_reads < 0) return fail(ctx, BWAGPU_E_INVAL, "negative read count");
+  if (n_reads & 1) return fail(ctx, BWAGPU_E_INVAL, "odd read count: reads 2i and 2i+1 are a pair");
+  if (!dev_pes) return fail(ctx, BWAGPU_E_INVAL, "NULL pes");
+  if (n_reads == 0) return BWAGPU_OK;
+  if (!dev_reg_off || !dev_regs || !dev_n || !dev_n_pri || !dev_sel || !dev_out_mapq)
+    return fail(ctx, BWAGPU_E_INVAL, "NULL array");
+  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
+  hipStream_t st = (hipStream_t)stream;
+  if (!st) HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
+  bwagpu_pestat_t hp[4];  // the pairing tables are made from the ranges here
+  HIPC(hipMemcpyAsync(hp, dev_pes, sizeof(hp), hipMemcpyDeviceToHost, st), "D2H");
+  HIPC(hipStreamSynchronize(st), "sync");
+  const char* why = "";
+  if (int rc = pes_check(hp, &why)) return fail(ctx, rc, why);
+  return enqueue_pairsel(ctx, *sopt, hp, pair_id0, n_reads, dev_reg_off, dev_regs, dev_n, dev_n_pri, dev_in_status,
+                         dev_sel, dev_out_mapq, st);
+}
+
+extern "C" int bwagpu_pair_select(bwagpu_ctx_t* ctx, const bwagpu_selopt_t* sopt, const bwagpu_pestat_t* pes,
+                                  int64_t pair_id0, int32_t n_reads, const int64_t* reg_off, bwagpu_alnreg_t* regs,
+                                  const int32_t* n, const int32_t* n_pri, const int32_t* in_status,
+                                  bwagpu_pairsel_t* sel, int32_t* out_mapq) {
+  if (!ctx) return BWAGPU_E_INVAL;
+  SelPlan plan;
+  const char* why = "";
+  int rc = pairsel_check(sopt, pes, n_reads, reg_off, regs, n, n_pri, sel, out_mapq, ctx->ref.n_seqs, &plan, &why);
+  if (rc) return fail(ctx, rc, why);
+  if (n_reads == 0) return BWAGPU_OK;
+  const size_t nr = (size_t)n_reads, np = nr / 2, span = (size_t)(plan.hi - plan.lo);
+  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
+  hipStream_t st = nullptr;
+  HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
+  HIPC(ctx->ps_regs.ensure(sizeof(bwagpu_alnreg_t) * std::max<size_t>(span, 1)), "hipMalloc");
+  HIPC(ctx->ps_mapq.ensure(sizeof(int32_t) * std::max<size_t>(span, 1)), "hipMalloc");
+  HIPC(ctx->ps_roff.ensure(sizeof(int64_t) * nr), "hipMalloc");
+  HIPC(ctx->ps_n.ensure(sizeof(int32_t) * nr), "hipMalloc");
+  HIPC(ctx->ps_npri.ensure(sizeof(int32_t) * nr), "hipMalloc");
+  HIPC(ctx->ps_instat.ensure(sizeof(int32_t) * np), "hipMalloc");
+  HIPC(ctx->ps_sel.ensure(sizeof(bwagpu_pairsel_t) * np), "hipMalloc");
+  std::vector<int64_t> roff(nr);
+  for (size_t r = 0; r < nr; ++r) roff[r] = n[r] ? reg_off[r] - plan.lo : 0;
+  if (span) {
+    HIPC(hipMemcpyAsync(ctx->ps_regs.p, regs + plan.lo, sizeof(bwagpu_alnreg_t) * span, hipMemcpyHostToDevice, st), "H2D");
+    // regions between the spans keep the caller's out_mapq
+    HIPC(hipMemcpyAsync(ctx->ps_mapq.p, out_mapq + plan.lo, sizeof(int32_t) * span, hipMemcpyHostToDevice, st), "H2D");
+  }
+  HIPC(hipMemcpyAsync(ctx->ps_roff.p, roff.data(), sizeof(int64_t) * nr, hipMemcpyHostToDevice, st), "H2D");
+  HIPC(hipMemcpyAsync(ctx->ps_n.p, n, sizeof(int32_t) * nr, hipMemcpyHostToDevice, st), "H2D");
+  HIPC(hipMemcpyAsync(ctx->ps_npri.p, n_pri, sizeof(int32_t) * nr, hipMemcpyHostToDevice, st), "H2D");
+  if (in_status) HIPC(hipMemcpyAsync(ctx->ps_instat.p, in_status, sizeof(int32_t) * np, hipMemcpyHostToDevice, st), "H2D");
+  HIPC(hipStreamSynchronize(st), "H2D");  // roff is a pageable local
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  HIPC(hipEventCreate(&e0), "event");
+  HIPC(hipEventCreate(&e1), "event");
+  HIPC(hipEventRecord(e0, st), "event");
+  rc = enqueue_pairsel(ctx, *sopt, pes, pair_id0, n_reads, ctx->ps_roff.as<int64_t>(), ctx->ps_regs.as<bwagpu_alnreg_t>(),
+                       ctx->ps_n.as<int32_t>(), ctx->ps_npri.as<int32_t>(),
+                       in_status ? ctx->ps_instat.as<int32_t>() : nullptr, ctx->ps_sel.as<bwagpu_pairsel_t>(),
+                       ctx->ps_mapq.as<int32_t>(), st);
+  if (rc) {
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return rc;
+  }
+  HIPC(hipEventRecord(e1, st), "event");
+  if (span) {
+    HIPC(hipMemcpyAsync(regs + plan.lo, ctx->ps_regs.p, sizeof(bwagpu_alnreg_t) * span, hipMemcpyDeviceToHost, st), "D2H");
+    HIPC(hipMemcpyAsync(out_mapq + plan.lo, ctx->ps_mapq.p, sizeof(int32_t) * span, hipMemcpyDeviceToHost, st), "D2H");
+  }
+  HIPC(hipMemcpyAsync(sel, ctx->ps_sel.p, sizeof(bwagpu_pairsel_t) * np, hipMemcpyDeviceToHost, st), "D2H");
+  HIPC(hipStreamSynchronize(st), "pair_select execution");
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, e0, e1);
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  Slot& s0 = ctx->slot[0];
+  s0.last = bwagpu_stats_t{};
+  s0.last.kernel_ms = ms;
+  s0.last.h2d_bytes = (int64_t)((sizeof(bwagpu_alnreg_t) + sizeof(int32_t)) * span + sizeof(int64_t) * nr + sizeof(int32_t) * (2 * nr + np));
+  s0.last.d2h_bytes = (int64_t)((sizeof(bwagpu_alnreg_t) + sizeof(int32_t)) * span + sizeof(bwagpu_pairsel_t) * np);
   return BWAGPU_OK;
 }

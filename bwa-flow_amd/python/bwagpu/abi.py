@@ -146,6 +146,29 @@ assert PESTAT_DTYPE.itemsize == 32 and C.sizeof(PairOpt) == 32
 RESCUE_DONE, RESCUE_UNFINISHED, RESCUE_OVERFLOW, RESCUE_UNSUPPORTED = 0, 1, 2, 3
 
 
+class SelOpt(C.Structure):
+    """bwagpu_selopt_t: mem_opt_t's fields of mem_mark_primary_se, mem_pair's caller and mem_approx_mapq_se"""
+    _fields_ = [("T", C.c_int32), ("pen_unpaired", C.c_int32), ("min_seed_len", C.c_int32),
+                ("mapQ_coef_len", C.c_float), ("mapQ_coef_fac", C.c_int32), ("mask_level", C.c_float),
+                ("drop_ratio", C.c_float), ("flags", C.c_int32)]
+
+
+def default_selopt(flags: int = 0) -> SelOpt:
+    """mem_opt_init's defaults (bwa/bwamem.c:48-84): mapQ_coef_fac is (int)log(50)"""
+    return SelOpt(30, 17, 19, 50.0, 3, 0.50, 0.50, int(flags))
+
+
+MEM_F_NOPAIRING, MEM_F_ALL, MEM_F_NO_MULTI, MEM_F_PRIMARY5, MEM_F_KEEP_SUPP_MAPQ = 0x4, 0x8, 0x10, 0x800, 0x1000
+SEL_MAX_REGS = 512
+SEL_DONE, SEL_TOO_MANY, SEL_SKIPPED = 0, 1, 2
+SEL_NO_PAIRING, SEL_PAIRED = 0, 1
+# bwagpu_pairsel_t
+PAIRSEL_DTYPE = np.dtype([("status", "<i4"), ("branch", "<i4"), ("n_pri", "<i4", (2,)), ("z", "<i4", (2,)),
+                          ("mapq", "<i4", (2,)), ("alt", "<i4", (2,)), ("extra_flag", "<i4"), ("o", "<i4"),
+                          ("subo", "<i4"), ("n_sub", "<i4"), ("pad", "<i4", (2,))])
+assert PAIRSEL_DTYPE.itemsize == 64 and C.sizeof(SelOpt) == 32
+
+
 def default_chainopt() -> dict:
     """mem_opt_init's chaining defaults (bwa/bwamem.c:62-72)"""
     return dict(max_occ=500, max_chain_gap=10000, min_chain_weight=0, max_chain_extend=1 << 30, mask_level=0.5,
@@ -210,6 +233,13 @@ PROTOS = {
     "bwagpu_mate_rescue": (C.c_int, [_VP, C.POINTER(PairOpt), _VP, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                       _VP, _VP]),
     "bwagpu_mate_rescue_device": (C.c_int, [_VP, C.POINTER(PairOpt), _VP, C.POINTER(BatchC), _VP, _VP, _VP, _VP, _VP,
+                                             _VP, _VP, _VP, _VP]),
+    "bwagpu_mark_primary": (C.c_int, [_VP, C.POINTER(SelOpt), C.c_int64, C.c_int32, _VP, _VP, _VP, _VP, _VP]),
+    "bwagpu_mark_primary_device": (C.c_int, [_VP, C.POINTER(SelOpt), C.c_int64, C.c_int32, _VP, _VP, _VP, _VP, _VP,
+                                              _VP]),
+    "bwagpu_pair_select": (C.c_int, [_VP, C.POINTER(SelOpt), _VP, C.c_int64, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP,
+                                      _VP]),
+    "bwagpu_pair_select_device": (C.c_int, [_VP, C.POINTER(SelOpt), _VP, C.c_int64, C.c_int32, _VP, _VP, _VP, _VP,
                                              _VP, _VP, _VP, _VP]),
     "bwagpu_debug_rescue_drop": (C.c_int, [_VP, C.c_int32]),
     "bwagpu_debug_rescue_times": (C.c_int, [_VP, _VP]),

@@ -494,6 +494,70 @@ class Engine:
             C.c_void_p(dev_out_n), C.c_void_p(dev_status), C.c_void_p(dev_n_sw),
             C.c_void_p(stream) if stream else None), "mate_rescue_device")
 
+    def mark_primary(self, reg_off, regs, n, id0: int = 0, sopt: abi.SelOpt | None = None):
+        """mem_mark_primary_se (bwa/bwamem.c:502-567) for every read of a batch, read r with id0 + r:
+        read r's n[r] regions at regs[reg_off[r]:] -> (regs copy reordered and marked, n_pri[n_reads],
+        status[n_reads] abi.SEL_*)"""
+        reg_off = np.ascontiguousarray(reg_off, np.int64)
+        regs = np.array(regs, abi.ALNREG_DTYPE, order="C")
+        n = np.ascontiguousarray(n, np.int32)
+        if len(reg_off) != len(n):
+            raise ValueError("mark_primary: reg_off and n differ in length")
+        so = abi.default_selopt() if sopt is None else sopt
+        nr = len(n)
+        n_pri = np.zeros(max(nr, 1), np.int32)
+        status = np.zeros(max(nr, 1), np.int32)
+        self._check(self.lib.bwagpu_mark_primary(self.ctx, C.byref(so), int(id0), nr, _ptr(reg_off), _ptr(regs),
+                                                 _ptr(n), _ptr(n_pri), _ptr(status)), "mark_primary")
+        return regs, n_pri[:nr], status[:nr]
+
+    def mark_primary_device(self, n_reads: int, dev_reg_off: int, dev_regs: int, dev_n: int, dev_n_pri: int,
+                            dev_status: int, id0: int = 0, sopt: abi.SelOpt | None = None,
+                            stream: int | None = None):
+        """the same in place on device memory, asynchronous on stream (pointers as ints)"""
+        so = abi.default_selopt() if sopt is None else sopt
+        self._check(self.lib.bwagpu_mark_primary_device(
+            self.ctx, C.byref(so), int(id0), int(n_reads), C.c_void_p(dev_reg_off), C.c_void_p(dev_regs),
+            C.c_void_p(dev_n), C.c_void_p(dev_n_pri), C.c_void_p(dev_status),
+            C.c_void_p(stream) if stream else None), "mark_primary_device")
+
+    def pair_select(self, pes, reg_off, regs, n, n_pri, pair_id0: int = 0, sopt: abi.SelOpt | None = None,
+                    in_status=None):
+        """mem_sam_pe from bwa/bwamem_pair.c:286 to its first mem_reg2aln for every pair (reads 2i, 2i+1;
+        pair i has id pair_id0 + i) on regions as mark_primary leaves them ->
+        (sel[n_reads/2] abi.PAIRSEL_DTYPE, out_mapq parallel to regs (-1: no record), regs copy as the
+        reference leaves them)"""
+        pes = np.ascontiguousarray(pes, abi.PESTAT_DTYPE)
+        reg_off = np.ascontiguousarray(reg_off, np.int64)
+        regs = np.array(regs, abi.ALNREG_DTYPE, order="C")
+        n = np.ascontiguousarray(n, np.int32)
+        n_pri = np.ascontiguousarray(n_pri, np.int32)
+        if len(pes) != 4 or len(reg_off) != len(n) or len(n_pri) != len(n):
+            raise ValueError("pair_select: pes / reg_off / n / n_pri do not fit the batch")
+        nr = len(n)
+        if in_status is not None:
+            in_status = np.ascontiguousarray(in_status, np.int32)
+            if len(in_status) != nr // 2:
+                raise ValueError("pair_select: in_status is not one word per pair")
+        so = abi.default_selopt() if sopt is None else sopt
+        sel = np.zeros(max(nr // 2, 1), abi.PAIRSEL_DTYPE)
+        out_mapq = np.full(max(len(regs), 1), -1, np.int32)
+        self._check(self.lib.bwagpu_pair_select(self.ctx, C.byref(so), _ptr(pes), int(pair_id0), nr, _ptr(reg_off),
+                                                _ptr(regs), _ptr(n), _ptr(n_pri), _ptr(in_status), _ptr(sel),
+                                                _ptr(out_mapq)), "pair_select")
+        return sel[:nr // 2], out_mapq[:len(regs)], regs
+
+    def pair_select_device(self, dev_pes: int, n_reads: int, dev_reg_off: int, dev_regs: int, dev_n: int,
+                           dev_n_pri: int, dev_in_status: int | None, dev_sel: int, dev_out_mapq: int,
+                           pair_id0: int = 0, sopt: abi.SelOpt | None = None, stream: int | None = None):
+        """the same on device memory, on stream (pointers as ints): directly after mark_primary_device"""
+        so = abi.default_selopt() if sopt is None else sopt
+        self._check(self.lib.bwagpu_pair_select_device(
+            self.ctx, C.byref(so), C.c_void_p(dev_pes), int(pair_id0), int(n_reads), C.c_void_p(dev_reg_off),
+            C.c_void_p(dev_regs), C.c_void_p(dev_n), C.c_void_p(dev_n_pri),
+            C.c_void_p(dev_in_status) if dev_in_status else None, C.c_void_p(dev_sel), C.c_void_p(dev_out_mapq),
+            C.c_void_p(stream) if stream else None), "pair_select_device")
+
     def debug_rescue_drop(self, k: int):
         """tests: the first round's plan of later mate_rescue calls leaves every k-th task out (0 = off)"""
         self._check(self.lib.bwagpu_debug_rescue_drop(self.ctx, int(k)), "debug_rescue_drop")

@@ -65,13 +65,18 @@
  *       the per-read head of RegionsToSam::compute (src/Pipeline.cpp:560-575,
  *       612): mem_sort_dedup_patch with mem_patch_reg (bwa/bwamem.c:415-498),
  *       and the is_alt flag (Pipeline.cpp:570-574) for every read of a batch
- *       (mem_mark_primary_se, Pipeline.cpp:612, stays on the host).
+ *       (mem_mark_primary_se, Pipeline.cpp:612, is bwagpu_mark_primary).
  *   bwagpu_pestat / bwagpu_mate_rescue (and their _device forms)
  *       what the reference does next with those regions: mem_pestat
  *       (bwa/bwamem_pair.c:49-112; src/Pipeline.cpp:288-289, 578-579) and the
  *       rescue loop at the top of mem_sam_pe (bwamem_pair.c:268-279) with
- *       mem_matesw (:114-183).  What follows them (mem_mark_primary_se,
- *       mem_pair, mapq and mem_reg2aln's bookkeeping) stays on the host.
+ *       mem_matesw (:114-183).
+ *   bwagpu_mark_primary / bwagpu_pair_select (and their _device forms)
+ *       what mem_sam_pe does after the rescue loop up to its first
+ *       mem_reg2aln: mem_mark_primary_se on both reads (bwamem_pair.c:280-281),
+ *       mem_pair (:185-246), the proper-pair / unpaired decision and the mapq
+ *       arithmetic (:288-336, :374-390, mem_approx_mapq_se).  mem_gen_alt / XA,
+ *       the CIGARs and the SAM text stay on the host.
  *   bwagpu_last_error
  *       the what() of fpgaHangError / fpgaResultsError / std::runtime_error
  *       (src/util.h:16-32, OpenCLEnv.h:21-31).
@@ -632,6 +637,123 @@ int bwagpu_mate_rescue_device(bwagpu_ctx_t *ctx, const bwagpu_pairopt_t *popt, c
                               const bwagpu_alnreg_t *dev_regs, const int32_t *dev_n, const int64_t *dev_out_off,
                               bwagpu_alnreg_t *dev_out_regs, int32_t *dev_out_n, int32_t *dev_status,
                               int32_t *dev_n_sw, void *stream);
+
+/* ---- paired ends: primary marking, mem_pair and the mapq arithmetic on the device ---- */
+
+/* mem_opt_t's fields the two passes read besides the context's bwagpu_opt_t
+   (bwa/bwamem.h:26-58; defaults 30, 17, 19, 50.f, 3, 0.50f, 0.50f: bwamem.c:48-84).
+   flags are mem_opt_t.flag's bits: BWAGPU_MEM_F_NOPAIRING is honoured, the
+   four refused ones below return BWAGPU_E_UNSUPPORTED, every other bit is
+   ignored (none of them is read between bwamem_pair.c:280 and the first
+   mem_reg2aln).  drop_ratio is carried for mem_reg2sam's third test
+   (bwamem.c:1035), which only MEM_F_ALL can reach. */
+typedef struct {
+  int32_t T;
+  int32_t pen_unpaired;
+  int32_t min_seed_len;
+  float mapQ_coef_len;
+  int32_t mapQ_coef_fac;
+  float mask_level;
+  float drop_ratio;
+  int32_t flags;
+} bwagpu_selopt_t;
+
+#define BWAGPU_MEM_F_NOPAIRING      0x4
+#define BWAGPU_MEM_F_ALL            0x8    /* refused */
+#define BWAGPU_MEM_F_NO_MULTI       0x10   /* refused */
+#define BWAGPU_MEM_F_PRIMARY5       0x800  /* refused */
+#define BWAGPU_MEM_F_KEEP_SUPP_MAPQ 0x1000 /* refused */
+
+/* regions of one read (bwagpu_mark_primary), primary regions of one pair
+   (bwagpu_pair_select) the kernels hold in LDS */
+#define BWAGPU_SEL_MAX_REGS 512
+
+#define BWAGPU_SEL_DONE     0 /* the read / pair is as the reference leaves it                     */
+#define BWAGPU_SEL_TOO_MANY 1 /* over BWAGPU_SEL_MAX_REGS, or (pair_select) an argument of the
+                                 mapq arithmetic's log outside the context's table [1, 65536)    */
+#define BWAGPU_SEL_SKIPPED  2 /* pair_select: in_status was non-zero for the pair                  */
+
+/* mem_mark_primary_se (bwamem.c:502-567) for every read of a batch, in place:
+   read r's n[r] regions at regs[reg_off[r] ..) with id = id0 + r (mem_sam_pe's
+   id<<1|r is id0 = 2 * the first pair's id; the contract BWAGPU_POST_PRIMARY
+   reserves).  The regions are reordered and sub, sub_n, alt_sc, secondary,
+   secondary_all and hash are written as the reference leaves them; n_pri[r] is
+   the function's return value.  status[r] is BWAGPU_SEL_DONE, or
+   BWAGPU_SEL_TOO_MANY for a read over BWAGPU_SEL_MAX_REGS regions, which is left
+   untouched (n_pri[r] = 0): the caller keeps the CPU path for it.  Of sopt only
+   mask_level is read.  Negative counts, overlapping spans and NULLs return
+   BWAGPU_E_INVAL before any launch.  Host buffers; blocking.
+   bwagpu_last_stats(ctx, 0): kernel_ms of the pass. */
+int bwagpu_mark_primary(bwagpu_ctx_t *ctx, const bwagpu_selopt_t *sopt, int64_t id0, int32_t n_reads,
+                        const int64_t *reg_off, bwagpu_alnreg_t *regs, const int32_t *n, int32_t *n_pri,
+                        int32_t *status);
+/* The same on device memory, asynchronous on stream (hipStream_t, NULL = the
+   context's slot-0 stream): directly on what bwagpu_mate_rescue_device wrote
+   (dev_out_off, dev_out_regs, dev_out_n).  Nothing is validated on the device
+   path except what keeps the kernel inside its buffers. */
+int bwagpu_mark_primary_device(bwagpu_ctx_t *ctx, const bwagpu_selopt_t *sopt, int64_t id0, int32_t n_reads,
+                               const int64_t *dev_reg_off, bwagpu_alnreg_t *dev_regs, const int32_t *dev_n,
+                               int32_t *dev_n_pri, int32_t *dev_status, void *stream);
+
+#define BWAGPU_SEL_NO_PAIRING 0 /* bwamem_pair.c:374-392: each read goes through mem_reg2sam      */
+#define BWAGPU_SEL_PAIRED     1 /* bwamem_pair.c:298-362: h[i] (and g[i]) are the pair's records   */
+
+/* What mem_sam_pe decides for one pair between bwamem_pair.c:286 and its first
+   mem_reg2aln; 64 bytes.
+   BWAGPU_SEL_PAIRED: z[i] is the region emitted as h[i] with mapq[i] (q_se as
+   mem_aln_t.mapq's 8 bits hold it) and flag 0x40<<i | extra_flag; alt[i] is the index of g[i] (n_pri[i]) or -1.
+   BWAGPU_SEL_NO_PAIRING: z[i] is the `which` of :375-384 (the mate record h[i]
+   the other read's lines refer to) or -1, mapq[i] that record's mapq, alt[i]
+   -1; the read's own records are the regions with out_mapq >= 0 in order
+   (mem_reg2sam, bwamem.c:1030-1047: the first one primary, later ones
+   supplementary), each with extra_flag | 0x41 / 0x81.
+   o, subo, n_sub: mem_pair's return value and outputs as it leaves them
+   (before :301), 0 where it was not called. */
+typedef struct {
+  int32_t status;     /* BWAGPU_SEL_* */
+  int32_t branch;
+  int32_t n_pri[2];
+  int32_t z[2];
+  int32_t mapq[2];
+  int32_t alt[2];
+  int32_t extra_flag;
+  int32_t o, subo, n_sub;
+  int32_t pad_[2];
+} bwagpu_pairsel_t;
+
+/* mem_sam_pe from bwamem_pair.c:286 to its first mem_reg2aln for every pair of
+   a batch: mem_pair (:185-246), the proper-pair / unpaired decision and the
+   mapq arithmetic (:288-336, :374-390, mem_approx_mapq_se).  Reads 2i and 2i+1
+   are pair i with id pair_id0 + i; read r's n[r] regions at regs[reg_off[r] ..)
+   as bwagpu_mark_primary leaves them (which was given id0 = 2 * pair_id0) with
+   its n_pri[r]; pes[4] as bwagpu_pestat returns it.
+   sel[n_reads/2] receives the decision.  out_mapq is parallel to regs:
+   out_mapq[reg_off[r] + k] is -1 for a region that gets no SAM record,
+   otherwise the record's mapq.  The regions are modified in place exactly as
+   the reference modifies them (sub and secondary = -2 of :312-313, the
+   secondary_all switch of :327-336).  in_status may be NULL; a pair with
+   in_status[i] != 0 (bwagpu_mate_rescue's status array fits) gets
+   BWAGPU_SEL_SKIPPED.  A pair with a non-zero status keeps its regions
+   untouched, its out_mapq entries are -1 and the caller keeps the CPU path for
+   it.  mem_gen_alt / XA, CIGARs and the SAM text stay on the host.
+   Before any launch: odd n_reads, negative counts, n_pri outside [0, n], a rid
+   outside the reference, overlapping spans and NULLs return BWAGPU_E_INVAL;
+   the refused flags and a live orientation with high - low over 2^20 return
+   BWAGPU_E_UNSUPPORTED.  Host buffers; blocking.  bwagpu_last_stats(ctx, 0):
+   kernel_ms of the pass. */
+int bwagpu_pair_select(bwagpu_ctx_t *ctx, const bwagpu_selopt_t *sopt, const bwagpu_pestat_t *pes, int64_t pair_id0,
+                       int32_t n_reads, const int64_t *reg_off, bwagpu_alnreg_t *regs, const int32_t *n,
+                       const int32_t *n_pri, const int32_t *in_status, bwagpu_pairsel_t *sel, int32_t *out_mapq);
+/* The same on device memory, on stream (hipStream_t, NULL = the context's
+   slot-0 stream), directly after bwagpu_mark_primary_device on that stream.
+   The 128 bytes of dev_pes come to the host for the pairing tables (the call
+   waits for the stream there, as bwagpu_mate_rescue_device does); the kernel
+   is left running on the stream. */
+int bwagpu_pair_select_device(bwagpu_ctx_t *ctx, const bwagpu_selopt_t *sopt, const bwagpu_pestat_t *dev_pes,
+                              int64_t pair_id0, int32_t n_reads, const int64_t *dev_reg_off,
+                              bwagpu_alnreg_t *dev_regs, const int32_t *dev_n, const int32_t *dev_n_pri,
+                              const int32_t *dev_in_status, bwagpu_pairsel_t *dev_sel, int32_t *dev_out_mapq,
+                              void *stream);
 
 /* Tuning, test and profiling entry points (bwagpu_debug_*, bwagpu_prof_*,
    bwagpu_ctx_ext_form / _row_bound, bwagpu_streams_concurrent) are declared

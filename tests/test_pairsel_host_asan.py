@@ -1,0 +1,16 @@
+"""tests/cpp/pairsel_host_asan.cpp: the host-side validation, span arithmetic and tables of
+bwagpu_mark_primary / bwagpu_pair_select (bwa-flow_amd/csrc/pairsel_host.h) as a
+stand-alone program under AddressSanitizer and UBSan, on the CPU."""
+import os
+import subprocess
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_pairsel_host_checks_are_clean_under_the_sanitizers(tmp_path):
+    exe = str(tmp_path / "pairsel_host_asan")
+    subprocess.run(["g++", "-std=c++17", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-I", os.path.join(REPO, "include"), "-I", os.path.join(REPO, "bwa-flow_amd", "csrc"),
+                    os.path.join(REPO, "tests", "cpp", "pairsel_host_asan.cpp"), "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and "pairsel_host_asan OK" in r.stdout, r.stdout + r.stderr
