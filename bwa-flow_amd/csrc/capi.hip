@@ -24,13 +24,9 @@
 #include "align2.h"
 #include "reg2aln.h"
 #include "regpost.h"
-#include "regpost_host.h"
-#include "rescue.h"
-#include "rescue_host.h"
-#include "pairsel.h"
-#include "pairsel_host.h"
 #include "seed.h"
 #include "chain.h"
+#include "ctx.h"
 #include "engine.h"
 
 using namespace bwagpu;
@@ -110,50 +106,6 @@ void host_parallel(int nt, F f) {
 }
 
 
-struct DevBuf {  // grow-only device buffer
-  void* p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t n) {
-    if (n <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t want = std::max<size_t>(n + n / 4, 4096);
-    hipError_t e = hipMalloc(&p, want);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <class T>
-  T* as() const { return (T*)p; }
-};
-
-struct HostBuf {  // grow-only pinned host buffer
-  void* p = nullptr;
-  size_t cap = 0;
-  unsigned flags = hipHostMallocDefault;
-  hipError_t ensure(size_t n) {
-    if (n <= cap) return hipSuccess;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t want = std::max<size_t>(n + n / 4, 4096);
-    hipError_t e = hipHostMalloc(&p, want, flags);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <class T>
-  T* as() const { return (T*)p; }
-};
 
 // layout of one batch inside a slot's single input allocation
 struct InLayout {
@@ -176,65 +128,6 @@ struct InLayout {
   }
 };
 
-struct Slot {
-  // created on first use (lazy_stream): the device entry runs on the caller's
-  // streams, and every stream a context creates takes a place on one of the
-  // process's hardware queues (GPU_MAX_HW_QUEUES) the caller's streams and
-  // the selection side streams share
-  hipStream_t stream = nullptr;
-  std::once_flag stream_once;
-  hipError_t stream_err = hipSuccess;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
-  DevBuf d_in, d_win, d_srt, d_prog, d_desc, d_out, d_n, d_stats, d_lists, d_counts;
-  DevBuf d_cread, d_ext, d_tasks, d_ctr, d_regpos, d_skipf, d_heavy, d_redo, d_rbits;  // speculative path
-  DevBuf d_schain, d_hinfo, d_mat, d_cov, d_hflag, d_colent, d_qh, d_longc, d_sorth, d_stasks, d_ftask, d_ftaskR;
-  SpecStreams spec;  // created on first use (choose_side)
-  bool side_chosen = false;
-  void release_scratch() {
-    d_win.release(); d_srt.release(); d_prog.release(); d_desc.release(); d_lists.release(); d_counts.release();
-    d_cread.release(); d_ext.release(); d_tasks.release(); d_ctr.release(); d_regpos.release(); d_skipf.release();
-    d_heavy.release(); d_redo.release(); d_rbits.release(); d_schain.release(); d_hinfo.release(); d_mat.release(); d_cov.release(); d_hflag.release(); d_colent.release(); d_longc.release();
-    d_qh.release();
-    d_sorth.release();
-    d_stasks.release();
-    d_ftask.release();
-    d_ftaskR.release();
-    if (spec.side) (void)hipStreamSynchronize(spec.side);
-    if (spec.side) (void)hipStreamDestroy(spec.side);
-    if (spec.fork) (void)hipEventDestroy(spec.fork);
-    if (spec.join) (void)hipEventDestroy(spec.join);
-    spec = SpecStreams{};
-    side_chosen = false;
-  }
-  HostBuf h_in, h_out, h_n, h_stats;
-  // the submit/wait path's results: regions written densely (read r's at
-  // h_dense[h_off[r] ..]) by dense_copy_kernel straight into pinned memory;
-  // h_out (the slot layout) is filled from them only when asked for
-  HostBuf h_dense, h_off;
-  DevBuf d_off;
-  size_t in_rco = 0, in_cso = 0;  // where the batch's offsets sit in h_in
-  bool slot_view = false;         // h_out holds the last batch's slot layout
-  bool busy = false;
-  // the last submitted batch finished and its results are in h_dense / h_n /
-  // h_off (set by _wait; cleared by the next _submit, and never set when a
-  // submit fails)
-  bool has_results = false;
-  // the finished batch's offsets, copied out of h_in by a _stage of the next
-  // batch (which overwrites h_in) so that a later _results can still build
-  // the slot layout
-  bool kept = false;
-  std::vector<int32_t> keep_rco, keep_cso;
-  int32_t n_reads = 0, n_chains = 0, n_seeds = 0;
-  std::chrono::steady_clock::time_point t_submit;
-  bwagpu_stats_t last{};
-  int64_t h2d = 0, d2h = 0;
-};
-
-hipError_t lazy_stream(Slot& s, hipStream_t* st) {
-  std::call_once(s.stream_once, [&s] { s.stream_err = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking); });
-  *st = s.stream;
-  return s.stream_err;
-}
 
 // Side-stream probes.  HIP maps every stream of the process onto one of
 // GPU_MAX_HW_QUEUES hardware queues (4 on the pool's boxes), and work on two
@@ -323,115 +216,8 @@ __global__ void __launch_bounds__(256) dense_copy_kernel(const bwagpu_alnreg_t* 
 
 }  // namespace
 
-struct bwagpu_ctx {
-  int device = 0;
-  // caller streams seen by the spec path, and side streams retired after a
-  // later caller turned out to share their hardware queue (choose_side)
-  std::mutex side_mu;
-  std::vector<hipStream_t> callers, side_graveyard;
-  DevOpt opt{};
-  DevRef ref{};
-  bool own_pac = false;
-  void* d_pac = nullptr;
-  int64_t* d_ann_off = nullptr;
-  int32_t* d_ann_len = nullptr;
-  int watchdog_ms = 10000;
-  int ext_form = 0;  // bwagpu_ctx_ext_form (the process default when made)
-  Slot slot[BWAGPU_NUM_SLOTS];
-  // bwagpu_chain2aln_device: the caller's streams, one per slot's scratch (a
-  // stream always reuses the same scratch, so its launches never race)
-  hipStream_t dev_stream[BWAGPU_NUM_SLOTS] = {};
-  // ... and its own scratch (only the Dev buffers of these are used): the
-  // submit/wait path's slots never share scratch with the device entry, so the
-  // two entry points may run concurrently on one context
-  Slot dev_scratch[BWAGPU_NUM_SLOTS];
-  // ksw_align2 batches (bwagpu_align2_*): grow-only, reused across calls
-  DevBuf a2_tasks, a2_q, a2_t, a2_out, a2_scratch, a2_lists, a2_counts, a2_boff;
-  // mem_reg2aln batches (bwagpu_reg2aln_batch)
-  DevBuf r2_tasks, r2_q, r2_out, r2_cig, r2_md, r2_lists, r2_z, r2_stats;
-  // bins run concurrently on these (fork/join with events from the caller's stream)
-  static constexpr int kA2Streams = 4;
-  hipStream_t a2_st[kA2Streams] = {};
-  hipEvent_t a2_fork = nullptr, a2_join[kA2Streams] = {};
-  // seeding (bwagpu_set_bwt / bwagpu_collect_intv): the resident FM-index and
-  // the batch buffers
-  DevBuf bwt_words, sa_d, sa_in, sa_out, occ_d, sup_d, sa_full;
-  DevBwt bwt{};
-  bool has_bwt = false;
-  DevBuf sd_off, sd_seq, sd_out, sd_n, sd_scratch, sd_poff, sd_pack, sd_heavy, sd_dbg;
-  // seeding's chaining (bwagpu_seqs2chains / bwagpu_seqs2regions): per read,
-  // per SA position, the kbtree arenas, mem_seed_sw tasks, the packed chains
-  DevBuf ch_npos, ch_posoff, ch_frac, ch_nout, ch_noseed, ch_nsw, ch_need, ch_swtab, ch_alt;
-  DevBuf ch_kpos, ch_rbeg, ch_qinfo, ch_label, ch_score, ch_slist, ch_ord, ch_chains, ch_nodes;
-  DevBuf ch_ochains, ch_oslist, ch_bins, ch_dbg;
-  DevBuf ch_swoff, ch_swtasks, ch_swt, ch_swskip, ch_swres, ch_swscr;
-  DevBuf ch_ocoff, ch_osoff, ch_rco, ch_cso, ch_rid, ch_cfrac, ch_out, ch_seeds;
-  DevBuf ch_regoff, ch_regc;
-  HostBuf chh_tot, chh_rco, chh_cso, chh_chains, chh_seeds, chh_regs, chh_n;
-  HostBuf sdh_in;  // the reads of a seeding call, staged for the H2D
-  hipEvent_t sdh_done = nullptr;  // recorded after the H2D out of sdh_in
-  Slot ch_slot;  // chain2aln scratch of bwagpu_seqs2regions
-  ChainStreams ch_cs{};  // created on first use
-  bool has_alt = false;
-  // region post-processing (bwagpu_regs_post*, bwagpu_set_regs_post): mem_opt_t.b,
-  // the switch's options / flags / next batch's id0, the host entry's buffers
-  int opt_b = 0;
-  bwagpu_postopt_t post_opt{};
-  int32_t post_flags = 0;
-  int64_t post_id0 = 0;
-  DevBuf rp_regs, rp_seq, rp_soff, rp_roff, rp_n, rp_stats;
-  // paired ends (bwagpu_pestat*, bwagpu_mate_rescue*): the lists and counters of
-  // mem_pestat; mate rescue's per-pair work arrays, query pool, per-round task
-  // lists / window pools / results, and the host entries' copies of their arguments
-  DevBuf pe_isize, pe_cnt, pe_pes, pe_regs, pe_roff, pe_n;
-  DevBuf rs_pair, rs_soff, rs_tab, rs_toff, rs_boff, rs_qpool, rs_ctr, rs_scr;
-  DevBuf rs_tasks[kRescueMaxRounds], rs_tpool[kRescueMaxRounds], rs_res[kRescueMaxRounds];
-  DevBuf rs_in, rs_seq, rs_seqoff, rs_roff, rs_n, rs_ooff, rs_out, rs_outn, rs_status, rs_nsw;
-  int32_t rescue_drop = 0;  // bwagpu_debug_rescue_drop
-  // bwagpu_debug_rescue_times: per round of the last call, events before the plan,
-  // after it, after align2 and after the replay
-  hipEvent_t rs_ev[4 * kRescueMaxRounds] = {};
-  int rs_ev_rounds = 0;
-  hipStream_t rs_ev_stream = nullptr;
-  // primary marking and pair selection (bwagpu_mark_primary*, bwagpu_pair_select*):
-  // the marking kernel's per-block scratch, the log table (filled once), the
-  // pairing tables of the last call, and the host entries' copies of their arguments
-  DevBuf ps_scratch, ps_log, ps_erfc, ps_regs, ps_roff, ps_n, ps_npri, ps_status, ps_instat, ps_sel, ps_mapq;
-  bool ps_log_ready = false;
-  // the FPGA wire format (bwagpu_sw_stream)
-  DevBuf st_buf, st_start, st_q, st_tasks, st_lists, st_seen, st_ctr, st_out;
-  // bwt_extend calls tier 1 spends on a read before tier 2 (one wave per read)
-  // takes it: ~p90 of the C2 batch's per-read counts (mean 666, p90 975)
-  int seed_budget = 1024;
-  int sup_shift = 32;  // bwagpu_debug_sup_shift: superblock size of the next set_bwt
-  int dev_read_len = BWAGPU_MAX_READ_LEN;  // bwagpu_set_device_read_len
-  // bwagpu_debug_fail_wait: after fail_after more successful waits, _wait
-  // returns fail_code once (tests of the stage's recovery path)
-  int fail_after = -1, fail_code = 0;
-  // bwagpu_prof_*: event pairs around the dominant extension launches
-  std::vector<hipEvent_t> prof_ev;
-  int prof_used = 0;
-  std::string err;
-};
-
 namespace {
 
-int fail(bwagpu_ctx_t* c, int code, const std::string& msg) {
-  if (c) c->err = msg;
-  return code;
-}
-
-int hip_fail(bwagpu_ctx_t* c, hipError_t e, const char* what) {
-  std::string m = std::string(what) + ": " + hipGetErrorString(e);
-  if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) return fail(c, BWAGPU_E_NOMEM, m);
-  return fail(c, BWAGPU_E_DEVICE, m);
-}
-
-#define HIPC(call, what)                             \
-  do {                                               \
-    hipError_t e_ = (call);                          \
-    if (e_ != hipSuccess) return hip_fail(ctx, e_, what); \
-  } while (0)
 
 bool make_opt(const bwagpu_opt_t* o, DevOpt* d, std::string* why) {
   if (!o) { *why = "opt is NULL"; return false; }
@@ -496,15 +282,6 @@ A2Prof make_a2prof(const DevOpt& o, bool u8) {
   return P;
 }
 
-// scoring limits of the align2 kernels (reasons are the E_UNSUPPORTED text)
-const char* align2_opt_unsupported(const DevOpt& o) {
-  if (o.o_ins <= 0)
-    return "ksw_align2 with o_ins == 0: the reference's lazy-F early exit (ksw.c:180) then depends on "
-           "its SIMD lane order; run it on the CPU";
-  if (o.max_mat <= 0) return "ksw_align2 needs a positive match score (ksw.c:216 divides by it)";
-  if (o.o_ins > 65535 || o.e_ins > 65535 || o.o_del > 65535 || o.e_del > 65535) return "gap penalty > 65535";
-  return nullptr;
-}
 
 // Launch the given bins concurrently: fork the align2 streams off `st`,
 // deal the bins (in the given order) round-robin over them, join back.
@@ -618,14 +395,11 @@ void destroy_ctx(bwagpu_ctx_t* ctx) {
                     &ctx->ch_ord, &ctx->ch_chains, &ctx->ch_nodes, &ctx->ch_ochains, &ctx->ch_oslist, &ctx->ch_bins, &ctx->ch_dbg, &ctx->ch_swoff, &ctx->ch_swtasks, &ctx->ch_swt,
                     &ctx->ch_swskip, &ctx->ch_swres, &ctx->ch_swscr, &ctx->ch_ocoff, &ctx->ch_osoff, &ctx->ch_rco,
                     &ctx->ch_cso, &ctx->ch_rid, &ctx->ch_cfrac, &ctx->ch_out, &ctx->ch_seeds, &ctx->ch_regoff,
-                    &ctx->ch_regc, &ctx->rp_regs, &ctx->rp_seq, &ctx->rp_soff, &ctx->rp_roff, &ctx->rp_n,
-                    &ctx->rp_stats, &ctx->pe_isize, &ctx->pe_cnt, &ctx->pe_pes, &ctx->pe_regs, &ctx->pe_roff, &ctx->pe_n,
-                    &ctx->rs_pair, &ctx->rs_soff, &ctx->rs_tab, &ctx->rs_toff, &ctx->rs_boff, &ctx->rs_qpool,
-                    &ctx->rs_ctr, &ctx->rs_scr, &ctx->rs_in, &ctx->rs_seq, &ctx->rs_seqoff, &ctx->rs_roff, &ctx->rs_n,
-                    &ctx->rs_ooff, &ctx->rs_out, &ctx->rs_outn, &ctx->rs_status, &ctx->rs_nsw, &ctx->ps_scratch,
-                    &ctx->ps_log, &ctx->ps_erfc, &ctx->ps_regs, &ctx->ps_roff, &ctx->ps_n, &ctx->ps_npri, &ctx->ps_status,
-                    &ctx->ps_instat, &ctx->ps_sel, &ctx->ps_mapq})
+                    &ctx->ch_regc, &ctx->rp_stats, &ctx->pe_isize, &ctx->pe_cnt, &ctx->rs_pair, &ctx->rs_soff,
+                    &ctx->rs_tab, &ctx->rs_toff, &ctx->rs_boff, &ctx->rs_qpool, &ctx->rs_ctr, &ctx->rs_scr,
+                    &ctx->ps_scratch, &ctx->ps_log, &ctx->ps_erfc})
     b->release();
+  ctx->stg.release();
   for (hipEvent_t e : ctx->rs_ev)
     if (e) (void)hipEventDestroy(e);
   for (int k = 0; k < kRescueMaxRounds; ++k)
@@ -1030,30 +804,6 @@ int enqueue_chain2aln(bwagpu_ctx_t* ctx, Slot& s, const DevBatch& db, int lq_max
 
 }  // namespace
 
-namespace {
-// the post-processing pass over read spans in device memory (regpost.hip)
-int enqueue_regpost(bwagpu_ctx_t* ctx, const bwagpu_postopt_t& po, int32_t flags, int64_t id0, int32_t n_reads,
-                    const int64_t* seq_off, const uint8_t* seq, const int64_t* reg_off, const int32_t* rco,
-                    const int32_t* cso, bwagpu_alnreg_t* regs, int32_t* n, int64_t* stats, hipStream_t st) {
-  RegPostArgs a{};
-  a.n_reads = n_reads;
-  a.flags = flags;
-  a.id0 = id0;
-  a.po = po;
-  a.opt_b = ctx->opt_b;
-  a.seq_off = seq_off;
-  a.seq = seq;
-  a.reg_off = reg_off;
-  a.rco = rco;
-  a.cso = cso;
-  a.regs = regs;
-  a.n = n;
-  a.alt = ctx->has_alt ? ctx->ch_alt.as<uint8_t>() : nullptr;
-  a.stats = stats;
-  HIPC(launch_regpost(ctx->opt, ctx->ref, a, st), "regpost launch");
-  return BWAGPU_OK;
-}
-}  // namespace
 
 extern "C" {
 
@@ -1474,10 +1224,8 @@ int bwagpu_extend_batch(bwagpu_ctx_t* ctx, int32_t n, const bwagpu_ext_task_t* t
   if (qpool_len && (rc = ck(hipMemcpyAsync(d_q.p, qpool, (size_t)qpool_len, hipMemcpyHostToDevice, st), "H2D"))) return rc;
   if (tpool_len && (rc = ck(hipMemcpyAsync(d_t.p, tpool, (size_t)tpool_len, hipMemcpyHostToDevice, st), "H2D"))) return rc;
   if ((rc = ck(hipMemsetAsync(d_stats.p, 0, sizeof(int64_t) * ST_N, st), "memset"))) return rc;
-  hipEvent_t e0, e1;
-  (void)hipEventCreate(&e0);
-  (void)hipEventCreate(&e1);
-  (void)hipEventRecord(e0, st);
+  EventPair ev;
+  (void)ev.start(st);
   int32_t off = 0;
   std::vector<int32_t> all;
   for (int v = 0; v <= kNumExtVariants; ++v) all.insert(all.end(), lists[v].begin(), lists[v].end());
@@ -1511,17 +1259,13 @@ int bwagpu_extend_batch(bwagpu_ctx_t* ctx, int32_t n, const bwagpu_ext_task_t* t
     }
     off += nv;
   }
-  (void)hipEventRecord(e1, st);
+  (void)ev.stop(st);
   int64_t hs[ST_N];
   if ((rc = ck(hipMemcpyAsync(results, d_res.p, sizeof(bwagpu_ext_result_t) * n, hipMemcpyDeviceToHost, st), "D2H"))) return rc;
   if ((rc = ck(hipMemcpyAsync(hs, d_stats.p, sizeof(hs), hipMemcpyDeviceToHost, st), "D2H"))) return rc;
   if ((rc = ck(hipStreamSynchronize(st), "extend batch"))) return rc;
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   s.last = bwagpu_stats_t{};
-  s.last.kernel_ms = ms;
+  s.last.kernel_ms = ev.ms();
   s.last.cells = hs[ST_CELLS];
   s.last.rows = hs[ST_ROWS];
   s.last.ext_calls = hs[ST_CALLS];
@@ -1685,10 +1429,8 @@ int bwagpu_reg2aln_batch(bwagpu_ctx_t* ctx, int32_t n, const bwagpu_reg2aln_task
   }
   std::sort(launches.begin(), launches.end(), [](const Launch& x, const Launch& y) { return x.work > y.work; });
   const int used = std::min<int>(NS, (int)launches.size());
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  HIPC(hipEventCreate(&e0), "event");
-  HIPC(hipEventCreate(&e1), "event");
-  HIPC(hipEventRecord(e0, st), "event");
+  EventPair ev;
+  HIPC(ev.start(st), "event");
   HIPC(hipEventRecord(ctx->a2_fork, st), "event");
   for (int i = 0; i < used; ++i) HIPC(hipStreamWaitEvent(ctx->a2_st[i], ctx->a2_fork, 0), "stream wait");
   auto make_args = [&](const Launch& L, int& wpb) {
@@ -1719,11 +1461,8 @@ int bwagpu_reg2aln_batch(bwagpu_ctx_t* ctx, int32_t n, const bwagpu_reg2aln_task
   for (Launch& L : launches) {
     int wpb = 4;
     const R2AArgs a = make_args(L, wpb);
-    if ((size_t)wpb * a.lds_per_wave > 160 * 1024) {
-      (void)hipEventDestroy(e0);
-      (void)hipEventDestroy(e1);
+    if ((size_t)wpb * a.lds_per_wave > 160 * 1024)
       return fail(ctx, BWAGPU_E_UNSUPPORTED, "reg2aln job needs more LDS than a workgroup has");
-    }
     int waves = r2_resident_waves(kR2CD[L.bk], (size_t)wpb * a.lds_per_wave, wpb);
     if (L.cls == 2) {
       waves = (int)std::min<int64_t>(waves, std::max<int64_t>(4, ((int64_t)1 << 30) / a.zstride));
@@ -1749,20 +1488,16 @@ int bwagpu_reg2aln_batch(bwagpu_ctx_t* ctx, int32_t n, const bwagpu_reg2aln_task
     HIPC(hipEventRecord(ctx->a2_join[i], ctx->a2_st[i]), "event");
     HIPC(hipStreamWaitEvent(st, ctx->a2_join[i], 0), "stream wait");
   }
-  HIPC(hipEventRecord(e1, st), "event");
+  HIPC(ev.stop(st), "event");
   HIPC(hipMemcpyAsync(out, ctx->r2_out.p, sizeof(bwagpu_aln_t) * n, hipMemcpyDeviceToHost, st), "D2H");
   HIPC(hipMemcpyAsync(cigar, ctx->r2_cig.p, sizeof(uint32_t) * (size_t)n * max_ops, hipMemcpyDeviceToHost, st), "D2H");
   HIPC(hipMemcpyAsync(md, ctx->r2_md.p, (size_t)n * max_md, hipMemcpyDeviceToHost, st), "D2H");
   int64_t hst[ST_N];
   HIPC(hipMemcpyAsync(hst, ctx->r2_stats.p, sizeof(hst), hipMemcpyDeviceToHost, st), "D2H");
   HIPC(hipStreamSynchronize(st), "reg2aln execution");
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   Slot& s0 = ctx->slot[0];
   s0.last = bwagpu_stats_t{};
-  s0.last.kernel_ms = ms;
+  s0.last.kernel_ms = ev.ms();
   s0.last.cells = hst[ST_CELLS];
   s0.last.rows = hst[ST_ROWS];
   s0.last.ext_calls = hst[ST_CALLS];
@@ -1839,10 +1574,8 @@ int bwagpu_align2_batch(bwagpu_ctx_t* ctx, int32_t n, const bwagpu_align2_task_t
   HIPC(hipMemcpyAsync(d_counts, counts, sizeof(counts), hipMemcpyHostToDevice, st), "H2D");  // + zero cursors
   HIPC(hipMemsetAsync(d_stats, 0, sizeof(int64_t) * ST_N, st), "memset");
   HIPC(hipMemcpyAsync(ctx->a2_boff.p, boff.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice, st), "H2D");
-  hipEvent_t e0 = nullptr, e1 = nullptr;  // own events: slot 0's may time an in-flight chain2aln batch
-  HIPC(hipEventCreate(&e0), "event");
-  HIPC(hipEventCreate(&e1), "event");
-  HIPC(hipEventRecord(e0, st), "event");
+  EventPair ev;  // own events: slot 0's may time an in-flight chain2aln batch
+  HIPC(ev.start(st), "event");
   {
     A2Args base{ctx->a2_tasks.as<bwagpu_align2_task_t>(), ctx->a2_q.as<uint8_t>(), ctx->a2_t.as<uint8_t>(),
                 ctx->a2_out.as<bwagpu_kswr_t>(), ctx->a2_scratch.as<int2>(), ctx->a2_boff.as<int64_t>(),
@@ -1850,17 +1583,13 @@ int bwagpu_align2_batch(bwagpu_ctx_t* ctx, int32_t n, const bwagpu_align2_task_t
     const int rc = launch_align2_concurrent(ctx, st, bins, base, list_off, counts, d_counts, d_counts + kA2Bins, 0);
     if (rc) return rc;
   }
-  HIPC(hipEventRecord(e1, st), "event");
+  HIPC(ev.stop(st), "event");
   int64_t hs[ST_N];
   HIPC(hipMemcpyAsync(results, ctx->a2_out.p, sizeof(bwagpu_kswr_t) * n, hipMemcpyDeviceToHost, st), "D2H");
   HIPC(hipMemcpyAsync(hs, d_stats, sizeof(hs), hipMemcpyDeviceToHost, st), "D2H");
   HIPC(hipStreamSynchronize(st), "align2 batch");
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   s.last = bwagpu_stats_t{};
-  s.last.kernel_ms = ms;
+  s.last.kernel_ms = ev.ms();
   s.last.cells = hs[ST_CELLS];
   s.last.rows = hs[ST_ROWS];
   s.last.ext_calls = hs[ST_CALLS];
@@ -1873,9 +1602,8 @@ int bwagpu_align2_device(bwagpu_ctx_t* ctx, int32_t n, const bwagpu_align2_task_
   if (!ctx || n < 0 || (n && (!dev_tasks || !dev_results || !dev_scratch))) return BWAGPU_E_INVAL;
   if (n == 0) return BWAGPU_OK;
   if (const char* why = align2_opt_unsupported(ctx->opt)) return fail(ctx, BWAGPU_E_UNSUPPORTED, why);
-  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
-  hipStream_t st = (hipStream_t)stream;
-  if (!st) HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
+  hipStream_t st = nullptr;
+  if (int rc = entry_stream(ctx, stream, &st)) return rc;
   HIPC(ctx->a2_lists.ensure(sizeof(int32_t) * (size_t)kA2Bins * n), "hipMalloc");
   HIPC(ctx->a2_boff.ensure(sizeof(int64_t) * n), "hipMalloc");
   // counts[kA2Bins] | cursors[kA2Bins] | scratch cursor (u64) | stats[ST_N]
@@ -1915,9 +1643,8 @@ int bwagpu_debug_fail_wait(bwagpu_ctx_t* ctx, int after_n_waits, int code) {
 
 int bwagpu_debug_occupancy(bwagpu_ctx_t* ctx, void* stream, int64_t* out) {
   if (!ctx || !out) return BWAGPU_E_INVAL;
-  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
-  hipStream_t st = (hipStream_t)stream;
-  if (!st) HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
+  hipStream_t st = nullptr;
+  if (int rc = entry_stream(ctx, stream, &st)) return rc;
   int k = 0;
   while (k < BWAGPU_NUM_SLOTS && ctx->dev_stream[k] != st) ++k;
   if (k == BWAGPU_NUM_SLOTS || !ctx->dev_scratch[k].d_ctr.p) return fail(ctx, BWAGPU_E_INVAL, "no device-entry batch on this stream");
@@ -1934,9 +1661,8 @@ int bwagpu_debug_occupancy(bwagpu_ctx_t* ctx, void* stream, int64_t* out) {
 
 int bwagpu_debug_spec_counters(bwagpu_ctx_t* ctx, void* stream, int64_t* out) {
   if (!ctx || !out) return BWAGPU_E_INVAL;
-  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
-  hipStream_t st = (hipStream_t)stream;
-  if (!st) HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
+  hipStream_t st = nullptr;
+  if (int rc = entry_stream(ctx, stream, &st)) return rc;
   int k = 0;
   while (k < BWAGPU_NUM_SLOTS && ctx->dev_stream[k] != st) ++k;
   if (k == BWAGPU_NUM_SLOTS || !ctx->dev_scratch[k].d_ctr.p) return fail(ctx, BWAGPU_E_INVAL, "no device-entry batch on this stream");
@@ -1959,9 +1685,8 @@ int bwagpu_debug_spec_counters(bwagpu_ctx_t* ctx, void* stream, int64_t* out) {
 
 int bwagpu_debug_spec_ext(bwagpu_ctx_t* ctx, void* stream, void* host_out, int32_t n) {
   if (!ctx || !host_out || n < 0) return BWAGPU_E_INVAL;
-  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
-  hipStream_t st = (hipStream_t)stream;
-  if (!st) HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
+  hipStream_t st = nullptr;
+  if (int rc = entry_stream(ctx, stream, &st)) return rc;
   int k = 0;
   while (k < BWAGPU_NUM_SLOTS && ctx->dev_stream[k] != st) ++k;
   if (k == BWAGPU_NUM_SLOTS || !ctx->dev_scratch[k].d_ext.p || ctx->dev_scratch[k].d_ext.cap < sizeof(SeedExt) * (size_t)n)
@@ -2749,665 +2474,5 @@ extern "C" int bwagpu_seqs2regions(bwagpu_ctx_t* ctx, const bwagpu_seedopt_t* so
   if (tot[6] & ERR_POST) return fail(ctx, BWAGPU_E_UNSUPPORTED, "a patch candidate's window exceeds 4096 bases");
   if (tot[6] & ERR_RID)
     return fail(ctx, BWAGPU_E_RESULTS, "a chain's first seed is not inside contig chain_rid (bwamem.c:669 assert)");
-  return BWAGPU_OK;
-}
-
-// ------------------------------------------------------------------ region post-processing
-extern "C" int bwagpu_set_regs_post(bwagpu_ctx_t* ctx, const bwagpu_postopt_t* popt, int32_t flags,
-                                    int64_t id0_of_next_batch) {
-  if (!ctx) return BWAGPU_E_INVAL;
-  const int32_t all = BWAGPU_POST_DEDUP_PATCH | BWAGPU_POST_MARK_ALT | BWAGPU_POST_PRIMARY;
-  if (flags < 0 || (flags & ~all)) return fail(ctx, BWAGPU_E_INVAL, "unknown flag");
-  if (flags & BWAGPU_POST_PRIMARY) return fail(ctx, BWAGPU_E_UNSUPPORTED, "BWAGPU_POST_PRIMARY is not implemented");
-  if (flags && !post_opt_ok(popt)) return fail(ctx, BWAGPU_E_INVAL, "bad bwagpu_postopt_t");
-  if (popt) ctx->post_opt = *popt;
-  ctx->post_flags = flags;
-  ctx->post_id0 = id0_of_next_batch;
-  return BWAGPU_OK;
-}
-
-extern "C" int bwagpu_regs_post_device(bwagpu_ctx_t* ctx, const bwagpu_postopt_t* popt, int32_t flags, int64_t id0,
-                                       const bwagpu_batch_t* b, const int64_t* dev_reg_off, bwagpu_alnreg_t* dev_regs,
-                                       int32_t* dev_n, void* stream) {
-  if (!ctx || !b) return BWAGPU_E_INVAL;
-  const int32_t all = BWAGPU_POST_DEDUP_PATCH | BWAGPU_POST_MARK_ALT | BWAGPU_POST_PRIMARY;
-  if (flags < 0 || (flags & ~all)) return fail(ctx, BWAGPU_E_INVAL, "unknown flag");
-  if (flags & BWAGPU_POST_PRIMARY) return fail(ctx, BWAGPU_E_UNSUPPORTED, "BWAGPU_POST_PRIMARY is not implemented");
-  if (!post_opt_ok(popt)) return fail(ctx, BWAGPU_E_INVAL, "bad bwagpu_postopt_t");
-  if (b->n_reads < 0) return fail(ctx, BWAGPU_E_INVAL, "negative read count");
-  if (b->n_reads == 0 || flags == 0) return BWAGPU_OK;
-  if (!dev_regs || !dev_n || !b->seq_off || !b->seq || (!dev_reg_off && (!b->read_chain_off || !b->chain_seed_off)))
-    return fail(ctx, BWAGPU_E_INVAL, "NULL array");
-  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
-  hipStream_t st = (hipStream_t)stream;
-  if (!st) HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
-  return enqueue_regpost(ctx, *popt, flags, id0, b->n_reads, b->seq_off, b->seq, dev_reg_off, b->read_chain_off,
-                         b->chain_seed_off, dev_regs, dev_n, nullptr, st);
-}
-
-extern "C" int bwagpu_regs_post(bwagpu_ctx_t* ctx, const bwagpu_postopt_t* popt, int32_t flags, int64_t id0,
-                                int32_t n_reads, const int64_t* seq_off, const uint8_t* seq, const int64_t* reg_off,
-                                bwagpu_alnreg_t* regs, int32_t* n) {
-  if (!ctx) return BWAGPU_E_INVAL;
-  PostPlan plan;
-  const char* why = "";
-  int rc = post_check(popt, flags, n_reads, seq_off, seq, reg_off, regs, n, &plan, &why);
-  if (rc) return fail(ctx, rc, why);
-  if (n_reads == 0 || flags == 0 || plan.n_regs == 0) return BWAGPU_OK;
-  const size_t nr = (size_t)n_reads;
-  const size_t span = (size_t)(plan.hi - plan.lo), nseq = (size_t)(plan.seq_hi - plan.seq_lo);
-  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
-  hipStream_t st = nullptr;
-  HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
-  HIPC(ctx->rp_regs.ensure(sizeof(bwagpu_alnreg_t) * span), "hipMalloc");
-  HIPC(ctx->rp_seq.ensure(nseq + 1), "hipMalloc");
-  HIPC(ctx->rp_soff.ensure(sizeof(int64_t) * (nr + 1)), "hipMalloc");
-  HIPC(ctx->rp_roff.ensure(sizeof(int64_t) * nr), "hipMalloc");
-  HIPC(ctx->rp_n.ensure(sizeof(int32_t) * nr), "hipMalloc");
-  HIPC(ctx->rp_stats.ensure(sizeof(int64_t) * ST_N), "hipMalloc");
-  // offsets relative to what is copied: regs[lo ..), seq[seq_lo ..)
-  std::vector<int64_t> soff(nr + 1), roff(nr);
-  for (size_t r = 0; r <= nr; ++r) soff[r] = seq_off[r] - plan.seq_lo;
-  for (size_t r = 0; r < nr; ++r) roff[r] = n[r] ? reg_off[r] - plan.lo : 0;
-  HIPC(hipMemcpyAsync(ctx->rp_regs.p, regs + plan.lo, sizeof(bwagpu_alnreg_t) * span, hipMemcpyHostToDevice, st), "H2D");
-  if (nseq) HIPC(hipMemcpyAsync(ctx->rp_seq.p, seq + plan.seq_lo, nseq, hipMemcpyHostToDevice, st), "H2D");
-  HIPC(hipMemcpyAsync(ctx->rp_soff.p, soff.data(), sizeof(int64_t) * (nr + 1), hipMemcpyHostToDevice, st), "H2D");
-  HIPC(hipMemcpyAsync(ctx->rp_roff.p, roff.data(), sizeof(int64_t) * nr, hipMemcpyHostToDevice, st), "H2D");
-  HIPC(hipMemcpyAsync(ctx->rp_n.p, n, sizeof(int32_t) * nr, hipMemcpyHostToDevice, st), "H2D");
-  HIPC(hipMemsetAsync(ctx->rp_stats.p, 0, sizeof(int64_t) * ST_N, st), "memset");
-  HIPC(hipStreamSynchronize(st), "H2D");  // soff / roff are pageable locals
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  HIPC(hipEventCreate(&e0), "event");
-  HIPC(hipEventCreate(&e1), "event");
-  HIPC(hipEventRecord(e0, st), "event");
-  rc = enqueue_regpost(ctx, *popt, flags, id0, n_reads, ctx->rp_soff.as<int64_t>(), ctx->rp_seq.as<uint8_t>(),
-                       ctx->rp_roff.as<int64_t>(), nullptr, nullptr, ctx->rp_regs.as<bwagpu_alnreg_t>(),
-                       ctx->rp_n.as<int32_t>(), ctx->rp_stats.as<int64_t>(), st);
-  if (rc) {
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return rc;
-  }
-  HIPC(hipEventRecord(e1, st), "event");
-  int64_t hst[ST_N] = {};
-  HIPC(hipMemcpyAsync(regs + plan.lo, ctx->rp_regs.p, sizeof(bwagpu_alnreg_t) * span, hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipMemcpyAsync(n, ctx->rp_n.p, sizeof(int32_t) * nr, hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipMemcpyAsync(hst, ctx->rp_stats.p, sizeof(hst), hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipStreamSynchronize(st), "regpost execution");
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  Slot& s0 = ctx->slot[0];
-  s0.last = bwagpu_stats_t{};
-  s0.last.kernel_ms = ms;
-  s0.last.ext_calls = hst[ST_CALLS];
-  s0.last.h2d_bytes = (int64_t)(sizeof(bwagpu_alnreg_t) * span + nseq + sizeof(int64_t) * (2 * nr + 1) + sizeof(int32_t) * nr);
-  s0.last.d2h_bytes = (int64_t)(sizeof(bwagpu_alnreg_t) * span + sizeof(int32_t) * nr);
-  if (hst[ST_ERR] & ERR_POST) return fail(ctx, BWAGPU_E_UNSUPPORTED, "a patch candidate's window exceeds 4096 bases");
-  return BWAGPU_OK;
-}
-
-// ------------------------------------------------------------------ paired ends: mem_pestat, mate rescue
-namespace {
-
-// mem_pestat over spans in device memory (rescue.hip); pes: 4 records in device memory
-int enqueue_pestat(bwagpu_ctx_t* ctx, const bwagpu_pairopt_t& po, int32_t n_reads, const int64_t* reg_off,
-                   const bwagpu_alnreg_t* regs, const int32_t* n, bwagpu_pestat_t* pes, hipStream_t st) {
-  PestatArgs a{};
-  a.n_pairs = n_reads >> 1;
-  a.cap = 1;
-  while (a.cap < a.n_pairs) a.cap <<= 1;
-  a.po = po;
-  a.reg_off = reg_off;
-  a.regs = regs;
-  a.n = n;
-  HIPC(ctx->pe_isize.ensure(sizeof(uint64_t) * 4 * (size_t)a.cap), "hipMalloc");
-  HIPC(ctx->pe_cnt.ensure(sizeof(int32_t) * 4), "hipMalloc");
-  HIPC(hipMemsetAsync(ctx->pe_cnt.p, 0, sizeof(int32_t) * 4, st), "memset");
-  a.isize = ctx->pe_isize.as<uint64_t>();
-  a.cnt = ctx->pe_cnt.as<int32_t>();
-  a.pes = pes;
-  HIPC(launch_pestat(ctx->opt, ctx->ref, a, st), "pestat launch");
-  return BWAGPU_OK;
-}
-
-struct RescueRun {
-  int rounds = 0;
-  int64_t tasks = 0;  // ksw_align2 tasks computed over all rounds
-  float ms = 0;
-};
-
-// Mate rescue over device memory.  The counts of every round come to the host
-// (stream waits); the last round's replay is left running on st.
-int enqueue_rescue(bwagpu_ctx_t* ctx, const bwagpu_pairopt_t& po, const bwagpu_pestat_t* dev_pes, int32_t n_reads,
-                   int64_t seq_bytes, const int64_t* seq_off, const uint8_t* seq, const int64_t* reg_off,
-                   const bwagpu_alnreg_t* regs, const int32_t* n, const int64_t* out_off, bwagpu_alnreg_t* out_regs,
-                   int32_t* out_n, int32_t* status, int32_t* n_sw, hipStream_t st, RescueRun* run) {
-  const int32_t np = n_reads >> 1;
-  const size_t npz = (size_t)np;
-  RescueArgs a{};
-  a.n_pairs = np;
-  a.po = po;
-  a.pes = dev_pes;
-  a.seq_off = seq_off;
-  a.seq = seq;
-  a.reg_off = reg_off;
-  a.regs = regs;
-  a.n = n;
-  a.out_off = out_off;
-  a.out_regs = out_regs;
-  a.out_n = out_n;
-  a.status = status;
-  a.n_sw = n_sw;
-  // per pair: pstate | nb0 | nslot | ntask | tbytes
-  HIPC(ctx->rs_pair.ensure(sizeof(int32_t) * 5 * npz), "hipMalloc");
-  HIPC(ctx->rs_soff.ensure(sizeof(int64_t) * (npz + 1)), "hipMalloc");
-  HIPC(ctx->rs_toff.ensure(sizeof(int64_t) * (npz + 1)), "hipMalloc");
-  HIPC(ctx->rs_boff.ensure(sizeof(int64_t) * (npz + 1)), "hipMalloc");
-  HIPC(ctx->rs_qpool.ensure(2 * (size_t)seq_bytes + 64), "hipMalloc");
-  HIPC(ctx->rs_ctr.ensure(sizeof(int32_t) * RC_WORDS), "hipMalloc");
-  HIPC(ctx->chh_tot.ensure(sizeof(int64_t) * 16), "hipHostMalloc");
-  a.pstate = ctx->rs_pair.as<int32_t>();
-  a.nb0 = a.pstate + npz;
-  a.nslot = a.nb0 + npz;
-  a.ntask = a.nslot + npz;
-  a.tbytes = a.ntask + npz;
-  a.slot_off = ctx->rs_soff.as<int64_t>();
-  a.task_off = ctx->rs_toff.as<int64_t>();
-  a.tb_off = ctx->rs_boff.as<int64_t>();
-  a.qpool = ctx->rs_qpool.as<uint8_t>();
-  a.rc_base = seq_bytes;
-  a.ctr = ctx->rs_ctr.as<int32_t>();
-  int64_t* tot = ctx->chh_tot.as<int64_t>();
-  ctx->rs_ev_rounds = 0;
-  ctx->rs_ev_stream = st;
-  HIPC(launch_rescue_pool(a, st), "rescue_pool launch");
-  HIPC(launch_rescue_init(ctx->opt, a, st), "rescue_init launch");
-  HIPC(launch_scan_i32(a.nslot, ctx->rs_soff.as<int64_t>(), np, st), "scan launch");
-  HIPC(hipMemcpyAsync(tot + 8, ctx->rs_soff.as<int64_t>() + np, sizeof(int64_t), hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipStreamSynchronize(st), "sync");
-  const int64_t S = tot[8];
-  HIPC(ctx->rs_tab.ensure(sizeof(int32_t) * (size_t)std::max<int64_t>(S, 1)), "hipMalloc");
-  HIPC(hipMemsetAsync(ctx->rs_tab.p, 0xff, sizeof(int32_t) * (size_t)std::max<int64_t>(S, 1), st), "memset");  // RS_NONE
-  a.tab = ctx->rs_tab.as<int32_t>();
-  HIPC(hipMemsetAsync(a.ctr, 0, sizeof(int32_t) * RC_WORDS, st), "memset");
-  for (int round = 0; round < po.max_rounds; ++round) {
-    a.round = round;
-    a.drop = round == 0 ? ctx->rescue_drop : 0;
-    HIPC(hipMemsetAsync(a.ctr + RC_PENDING, 0, sizeof(int32_t), st), "memset");
-    hipEvent_t* ev = ctx->rs_ev + 4 * round;
-    for (int k = 0; k < 4; ++k)
-      if (!ev[k]) HIPC(hipEventCreate(&ev[k]), "hipEventCreate");
-    HIPC(hipEventRecord(ev[0], st), "event");
-    HIPC(launch_rescue_plan(ctx->opt, ctx->ref, a, false, st), "rescue_plan launch");
-    HIPC(launch_scan_i32(a.ntask, ctx->rs_toff.as<int64_t>(), np, st), "scan launch");
-    HIPC(launch_scan_i32(a.tbytes, ctx->rs_boff.as<int64_t>(), np, st), "scan launch");
-    HIPC(hipMemcpyAsync(tot + 9, ctx->rs_toff.as<int64_t>() + np, sizeof(int64_t), hipMemcpyDeviceToHost, st), "D2H");
-    HIPC(hipMemcpyAsync(tot + 10, ctx->rs_boff.as<int64_t>() + np, sizeof(int64_t), hipMemcpyDeviceToHost, st), "D2H");
-    HIPC(hipStreamSynchronize(st), "sync");
-    const int64_t T = tot[9], B = tot[10];
-    if (T >= (int64_t)1 << kRescueIdxBits) return fail(ctx, BWAGPU_E_UNSUPPORTED, "too many rescue alignments in one batch");
-    if (T) {
-      HIPC(ctx->rs_tasks[round].ensure(sizeof(bwagpu_align2_task_t) * (size_t)T), "hipMalloc");
-      HIPC(ctx->rs_tpool[round].ensure((size_t)B + 64), "hipMalloc");
-      HIPC(ctx->rs_res[round].ensure(sizeof(bwagpu_kswr_t) * (size_t)T), "hipMalloc");
-      HIPC(ctx->rs_scr.ensure(8 * ((size_t)B + (size_t)T)), "hipMalloc");
-      a.tasks = ctx->rs_tasks[round].as<bwagpu_align2_task_t>();
-      a.tpool = ctx->rs_tpool[round].as<uint8_t>();
-      a.res[round] = ctx->rs_res[round].as<bwagpu_kswr_t>();
-      HIPC(launch_rescue_plan(ctx->opt, ctx->ref, a, true, st), "rescue_plan launch");
-      HIPC(hipEventRecord(ev[1], st), "event");
-      if (int rc = bwagpu_align2_device(ctx, (int32_t)T, a.tasks, a.qpool, a.tpool, ctx->rs_res[round].as<bwagpu_kswr_t>(),
-                                        ctx->rs_scr.p, st))
-        return rc;
-      run->tasks += T;
-    } else {
-      HIPC(hipEventRecord(ev[1], st), "event");
-    }
-    HIPC(hipEventRecord(ev[2], st), "event");
-    HIPC(launch_rescue_apply(ctx->opt, ctx->ref, a, st), "rescue_apply launch");
-    HIPC(hipEventRecord(ev[3], st), "event");
-    run->rounds = ctx->rs_ev_rounds = round + 1;
-    if (round + 1 == po.max_rounds) break;
-    HIPC(hipMemcpyAsync(tot + 11, a.ctr, sizeof(int32_t) * 2, hipMemcpyDeviceToHost, st), "D2H");
-    HIPC(hipStreamSynchronize(st), "sync");
-    if (reinterpret_cast<const int32_t*>(tot + 11)[RC_PENDING] == 0) break;
-  }
-  return BWAGPU_OK;
-}
-
-}  // namespace
-
-extern "C" int bwagpu_debug_rescue_drop(bwagpu_ctx_t* ctx, int32_t k) {
-  if (!ctx || k < 0) return BWAGPU_E_INVAL;
-  ctx->rescue_drop = k;
-  return BWAGPU_OK;
-}
-
-extern "C" int bwagpu_debug_rescue_times(bwagpu_ctx_t* ctx, double* out) {
-  if (!ctx || !out) return BWAGPU_E_INVAL;
-  out[0] = out[1] = out[2] = 0;
-  out[3] = ctx->rs_ev_rounds;
-  if (ctx->rs_ev_rounds == 0) return BWAGPU_OK;
-  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
-  HIPC(hipEventSynchronize(ctx->rs_ev[4 * (ctx->rs_ev_rounds - 1) + 3]), "event sync");
-  for (int r = 0; r < ctx->rs_ev_rounds; ++r)
-    for (int k = 0; k < 3; ++k) {
-      float ms = 0;
-      HIPC(hipEventElapsedTime(&ms, ctx->rs_ev[4 * r + k], ctx->rs_ev[4 * r + k + 1]), "event time");
-      out[k] += ms;
-    }
-  return BWAGPU_OK;
-}
-
-extern "C" int bwagpu_pestat_device(bwagpu_ctx_t* ctx, const bwagpu_pairopt_t* popt, int32_t n_reads,
-                                    const int64_t* dev_reg_off, const bwagpu_alnreg_t* dev_regs, const int32_t* dev_n,
-                                    bwagpu_pestat_t* dev_pes, void* stream) {
-  if (!ctx) return BWAGPU_E_INVAL;
-  if (!pair_opt_ok(popt)) return fail(ctx, BWAGPU_E_INVAL, "bad bwagpu_pairopt_t");
-  if (n_reads < 0) return fail(ctx, BWAGPU_E_INVAL, "negative read count");
-  if (!dev_pes || ((n_reads >> 1) && (!dev_reg_off || !dev_regs || !dev_n))) return fail(ctx, BWAGPU_E_INVAL, "NULL array");
-  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
-  hipStream_t st = (hipStream_t)stream;
-  if (!st) HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
-  return enqueue_pestat(ctx, *popt, n_reads, dev_reg_off, dev_regs, dev_n, dev_pes, st);
-}
-
-extern "C" int bwagpu_pestat(bwagpu_ctx_t* ctx, const bwagpu_pairopt_t* popt, int32_t n_reads, const int64_t* reg_off,
-                             const bwagpu_alnreg_t* regs, const int32_t* n, bwagpu_pestat_t* pes) {
-  if (!ctx) return BWAGPU_E_INVAL;
-  RescuePlan plan;
-  const char* why = "";
-  int rc = pestat_check(popt, n_reads, reg_off, regs, n, pes, &plan, &why);
-  if (rc) return fail(ctx, rc, why);
-  const size_t nr = (size_t)(n_reads & ~1), span = (size_t)(plan.hi - plan.lo);
-  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
-  hipStream_t st = nullptr;
-  HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
-  HIPC(ctx->pe_regs.ensure(sizeof(bwagpu_alnreg_t) * std::max<size_t>(span, 1)), "hipMalloc");
-  HIPC(ctx->pe_roff.ensure(sizeof(int64_t) * std::max<size_t>(nr, 1)), "hipMalloc");
-  HIPC(ctx->pe_n.ensure(sizeof(int32_t) * std::max<size_t>(nr, 1)), "hipMalloc");
-  HIPC(ctx->pe_pes.ensure(sizeof(bwagpu_pestat_t) * 4), "hipMalloc");
-  std::vector<int64_t> roff(nr);
-  for (size_t r = 0; r < nr; ++r) roff[r] = n[r] ? reg_off[r] - plan.lo : 0;
-  if (span) HIPC(hipMemcpyAsync(ctx->pe_regs.p, regs + plan.lo, sizeof(bwagpu_alnreg_t) * span, hipMemcpyHostToDevice, st), "H2D");
-  if (nr) {
-    HIPC(hipMemcpyAsync(ctx->pe_roff.p, roff.data(), sizeof(int64_t) * nr, hipMemcpyHostToDevice, st), "H2D");
-    HIPC(hipMemcpyAsync(ctx->pe_n.p, n, sizeof(int32_t) * nr, hipMemcpyHostToDevice, st), "H2D");
-  }
-  HIPC(hipStreamSynchronize(st), "H2D");  // roff is a pageable local
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  HIPC(hipEventCreate(&e0), "event");
-  HIPC(hipEventCreate(&e1), "event");
-  HIPC(hipEventRecord(e0, st), "event");
-  rc = enqueue_pestat(ctx, *popt, (int32_t)nr, ctx->pe_roff.as<int64_t>(), ctx->pe_regs.as<bwagpu_alnreg_t>(),
-                      ctx->pe_n.as<int32_t>(), ctx->pe_pes.as<bwagpu_pestat_t>(), st);
-  if (rc) {
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return rc;
-  }
-  HIPC(hipEventRecord(e1, st), "event");
-  HIPC(hipMemcpyAsync(pes, ctx->pe_pes.p, sizeof(bwagpu_pestat_t) * 4, hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipStreamSynchronize(st), "pestat execution");
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  Slot& s0 = ctx->slot[0];
-  s0.last = bwagpu_stats_t{};
-  s0.last.kernel_ms = ms;
-  return BWAGPU_OK;
-}
-
-extern "C" int bwagpu_mate_rescue_device(bwagpu_ctx_t* ctx, const bwagpu_pairopt_t* popt, const bwagpu_pestat_t* dev_pes,
-                                         const bwagpu_batch_t* b, const int64_t* dev_reg_off,
-                                         const bwagpu_alnreg_t* dev_regs, const int32_t* dev_n,
-                                         const int64_t* dev_out_off, bwagpu_alnreg_t* dev_out_regs, int32_t* dev_out_n,
-                                         int32_t* dev_status, int32_t* dev_n_sw, void* stream) {
-  if (!ctx || !b) return BWAGPU_E_INVAL;
-  if (!pair_opt_ok(popt)) return fail(ctx, BWAGPU_E_INVAL, "bad bwagpu_pairopt_t");
-  if (b->n_reads < 0) return fail(ctx, BWAGPU_E_INVAL, "negative read count");
-  if (b->n_reads & 1) return fail(ctx, BWAGPU_E_INVAL, "odd read count: reads 2i and 2i+1 are a pair");
-  if (!dev_pes) return fail(ctx, BWAGPU_E_INVAL, "NULL pes");
-  if (const char* why = align2_opt_unsupported(ctx->opt)) return fail(ctx, BWAGPU_E_UNSUPPORTED, why);
-  if (b->n_reads == 0) return BWAGPU_OK;
-  if (!b->seq_off || !b->seq || b->seq_bytes < 0 || !dev_reg_off || !dev_regs || !dev_n || !dev_out_off ||
-      !dev_out_regs || !dev_out_n || !dev_status || !dev_n_sw)
-    return fail(ctx, BWAGPU_E_INVAL, "NULL array");
-  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
-  hipStream_t st = (hipStream_t)stream;
-  if (!st) HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
-  bwagpu_pestat_t hp[4];  // the windows' size bound needs the ranges here
-  HIPC(hipMemcpyAsync(hp, dev_pes, sizeof(hp), hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipStreamSynchronize(st), "sync");
-  const char* why = "";
-  if (int rc = pes_check(hp, &why)) return fail(ctx, rc, why);
-  RescueRun run;
-  int rc = enqueue_rescue(ctx, *popt, dev_pes, b->n_reads, b->seq_bytes, b->seq_off, b->seq, dev_reg_off, dev_regs,
-                          dev_n, dev_out_off, dev_out_regs, dev_out_n, dev_status, dev_n_sw, st, &run);
-  if (rc) return rc;
-  Slot& s0 = ctx->slot[0];
-  s0.last = bwagpu_stats_t{};
-  s0.last.ext_calls = run.tasks;
-  s0.last.rows = run.rounds;
-  return BWAGPU_OK;
-}
-
-extern "C" int bwagpu_mate_rescue(bwagpu_ctx_t* ctx, const bwagpu_pairopt_t* popt, const bwagpu_pestat_t* pes,
-                                  int32_t n_reads, const int64_t* seq_off, const uint8_t* seq, const int64_t* reg_off,
-                                  const bwagpu_alnreg_t* regs, const int32_t* n, const int64_t* out_off,
-                                  bwagpu_alnreg_t* out_regs, int32_t* out_n, int32_t* status, int32_t* n_sw) {
-  if (!ctx) return BWAGPU_E_INVAL;
-  RescuePlan plan;
-  const char* why = "";
-  int rc = rescue_check(popt, pes, n_reads, seq_off, seq, reg_off, regs, n, out_off, out_regs, out_n, status, n_sw,
-                        &plan, &why);
-  if (rc) return fail(ctx, rc, why);
-  if (const char* w = align2_opt_unsupported(ctx->opt)) return fail(ctx, BWAGPU_E_UNSUPPORTED, w);
-  if (n_reads == 0) return BWAGPU_OK;
-  const size_t nr = (size_t)n_reads, np = nr / 2;
-  const size_t span = (size_t)(plan.hi - plan.lo), ospan = (size_t)(plan.out_hi - plan.out_lo),
-               nseq = (size_t)(plan.seq_hi - plan.seq_lo);
-  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
-  hipStream_t st = nullptr;
-  HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
-  HIPC(ctx->rs_in.ensure(sizeof(bwagpu_alnreg_t) * std::max<size_t>(span, 1)), "hipMalloc");
-  HIPC(ctx->rs_out.ensure(sizeof(bwagpu_alnreg_t) * std::max<size_t>(ospan, 1)), "hipMalloc");
-  HIPC(ctx->rs_seq.ensure(nseq + 1), "hipMalloc");
-  HIPC(ctx->rs_seqoff.ensure(sizeof(int64_t) * (nr + 1)), "hipMalloc");
-  HIPC(ctx->rs_roff.ensure(sizeof(int64_t) * nr), "hipMalloc");
-  HIPC(ctx->rs_ooff.ensure(sizeof(int64_t) * (nr + 1)), "hipMalloc");
-  HIPC(ctx->rs_n.ensure(sizeof(int32_t) * nr), "hipMalloc");
-  HIPC(ctx->rs_outn.ensure(sizeof(int32_t) * nr), "hipMalloc");
-  HIPC(ctx->rs_status.ensure(sizeof(int32_t) * np), "hipMalloc");
-  HIPC(ctx->rs_nsw.ensure(sizeof(int32_t) * np), "hipMalloc");
-  HIPC(ctx->pe_pes.ensure(sizeof(bwagpu_pestat_t) * 4), "hipMalloc");
-  // offsets relative to what is copied
-  std::vector<int64_t> soff(nr + 1), roff(nr), ooff(nr + 1);
-  for (size_t r = 0; r <= nr; ++r) soff[r] = seq_off[r] - plan.seq_lo, ooff[r] = out_off[r] - plan.out_lo;
-  for (size_t r = 0; r < nr; ++r) roff[r] = n[r] ? reg_off[r] - plan.lo : 0;
-  if (span) HIPC(hipMemcpyAsync(ctx->rs_in.p, regs + plan.lo, sizeof(bwagpu_alnreg_t) * span, hipMemcpyHostToDevice, st), "H2D");
-  if (nseq) HIPC(hipMemcpyAsync(ctx->rs_seq.p, seq + plan.seq_lo, nseq, hipMemcpyHostToDevice, st), "H2D");
-  HIPC(hipMemcpyAsync(ctx->rs_seqoff.p, soff.data(), sizeof(int64_t) * (nr + 1), hipMemcpyHostToDevice, st), "H2D");
-  HIPC(hipMemcpyAsync(ctx->rs_roff.p, roff.data(), sizeof(int64_t) * nr, hipMemcpyHostToDevice, st), "H2D");
-  HIPC(hipMemcpyAsync(ctx->rs_ooff.p, ooff.data(), sizeof(int64_t) * (nr + 1), hipMemcpyHostToDevice, st), "H2D");
-  HIPC(hipMemcpyAsync(ctx->rs_n.p, n, sizeof(int32_t) * nr, hipMemcpyHostToDevice, st), "H2D");
-  HIPC(hipMemcpyAsync(ctx->pe_pes.p, pes, sizeof(bwagpu_pestat_t) * 4, hipMemcpyHostToDevice, st), "H2D");
-  HIPC(hipStreamSynchronize(st), "H2D");  // the offset vectors are pageable locals
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  HIPC(hipEventCreate(&e0), "event");
-  HIPC(hipEventCreate(&e1), "event");
-  HIPC(hipEventRecord(e0, st), "event");
-  RescueRun run;
-  rc = enqueue_rescue(ctx, *popt, ctx->pe_pes.as<bwagpu_pestat_t>(), n_reads, (int64_t)nseq, ctx->rs_seqoff.as<int64_t>(),
-                      ctx->rs_seq.as<uint8_t>(), ctx->rs_roff.as<int64_t>(), ctx->rs_in.as<bwagpu_alnreg_t>(),
-                      ctx->rs_n.as<int32_t>(), ctx->rs_ooff.as<int64_t>(), ctx->rs_out.as<bwagpu_alnreg_t>(),
-                      ctx->rs_outn.as<int32_t>(), ctx->rs_status.as<int32_t>(), ctx->rs_nsw.as<int32_t>(), st, &run);
-  if (rc) {
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return rc;
-  }
-  HIPC(hipEventRecord(e1, st), "event");
-  int32_t hctr[RC_WORDS] = {};
-  // only the regions of every span that the pass wrote: spans are copied back whole
-  if (ospan)
-    HIPC(hipMemcpyAsync(out_regs + plan.out_lo, ctx->rs_out.p, sizeof(bwagpu_alnreg_t) * ospan, hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipMemcpyAsync(out_n, ctx->rs_outn.p, sizeof(int32_t) * nr, hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipMemcpyAsync(status, ctx->rs_status.p, sizeof(int32_t) * np, hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipMemcpyAsync(n_sw, ctx->rs_nsw.p, sizeof(int32_t) * np, hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipMemcpyAsync(hctr, ctx->rs_ctr.p, sizeof(hctr), hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipStreamSynchronize(st), "mate rescue execution");
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  Slot& s0 = ctx->slot[0];
-  s0.last = bwagpu_stats_t{};
-  s0.last.kernel_ms = ms;
-  s0.last.ext_calls = run.tasks;
-  s0.last.rows = run.rounds;
-  s0.last.cells = hctr[RC_USED];
-  s0.last.h2d_bytes = (int64_t)(sizeof(bwagpu_alnreg_t) * span + nseq + sizeof(int64_t) * (3 * nr + 2) + sizeof(int32_t) * nr);
-  s0.last.d2h_bytes = (int64_t)(sizeof(bwagpu_alnreg_t) * ospan + sizeof(int32_t) * (nr + 2 * np));
-  return BWAGPU_OK;
-}
-
-// ------------------------------------------------------------------ paired ends: primary marking, pair selection
-namespace {
-
-int sel_tmp(const bwagpu_ctx_t* ctx) {  // bwamem.c:505-507
-  int tmp = ctx->opt.a + ctx->opt_b;
-  tmp = std::max(tmp, ctx->opt.o_del + ctx->opt.e_del);
-  return std::max(tmp, ctx->opt.o_ins + ctx->opt.e_ins);
-}
-
-int enqueue_mark(bwagpu_ctx_t* ctx, const bwagpu_selopt_t& so, int64_t id0, int32_t n_reads, const int64_t* reg_off,
-                 bwagpu_alnreg_t* regs, const int32_t* n, int32_t* n_pri, int32_t* status, hipStream_t st) {
-  HIPC(ctx->ps_scratch.ensure(sizeof(bwagpu_alnreg_t) * (size_t)kSelCap * kSelMaxBlocks), "hipMalloc");
-  MarkArgs a{};
-  a.n_reads = n_reads;
-  a.tmp = sel_tmp(ctx);
-  a.mask_level = so.mask_level;
-  a.id0 = id0;
-  a.reg_off = reg_off;
-  a.regs = regs;
-  a.n = n;
-  a.n_pri = n_pri;
-  a.status = status;
-  a.scratch = ctx->ps_scratch.as<bwagpu_alnreg_t>();
-  HIPC(launch_mark_primary(a, st), "mark_primary launch");
-  return BWAGPU_OK;
-}
-
-// hpes: the four records on the host.  The tables go to the device before the
-// launch (the call waits for the copies: their sources are pageable).
-int enqueue_pairsel(bwagpu_ctx_t* ctx, const bwagpu_selopt_t& so, const bwagpu_pestat_t* hpes, int64_t pair_id0,
-                    int32_t n_reads, const int64_t* reg_off, bwagpu_alnreg_t* regs, const int32_t* n,
-                    const int32_t* n_pri, const int32_t* in_status, bwagpu_pairsel_t* sel, int32_t* out_mapq,
-                    hipStream_t st) {
-  if (!ctx->ps_log_ready) {
-    std::vector<double> lg((size_t)kSelLogN);
-    fill_log_table(lg.data(), kSelLogN);
-    HIPC(ctx->ps_log.ensure(sizeof(double) * (size_t)kSelLogN), "hipMalloc");
-    HIPC(hipMemcpyAsync(ctx->ps_log.p, lg.data(), sizeof(double) * (size_t)kSelLogN, hipMemcpyHostToDevice, st), "H2D");
-    HIPC(hipStreamSynchronize(st), "H2D");
-    ctx->ps_log_ready = true;
-  }
-  int64_t len[4], total = 0;
-  for (int r = 0; r < 4; ++r) total += len[r] = erfc_table_len(hpes[r]);
-  std::vector<double> tab((size_t)std::max<int64_t>(total, 1));
-  HIPC(ctx->ps_erfc.ensure(sizeof(double) * tab.size()), "hipMalloc");
-  PairSelArgs a{};
-  int64_t at = 0;
-  for (int r = 0; r < 4; ++r) {
-    a.pes[r] = hpes[r];
-    a.erfc_tab[r] = ctx->ps_erfc.as<double>() + at;
-    if (len[r]) fill_erfc_table(hpes[r], tab.data() + at);
-    at += len[r];
-  }
-  if (total) {
-    HIPC(hipMemcpyAsync(ctx->ps_erfc.p, tab.data(), sizeof(double) * (size_t)total, hipMemcpyHostToDevice, st), "H2D");
-    HIPC(hipStreamSynchronize(st), "H2D");
-  }
-  a.n_pairs = n_reads >> 1;
-  a.a = ctx->opt.a;
-  a.b = ctx->opt_b;
-  a.tmp = sel_tmp(ctx);
-  a.so = so;
-  a.pair_id0 = pair_id0;
-  a.log_tab = ctx->ps_log.as<double>();
-  a.log_n = kSelLogN;
-  a.reg_off = reg_off;
-  a.regs = regs;
-  a.n = n;
-  a.n_pri = n_pri;
-  a.in_status = in_status;
-  a.sel = sel;
-  a.out_mapq = out_mapq;
-  HIPC(launch_pair_select(ctx->ref, a, st), "pair_select launch");
-  return BWAGPU_OK;
-}
-
-}  // namespace
-
-extern "C" int bwagpu_mark_primary_device(bwagpu_ctx_t* ctx, const bwagpu_selopt_t* sopt, int64_t id0, int32_t n_reads,
-                                          const int64_t* dev_reg_off, bwagpu_alnreg_t* dev_regs, const int32_t* dev_n,
-                                          int32_t* dev_n_pri, int32_t* dev_status, void* stream) {
-  if (!ctx) return BWAGPU_E_INVAL;
-  if (!sel_opt_ok(sopt)) return fail(ctx, BWAGPU_E_INVAL, "bad bwagpu_selopt_t");
-  if (n_reads < 0) return fail(ctx, BWAGPU_E_INVAL, "negative read count");
-  if (n_reads == 0) return BWAGPU_OK;
-  if (!dev_reg_off || !dev_regs || !dev_n || !dev_n_pri || !dev_status) return fail(ctx, BWAGPU_E_INVAL, "NULL array");
-  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
-  hipStream_t st = (hipStream_t)stream;
-  if (!st) HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
-  return enqueue_mark(ctx, *sopt, id0, n_reads, dev_reg_off, dev_regs, dev_n, dev_n_pri, dev_status, st);
-}
-
-extern "C" int bwagpu_mark_primary(bwagpu_ctx_t* ctx, const bwagpu_selopt_t* sopt, int64_t id0, int32_t n_reads,
-                                   const int64_t* reg_off, bwagpu_alnreg_t* regs, const int32_t* n, int32_t* n_pri,
-                                   int32_t* status) {
-  if (!ctx) return BWAGPU_E_INVAL;
-  SelPlan plan;
-  const char* why = "";
-  int rc = mark_check(sopt, n_reads, reg_off, regs, n, n_pri, status, &plan, &why);
-  if (rc) return fail(ctx, rc, why);
-  if (n_reads == 0) return BWAGPU_OK;
-  const size_t nr = (size_t)n_reads, span = (size_t)(plan.hi - plan.lo);
-  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
-  hipStream_t st = nullptr;
-  HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
-  HIPC(ctx->ps_regs.ensure(sizeof(bwagpu_alnreg_t) * std::max<size_t>(span, 1)), "hipMalloc");
-  HIPC(ctx->ps_roff.ensure(sizeof(int64_t) * nr), "hipMalloc");
-  HIPC(ctx->ps_n.ensure(sizeof(int32_t) * nr), "hipMalloc");
-  HIPC(ctx->ps_npri.ensure(sizeof(int32_t) * nr), "hipMalloc");
-  HIPC(ctx->ps_status.ensure(sizeof(int32_t) * nr), "hipMalloc");
-  std::vector<int64_t> roff(nr);
-  for (size_t r = 0; r < nr; ++r) roff[r] = n[r] ? reg_off[r] - plan.lo : 0;
-  if (span) HIPC(hipMemcpyAsync(ctx->ps_regs.p, regs + plan.lo, sizeof(bwagpu_alnreg_t) * span, hipMemcpyHostToDevice, st), "H2D");
-  HIPC(hipMemcpyAsync(ctx->ps_roff.p, roff.data(), sizeof(int64_t) * nr, hipMemcpyHostToDevice, st), "H2D");
-  HIPC(hipMemcpyAsync(ctx->ps_n.p, n, sizeof(int32_t) * nr, hipMemcpyHostToDevice, st), "H2D");
-  HIPC(hipStreamSynchronize(st), "H2D");  // roff is a pageable local
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  HIPC(hipEventCreate(&e0), "event");
-  HIPC(hipEventCreate(&e1), "event");
-  HIPC(hipEventRecord(e0, st), "event");
-  rc = enqueue_mark(ctx, *sopt, id0, n_reads, ctx->ps_roff.as<int64_t>(), ctx->ps_regs.as<bwagpu_alnreg_t>(),
-                    ctx->ps_n.as<int32_t>(), ctx->ps_npri.as<int32_t>(), ctx->ps_status.as<int32_t>(), st);
-  if (rc) {
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return rc;
-  }
-  HIPC(hipEventRecord(e1, st), "event");
-  if (span) HIPC(hipMemcpyAsync(regs + plan.lo, ctx->ps_regs.p, sizeof(bwagpu_alnreg_t) * span, hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipMemcpyAsync(n_pri, ctx->ps_npri.p, sizeof(int32_t) * nr, hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipMemcpyAsync(status, ctx->ps_status.p, sizeof(int32_t) * nr, hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipStreamSynchronize(st), "mark_primary execution");
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  Slot& s0 = ctx->slot[0];
-  s0.last = bwagpu_stats_t{};
-  s0.last.kernel_ms = ms;
-  s0.last.h2d_bytes = (int64_t)(sizeof(bwagpu_alnreg_t) * span + sizeof(int64_t) * nr + sizeof(int32_t) * nr);
-  s0.last.d2h_bytes = (int64_t)(sizeof(bwagpu_alnreg_t) * span + sizeof(int32_t) * 2 * nr);
-  return BWAGPU_OK;
-}
-
-extern "C" int bwagpu_pair_select_device(bwagpu_ctx_t* ctx, const bwagpu_selopt_t* sopt, const bwagpu_pestat_t* dev_pes,
-                                         int64_t pair_id0, int32_t n_reads, const int64_t* dev_reg_off,
-                                         bwagpu_alnreg_t* dev_regs, const int32_t* dev_n, const int32_t* dev_n_pri,
-                                         const int32_t* dev_in_status, bwagpu_pairsel_t* dev_sel,
-                                         int32_t* dev_out_mapq, void* stream) {
-  if (!ctx) return BWAGPU_E_INVAL;
-  if (!sel_opt_ok(sopt)) return fail(ctx, BWAGPU_E_INVAL, "bad bwagpu_selopt_t");
-  if (sopt->flags & kSelRefused)
-    return fail(ctx, BWAGPU_E_UNSUPPORTED,
-                "MEM_F_ALL, MEM_F_NO_MULTI, MEM_F_PRIMARY5 and MEM_F_KEEP_SUPP_MAPQ are not implemented");
-  if (n_reads < 0) return fail(ctx, BWAGPU_E_INVAL, "negative read count");
-  if (n_reads & 1) return fail(ctx, BWAGPU_E_INVAL, "odd read count: reads 2i and 2i+1 are a pair");
-  if (!dev_pes) return fail(ctx, BWAGPU_E_INVAL, "NULL pes");
-  if (n_reads == 0) return BWAGPU_OK;
-  if (!dev_reg_off || !dev_regs || !dev_n || !dev_n_pri || !dev_sel || !dev_out_mapq)
-    return fail(ctx, BWAGPU_E_INVAL, "NULL array");
-  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
-  hipStream_t st = (hipStream_t)stream;
-  if (!st) HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
-  bwagpu_pestat_t hp[4];  // the pairing tables are made from the ranges here
-  HIPC(hipMemcpyAsync(hp, dev_pes, sizeof(hp), hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipStreamSynchronize(st), "sync");
-  const char* why = "";
-  if (int rc = pes_check(hp, &why)) return fail(ctx, rc, why);
-  return enqueue_pairsel(ctx, *sopt, hp, pair_id0, n_reads, dev_reg_off, dev_regs, dev_n, dev_n_pri, dev_in_status,
-                         dev_sel, dev_out_mapq, st);
-}
-
-extern "C" int bwagpu_pair_select(bwagpu_ctx_t* ctx, const bwagpu_selopt_t* sopt, const bwagpu_pestat_t* pes,
-                                  int64_t pair_id0, int32_t n_reads, const int64_t* reg_off, bwagpu_alnreg_t* regs,
-                                  const int32_t* n, const int32_t* n_pri, const int32_t* in_status,
-                                  bwagpu_pairsel_t* sel, int32_t* out_mapq) {
-  if (!ctx) return BWAGPU_E_INVAL;
-  SelPlan plan;
-  const char* why = "";
-  int rc = pairsel_check(sopt, pes, n_reads, reg_off, regs, n, n_pri, sel, out_mapq, ctx->ref.n_seqs, &plan, &why);
-  if (rc) return fail(ctx, rc, why);
-  if (n_reads == 0) return BWAGPU_OK;
-  const size_t nr = (size_t)n_reads, np = nr / 2, span = (size_t)(plan.hi - plan.lo);
-  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
-  hipStream_t st = nullptr;
-  HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
-  HIPC(ctx->ps_regs.ensure(sizeof(bwagpu_alnreg_t) * std::max<size_t>(span, 1)), "hipMalloc");
-  HIPC(ctx->ps_mapq.ensure(sizeof(int32_t) * std::max<size_t>(span, 1)), "hipMalloc");
-  HIPC(ctx->ps_roff.ensure(sizeof(int64_t) * nr), "hipMalloc");
-  HIPC(ctx->ps_n.ensure(sizeof(int32_t) * nr), "hipMalloc");
-  HIPC(ctx->ps_npri.ensure(sizeof(int32_t) * nr), "hipMalloc");
-  HIPC(ctx->ps_instat.ensure(sizeof(int32_t) * np), "hipMalloc");
-  HIPC(ctx->ps_sel.ensure(sizeof(bwagpu_pairsel_t) * np), "hipMalloc");
-  std::vector<int64_t> roff(nr);
-  for (size_t r = 0; r < nr; ++r) roff[r] = n[r] ? reg_off[r] - plan.lo : 0;
-  if (span) {
-    HIPC(hipMemcpyAsync(ctx->ps_regs.p, regs + plan.lo, sizeof(bwagpu_alnreg_t) * span, hipMemcpyHostToDevice, st), "H2D");
-    // regions between the spans keep the caller's out_mapq
-    HIPC(hipMemcpyAsync(ctx->ps_mapq.p, out_mapq + plan.lo, sizeof(int32_t) * span, hipMemcpyHostToDevice, st), "H2D");
-  }
-  HIPC(hipMemcpyAsync(ctx->ps_roff.p, roff.data(), sizeof(int64_t) * nr, hipMemcpyHostToDevice, st), "H2D");
-  HIPC(hipMemcpyAsync(ctx->ps_n.p, n, sizeof(int32_t) * nr, hipMemcpyHostToDevice, st), "H2D");
-  HIPC(hipMemcpyAsync(ctx->ps_npri.p, n_pri, sizeof(int32_t) * nr, hipMemcpyHostToDevice, st), "H2D");
-  if (in_status) HIPC(hipMemcpyAsync(ctx->ps_instat.p, in_status, sizeof(int32_t) * np, hipMemcpyHostToDevice, st), "H2D");
-  HIPC(hipStreamSynchronize(st), "H2D");  // roff is a pageable local
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  HIPC(hipEventCreate(&e0), "event");
-  HIPC(hipEventCreate(&e1), "event");
-  HIPC(hipEventRecord(e0, st), "event");
-  rc = enqueue_pairsel(ctx, *sopt, pes, pair_id0, n_reads, ctx->ps_roff.as<int64_t>(), ctx->ps_regs.as<bwagpu_alnreg_t>(),
-                       ctx->ps_n.as<int32_t>(), ctx->ps_npri.as<int32_t>(),
-                       in_status ? ctx->ps_instat.as<int32_t>() : nullptr, ctx->ps_sel.as<bwagpu_pairsel_t>(),
-                       ctx->ps_mapq.as<int32_t>(), st);
-  if (rc) {
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return rc;
-  }
-  HIPC(hipEventRecord(e1, st), "event");
-  if (span) {
-    HIPC(hipMemcpyAsync(regs + plan.lo, ctx->ps_regs.p, sizeof(bwagpu_alnreg_t) * span, hipMemcpyDeviceToHost, st), "D2H");
-    HIPC(hipMemcpyAsync(out_mapq + plan.lo, ctx->ps_mapq.p, sizeof(int32_t) * span, hipMemcpyDeviceToHost, st), "D2H");
-  }
-  HIPC(hipMemcpyAsync(sel, ctx->ps_sel.p, sizeof(bwagpu_pairsel_t) * np, hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipStreamSynchronize(st), "pair_select execution");
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  Slot& s0 = ctx->slot[0];
-  s0.last = bwagpu_stats_t{};
-  s0.last.kernel_ms = ms;
-  s0.last.h2d_bytes = (int64_t)((sizeof(bwagpu_alnreg_t) + sizeof(int32_t)) * span + sizeof(int64_t) * nr + sizeof(int32_t) * (2 * nr + np));
-  s0.last.d2h_bytes = (int64_t)((sizeof(bwagpu_alnreg_t) + sizeof(int32_t)) * span + sizeof(bwagpu_pairsel_t) * np);
   return BWAGPU_OK;
 }

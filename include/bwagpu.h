@@ -587,7 +587,11 @@ typedef struct {
    i (a trailing odd read is ignored, as n >> 1 does), read r's n[r] regions at
    regs[reg_off[r] ..) as bwagpu_regs_post leaves them.  pes[4] equals the
    reference's bit for bit, the doubles included.  Host buffers; blocking.
-   Negative counts return BWAGPU_E_INVAL before any launch. */
+   Negative counts return BWAGPU_E_INVAL before any launch.
+   bwagpu_last_stats(ctx, 0): kernel_ms of the pass; h2d_bytes counts the
+   caller's arrays that were moved, as for the other host-buffer entries (the
+   regions from the first to the last span, reg_off and n of the reads in
+   pairs); d2h_bytes is 0, the four fixed-size records are not counted. */
 int bwagpu_pestat(bwagpu_ctx_t *ctx, const bwagpu_pairopt_t *popt, int32_t n_reads, const int64_t *reg_off,
                   const bwagpu_alnreg_t *regs, const int32_t *n, bwagpu_pestat_t *pes);
 /* The same on device memory, asynchronous on stream (hipStream_t, NULL = the
@@ -740,7 +744,8 @@ typedef struct {
    outside the reference, overlapping spans and NULLs return BWAGPU_E_INVAL;
    the refused flags and a live orientation with high - low over 2^20 return
    BWAGPU_E_UNSUPPORTED.  Host buffers; blocking.  bwagpu_last_stats(ctx, 0):
-   kernel_ms of the pass. */
+   kernel_ms of the pass; h2d_bytes / d2h_bytes count the caller's arrays that
+   were moved, so the n_reads/2 words of in_status only when it is not NULL. */
 int bwagpu_pair_select(bwagpu_ctx_t *ctx, const bwagpu_selopt_t *sopt, const bwagpu_pestat_t *pes, int64_t pair_id0,
                        int32_t n_reads, const int64_t *reg_off, bwagpu_alnreg_t *regs, const int32_t *n,
                        const int32_t *n_pri, const int32_t *in_status, bwagpu_pairsel_t *sel, int32_t *out_mapq);

@@ -1,6 +1,6 @@
 // pairsel_host_asan.cpp — the host-side argument validation, span arithmetic
 // and tables of bwagpu_mark_primary and bwagpu_pair_select
-// (bwa-flow_amd/csrc/pairsel_host.h) under the host sanitizers.  Stand-alone:
+// (bwa-flow_amd/csrc/stage_host.h) under the host sanitizers.  Stand-alone:
 // no GPU, no HIP, not loaded into any other process.
 //
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
@@ -17,7 +17,7 @@
 #include <limits>
 #include <vector>
 
-#include "pairsel_host.h"
+#include "stage_host.h"
 
 using namespace bwagpu;
 
@@ -39,7 +39,7 @@ struct Case {
   bwagpu_selopt_t so = dflt();
   bwagpu_pestat_t pes[4] = {{0, 0, 1, 0, 0., 0.}, {200, 600, 0, 0, 400., 50.}, {0, 0, 1, 0, 0., 0.}, {0, 0, 1, 0, 0., 0.}};
   int32_t n_seqs = 3;
-  SelPlan plan;
+  StagePlan plan;
   const char* why = nullptr;
   template <class V>
   static typename V::value_type* dup(const V& v) {  // exact-size copies: a vector's capacity may exceed its size
@@ -98,7 +98,7 @@ int main() {
   {  // an empty batch reads nothing at all
     bwagpu_selopt_t so = dflt();
     Case c = base();
-    SelPlan plan;
+    StagePlan plan;
     const char* why = nullptr;
     EXPECT(mark_check(&so, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &plan, &why) == BWAGPU_OK);
     EXPECT(mark_check(nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &plan, &why) == BWAGPU_E_INVAL);
@@ -143,6 +143,17 @@ int main() {
     EXPECT(c.run_mark() == BWAGPU_E_INVAL && c.run_sel() == BWAGPU_E_INVAL);
     c.reg_off[3] = 0;  // regs[0..1): touches read 2's span, does not overlap it
     EXPECT(c.run_mark() == BWAGPU_OK && c.plan.lo == 0 && c.plan.hi == 7);
+  }
+  {  // two spans that touch (off[a] + n[a] == off[b]) do not overlap: every span of this layout touches the next
+    Case c = base();
+    c.reg_off = {5, 0, 0, 3};  // read 2 at regs[0..3), read 3 at regs[3..4), read 0 at regs[5..7)
+    EXPECT(c.run_mark() == BWAGPU_OK && c.plan.lo == 0 && c.plan.hi == 7 && c.plan.n_regs == 6);
+    EXPECT(c.run_sel() == BWAGPU_OK && c.plan.lo == 0 && c.plan.hi == 7 && c.plan.n_regs == 6);
+    c.reg_off = {4, 0, 0, 3};  // ... and read 0 at regs[4..6)
+    EXPECT(c.run_mark() == BWAGPU_OK && c.plan.lo == 0 && c.plan.hi == 6);
+    EXPECT(c.run_sel() == BWAGPU_OK && c.plan.lo == 0 && c.plan.hi == 6);
+    c.reg_off = {3, 0, 0, 3};  // read 0 and read 3 start at the same record
+    EXPECT(c.run_mark() == BWAGPU_E_INVAL && c.run_sel() == BWAGPU_E_INVAL);
   }
   {  // n_pri and rid
     Case c = base();

@@ -1,5 +1,5 @@
 // post_host_asan.cpp — the host-side argument validation and span arithmetic
-// of bwagpu_regs_post (bwa-flow_amd/csrc/regpost_host.h) under the host
+// of bwagpu_regs_post (bwa-flow_amd/csrc/stage_host.h) under the host
 // sanitizers.  Stand-alone: no GPU, no HIP, not loaded into any other process.
 //
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
@@ -14,7 +14,7 @@
 #include <limits>
 #include <vector>
 
-#include "regpost_host.h"
+#include "stage_host.h"
 
 using namespace bwagpu;
 
@@ -34,7 +34,7 @@ struct Case {
   std::vector<int32_t> n;
   bwagpu_postopt_t po{10000, 0.95f, 0.50f, 0};
   int32_t flags = 3;
-  PostPlan plan;
+  StagePlan plan;
   const char* why = nullptr;
   int run() {
     // exact-size copies: the vectors' capacity may exceed their size
@@ -91,7 +91,7 @@ int main() {
   }
   {  // an empty batch reads nothing at all
     bwagpu_postopt_t po{10000, 0.95f, 0.50f, 0};
-    PostPlan plan;
+    StagePlan plan;
     const char* why = nullptr;
     EXPECT(post_check(&po, 3, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &plan, &why) == BWAGPU_OK);
     EXPECT(plan.n_regs == 0 && plan.hi == 0);
@@ -163,6 +163,26 @@ int main() {
     EXPECT(c.run() == BWAGPU_OK);
     c.regs[0].qe = 5000;  // regs[0] belongs to no span: never looked at
     EXPECT(c.run() == BWAGPU_OK);
+  }
+  {  // the order of verdicts: overlapping spans, then the length limit, then qb / qe
+    Case c = base();
+    c.seq_off = {0, 100, 200, 201 + BWAGPU_MAX_READ_LEN};  // read 2 is one base over the limit
+    c.seq.assign((size_t)c.seq_off[3], 0);
+    c.reg_off = {3, 0, 1};  // read 0's span starts inside read 2's
+    EXPECT(c.run() == BWAGPU_E_INVAL && !std::strcmp(c.why, "region spans overlap"));
+    EXPECT(c.plan.n_regs == 0 && c.plan.hi == 0 && c.plan.seq_hi == 0);  // a refused call has no plan
+    c.reg_off = {5, 0, 1};
+    c.regs[5].qe = 101;  // read 0 has 100 bases
+    EXPECT(c.run() == BWAGPU_E_UNSUPPORTED && !std::strcmp(c.why, "read longer than BWAGPU_MAX_READ_LEN"));
+    c.seq_off[3] -= 1;
+    EXPECT(c.run() == BWAGPU_E_INVAL && !std::strcmp(c.why, "a region's qb/qe lie outside its read"));
+  }
+  {  // two spans that touch (off[a] + n[a] == off[b]) do not overlap
+    Case c = base();
+    c.reg_off = {4, 0, 1};  // read 2 at regs[1..4), read 0 at regs[4..6)
+    EXPECT(c.run() == BWAGPU_OK && c.plan.lo == 1 && c.plan.hi == 6 && c.plan.n_regs == 5);
+    c.reg_off = {0, 0, 2};  // read 0 at regs[0..2), read 2 at regs[2..5)
+    EXPECT(c.run() == BWAGPU_OK && c.plan.lo == 0 && c.plan.hi == 5);
   }
   {  // options
     Case c = base();

@@ -1,5 +1,5 @@
 // rescue_host_asan.cpp — the host-side argument validation and span arithmetic
-// of bwagpu_pestat and bwagpu_mate_rescue (bwa-flow_amd/csrc/rescue_host.h)
+// of bwagpu_pestat and bwagpu_mate_rescue (bwa-flow_amd/csrc/stage_host.h)
 // under the host sanitizers.  Stand-alone: no GPU, no HIP, not loaded into any
 // other process.
 //
@@ -16,7 +16,7 @@
 #include <limits>
 #include <vector>
 
-#include "rescue_host.h"
+#include "stage_host.h"
 
 using namespace bwagpu;
 
@@ -38,7 +38,7 @@ struct Case {
   std::vector<int32_t> n;
   bwagpu_pairopt_t po = dflt();
   bwagpu_pestat_t pes[4] = {{0, 0, 1, 0, 0., 0.}, {200, 600, 0, 0, 400., 50.}, {0, 0, 1, 0, 0., 0.}, {0, 0, 1, 0, 0., 0.}};
-  RescuePlan plan;
+  StagePlan plan;
   const char* why = nullptr;
   template <class V>
   static typename V::value_type* dup(const V& v) {  // exact-size copies: a vector's capacity may exceed its size
@@ -102,7 +102,7 @@ int main() {
   {  // an empty batch reads nothing at all
     bwagpu_pairopt_t po = dflt();
     Case c = base();
-    RescuePlan plan;
+    StagePlan plan;
     const char* why = nullptr;
     bwagpu_pestat_t out[4];
     EXPECT(rescue_check(&po, c.pes, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
@@ -155,6 +155,20 @@ int main() {
     c.reg_off[0] = -1;
     EXPECT(c.run() == BWAGPU_E_INVAL);
     EXPECT(c.run_pestat(4) == BWAGPU_E_INVAL);
+  }
+  {  // overlapping input spans are legal here: neither pass writes its input (spans_check, disjoint = false)
+    Case c = base();
+    c.reg_off = {3, 0, 1, 4};  // read 0 at regs[3..5), inside read 2's regs[1..4) and over read 3's regs[4..5)
+    EXPECT(c.run() == BWAGPU_OK && c.plan.lo == 1 && c.plan.hi == 5 && c.plan.n_regs == 6);
+    EXPECT(c.run_pestat(4) == BWAGPU_OK && c.plan.lo == 1 && c.plan.hi == 5 && c.plan.n_regs == 6);
+    c.reg_off = {1, 0, 1, 1};  // three spans from the same record on
+    EXPECT(c.run() == BWAGPU_OK && c.plan.lo == 1 && c.plan.hi == 4);
+    StagePlan p;
+    const char* why = "";
+    int64_t off[2] = {0, 1};
+    int32_t n[2] = {3, 2};
+    EXPECT(spans_check(2, off, c.regs.data(), n, false, &p, &why) == BWAGPU_OK && p.lo == 0 && p.hi == 3);
+    EXPECT(spans_check(2, off, c.regs.data(), n, true, &p, &why) == BWAGPU_E_INVAL && !std::strcmp(why, "region spans overlap"));
   }
   {  // reads: descending offsets, a negative start, a base over 4
     Case c = base();

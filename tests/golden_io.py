@@ -31,6 +31,18 @@ def opt_of(z) -> dict:
     return o
 
 
+def offsets(n):
+    """where each read's span starts when the spans lie back to back: int64 off[r] = n[0] + ... + n[r-1]"""
+    n = np.asarray(n, np.int64)
+    return (np.cumsum(n) - n).astype(np.int64)
+
+
+def dense(regs, off, n):
+    """the first n[r] regions of every span, back to back in read order"""
+    parts = [regs[o:o + k] for o, k in zip(off, n)]
+    return np.concatenate(parts) if parts else regs[:0]
+
+
 def load_chain_set(name):
     """-> opt, Batch, expected regions (read order, compact), expected per-read counts"""
     z = _npz(name)

@@ -35,7 +35,7 @@ class PairData:
 
     def __init__(self, name, z, pre, regs, pes, opt, genome, genome_id, alt):
         self.name, self.opt, self.genome, self.genome_id, self.alt = name, opt, genome, genome_id, alt
-        self._sel = (z["selopt_int"].copy(), z["selopt_f"].copy())
+        self._sel = dict(selopt_int=z["selopt_int"].copy(), selopt_f=z["selopt_f"].copy())
         self.pair_id0 = int(z["pair_id0"][0])
         self.pes = pes.astype(abi.PESTAT_DTYPE)
         self.n = z[pre + "n"].astype(np.int32)
@@ -52,8 +52,7 @@ class PairData:
         return len(self.n)
 
     def selopt(self, flags=0) -> abi.SelOpt:
-        i, f = self._sel
-        return abi.SelOpt(int(i[0]), int(i[1]), int(i[2]), float(f[0]), int(i[3]), float(f[1]), float(f[2]), int(flags))
+        return selopt_of(self._sel, flags)
 
 
 @functools.lru_cache(maxsize=None)

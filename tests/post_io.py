@@ -10,6 +10,7 @@ import numpy as np
 import golden_io as G
 from bwagpu import abi
 from bwagpu.engine import Batch
+from golden_io import dense  # noqa: F401  (P.dense of the tests)
 
 POST_SETS = ["c1_default", "c5_mixed", "opt1_scoring", "opt2_band", "chain_rep", "rep_redun1", "sv", "c5_refseed"]
 COVERAGE_KEYS = ("reads_lost_to_redundancy", "regs_patched", "regs_patched_rev", "pairs_gated_not_merged",
@@ -33,7 +34,7 @@ class PostSet:
         self.seq_off, self.seq = z["seq_off"], z["seq"]
         self.n = z["reg_n"].astype(np.int32)
         self.regs = z["regs"].astype(abi.ALNREG_DTYPE)
-        self.off = (np.cumsum(self.n, dtype=np.int64) - self.n).astype(np.int64)
+        self.off = G.offsets(self.n)
         # expected results by flags
         self.want = {3: (z["out3_regs"].astype(abi.ALNREG_DTYPE), z["out3_n"].astype(np.int32)),
                      7: (z["out7_regs"].astype(abi.ALNREG_DTYPE), z["out7_n"].astype(np.int32))}
@@ -57,9 +58,3 @@ def genome(kind: int) -> dict:
     from bwagpu import workload
     _, ref, _ = workload.load_fixture(workload.C5_FIXTURE)
     return dict(l_pac=int(ref.l_pac), ann_offset=ref.ann_offset, ann_len=ref.ann_len, pac=ref.pac)
-
-
-def dense(regs, off, n):
-    """the first n[r] regions of every span, back to back in read order"""
-    parts = [regs[o:o + k] for o, k in zip(off, n)]
-    return np.concatenate(parts) if parts else regs[:0]

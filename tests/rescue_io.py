@@ -10,6 +10,7 @@ import numpy as np
 
 import golden_io as G
 from bwagpu import abi
+from golden_io import dense, offsets  # noqa: F401  (R.dense, R.offsets of the tests and the generators)
 
 RESCUE_SETS = ["fr", "mixed", "shift", "ends", "rep", "rep_sw2"]
 COVERAGE_KEYS = ("pairs_sw", "regs_added", "regs_added_rev", "regs_added_to_empty", "sw_no_region", "dedup_removed",
@@ -28,17 +29,12 @@ def pairopt_of(z, max_rounds=3) -> abi.PairOpt:
     return abi.PairOpt(int(i[0]), int(i[1]), int(i[2]), int(i[3]), int(i[4]), float(m[0]), float(m[1]), max_rounds)
 
 
-def offsets(n):
-    n = np.asarray(n, np.int64)
-    return (np.cumsum(n) - n).astype(np.int64)
-
-
 class RescueSet:
     def __init__(self, name):
         z = np.load(os.path.join(G.GOLD, f"rescue_{name}.npz"), allow_pickle=False)
         self.name = name
         self.opt = G.opt_of(z)
-        self._z_pairopt = (z["pairopt_int"].copy(), z["pairopt_mask"].copy())
+        self._z_pairopt = dict(pairopt_int=z["pairopt_int"].copy(), pairopt_mask=z["pairopt_mask"].copy())
         self.genome_id = int(z["genome"][0])  # 0: tests/golden/ref.npz, 2: the set's own genome (g_*)
         if self.genome_id == 0:
             self.genome = G.load_ref()
@@ -62,8 +58,7 @@ class RescueSet:
         return len(self.n)
 
     def pairopt(self, max_rounds=3) -> abi.PairOpt:
-        i, m = self._z_pairopt
-        return abi.PairOpt(int(i[0]), int(i[1]), int(i[2]), int(i[3]), int(i[4]), float(m[0]), float(m[1]), max_rounds)
+        return pairopt_of(self._z_pairopt, max_rounds)
 
     def out_off(self, headroom):
         """output spans of n + headroom regions per read -> int64[n_reads + 1]"""
@@ -82,9 +77,3 @@ def load_cases():
     cases = {str(k): (z[f"{k}_n"].astype(np.int32), z[f"{k}_regs"].astype(abi.ALNREG_DTYPE),
                       z[f"{k}_pes"].astype(abi.PESTAT_DTYPE)) for k in z["names"]}
     return G.opt_of(z), pairopt_of(z), cases
-
-
-def dense(regs, off, n):
-    """the first n[r] regions of every span, back to back in read order"""
-    parts = [regs[o:o + k] for o, k in zip(off, n)]
-    return np.concatenate(parts) if parts else regs[:0]

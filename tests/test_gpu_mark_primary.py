@@ -81,7 +81,7 @@ def test_post_sets_flags3_to_flags7(name):
     so = abi.default_selopt()
     so.mask_level = float(s.popt.mask_level)
     alt = (regs7["n_comp_is_alt"] >> np.uint32(30)) != 0
-    off = (np.cumsum(n3, dtype=np.int64) - n3).astype(np.int64)
+    off = G.offsets(n3)
     want_npri = np.array([int((~alt[o:o + k]).sum()) for o, k in zip(off, n3)], np.int32)
     assert n3.max() <= abi.SEL_MAX_REGS
     check(eng, torch, f"post_{name}", off, regs3, n3, s.id0, so, regs7, want_npri)

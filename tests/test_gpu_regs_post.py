@@ -114,7 +114,7 @@ def test_switch_on_chain2aln_and_submit_wait():
     raw, raw_n = eng.chain2aln(batch)
     plain = compact(batch, raw, raw_n)
     assert G.region_mismatch(plain, raw_want) is None
-    off = (np.cumsum(raw_n, dtype=np.int64) - raw_n).astype(np.int64)
+    off = G.offsets(raw_n)
     for flags in (1, 3):
         want_regs, want_n = eng.regs_post(batch.seq_off, batch.seq, off, plain, raw_n, flags, 4242, s.popt)
         want = (P.dense(want_regs, off, want_n), want_n)
@@ -140,7 +140,7 @@ def test_switch_on_seqs2regions():
     nr = 600
     seq_off, seq = cg["seq_off"][:nr + 1], cg["seq"][:int(cg["seq_off"][nr])]
     raw_n, raw = eng.seqs2regions(seq_off, seq, cg["seedopt"], cg["split_factor"], cg["copt"])
-    off = (np.cumsum(raw_n, dtype=np.int64) - raw_n).astype(np.int64)
+    off = G.offsets(raw_n)
     popt = abi.default_postopt()
     want_regs, want_n = eng.regs_post(seq_off, seq, off, raw, raw_n, 3, 99, popt)
     eng.set_regs_post(3, 99, popt)
@@ -167,7 +167,7 @@ def _reg(rb, re, qb, qe, rid=0, score=None, **kw):
 def _hand(eng, reads, flags=1, l_seq=100):
     """reads: a list of per-read region lists -> per-read surviving regions"""
     n = np.array([len(r) for r in reads], np.int32)
-    off = (np.cumsum(n, dtype=np.int64) - n).astype(np.int64)
+    off = G.offsets(n)
     regs = np.concatenate([x for r in reads for x in r]) if n.sum() else np.zeros(0, abi.ALNREG_DTYPE)
     seq_off = np.arange(len(reads) + 1, dtype=np.int64) * l_seq
     seq = np.zeros(int(seq_off[-1]), np.uint8)

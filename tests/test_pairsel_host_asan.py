@@ -1,5 +1,5 @@
 """tests/cpp/pairsel_host_asan.cpp: the host-side validation, span arithmetic and tables of
-bwagpu_mark_primary / bwagpu_pair_select (bwa-flow_amd/csrc/pairsel_host.h) as a
+bwagpu_mark_primary / bwagpu_pair_select (bwa-flow_amd/csrc/stage_host.h) as a
 stand-alone program under AddressSanitizer and UBSan, on the CPU."""
 import os
 import subprocess

@@ -10,6 +10,7 @@ import tempfile
 import numpy as np
 import pytest
 
+import golden_io as G
 import post_io as P
 from bwagpu import abi
 
@@ -46,7 +47,7 @@ def test_expected_outputs_obey_the_invariants(name):
     assert np.array_equal(n3, n7)
     assert (n3 <= s.n).all()
     assert (r3["qe"] > r3["qb"]).all() and (r7["qe"] > r7["qb"]).all()
-    o3 = np.cumsum(n3) - n3
+    o3 = G.offsets(n3)
     # a read with n <= 1 is unchanged apart from the flags (is_alt; with flag 4 also
     # sub / alt_sc / secondary / secondary_all / hash)
     one = np.nonzero(s.n == 1)[0]

@@ -1,5 +1,5 @@
 """tests/cpp/post_host_asan.cpp: bwagpu_regs_post's host-side validation and
-span arithmetic (bwa-flow_amd/csrc/regpost_host.h) as a stand-alone program
+span arithmetic (bwa-flow_amd/csrc/stage_host.h) as a stand-alone program
 under AddressSanitizer and UBSan, on the CPU."""
 import os
 import subprocess

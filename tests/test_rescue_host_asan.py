@@ -1,5 +1,5 @@
 """tests/cpp/rescue_host_asan.cpp: the host-side validation and span arithmetic of
-bwagpu_pestat / bwagpu_mate_rescue (bwa-flow_amd/csrc/rescue_host.h) as a
+bwagpu_pestat / bwagpu_mate_rescue (bwa-flow_amd/csrc/stage_host.h) as a
 stand-alone program under AddressSanitizer and UBSan, on the CPU."""
 import os
 import subprocess
