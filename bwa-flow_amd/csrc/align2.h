@@ -1,5 +1,5 @@
 // align2.h — internal declarations of the batched ksw_align2 kernels
-// (align2.hip) shared with the C ABI (capi.hip).  Not part of the ABI.
+// (align2.hip) shared with the C ABI (capi_tasks.hip).  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -9,20 +9,7 @@
 
 namespace bwagpu {
 
-// Segment-count buckets: one compiled kernel per (bucket, u8/i16).  A task's
-// bucket is that of its first pass (p*ceil(qlen/p) columns over 64 lanes);
-// its reverse pass has fewer columns and reuses the same body.
-constexpr int kA2Buckets = 8;
-extern const int kA2CD[kA2Buckets];  // {1, 2, 3, 4, 6, 8, 12, 16}
-constexpr int kA2Bins = 2 * kA2Buckets;  // bins [0, 8): i16, [8, 16): u8
-
-__host__ __device__ inline int a2_bin_of(int qlen, bool u8) {
-  const int p = u8 ? 16 : 8;
-  const int ncol = (qlen + p - 1) / p * p;
-  const int cd = ncol > 64 ? (ncol + 63) / 64 : 1;
-  const int b = cd <= 4 ? cd - 1 : cd <= 6 ? 4 : cd <= 8 ? 5 : cd <= 12 ? 6 : 7;
-  return (u8 ? kA2Buckets : 0) + b;
-}
+// (the buckets, kA2CD and a2_bin_of: pure.h)
 
 // Query-profile rows for v_perm_b32: for target base t, the 8-byte pool
 // {lo[t], hi[t]} holds the profile byte of query base 0..3 (lo), 4 (hi byte 0)

@@ -42,8 +42,6 @@
 
 namespace bwagpu {
 
-const int kA2CD[kA2Buckets] = {1, 2, 3, 4, 6, 8, 12, 16};
-
 namespace {
 
 __device__ __forceinline__ int usat(int a, int b) {  // max(a - b, 0) for a, b >= 0 (v_sub_u32 clamp)

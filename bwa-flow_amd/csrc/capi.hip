@@ -21,8 +21,6 @@
 #include <thread>
 #include <vector>
 
-#include "align2.h"
-#include "reg2aln.h"
 #include "regpost.h"
 #include "seed.h"
 #include "chain.h"
@@ -105,8 +103,6 @@ void host_parallel(int nt, F f) {
   done.wait(g, [&] { return left == 0; });
 }
 
-
-
 // layout of one batch inside a slot's single input allocation
 struct InLayout {
   size_t seq_off, seq, rco, cso, rid, frac, seeds, total;
@@ -127,7 +123,6 @@ struct InLayout {
     total = o;
   }
 };
-
 
 // Side-stream probes.  HIP maps every stream of the process onto one of
 // GPU_MAX_HW_QUEUES hardware queues (4 on the pool's boxes), and work on two
@@ -218,7 +213,6 @@ __global__ void __launch_bounds__(256) dense_copy_kernel(const bwagpu_alnreg_t* 
 
 namespace {
 
-
 bool make_opt(const bwagpu_opt_t* o, DevOpt* d, std::string* why) {
   if (!o) { *why = "opt is NULL"; return false; }
   if (o->e_del <= 0 || o->e_ins <= 0) { *why = "gap extension penalties must be > 0"; return false; }
@@ -256,39 +250,6 @@ bool make_opt(const bwagpu_opt_t* o, DevOpt* d, std::string* why) {
   }
   return true;
 }
-
-// ksw_qinit's profile (ksw.c:69-108) as v_perm byte pools, see A2Prof
-A2Prof make_a2prof(const DevOpt& o, bool u8) {
-  A2Prof P{};
-  int mn = 127, mx = 0;
-  for (int i = 0; i < 25; ++i) {
-    mn = std::min<int>(mn, o.mat[i]);
-    mx = std::max<int>(mx, o.mat[i]);
-  }
-  const int shift = (256 - (mn & 0xff)) & 0xff;
-  const int bias = u8 ? shift : 128;
-  for (int t = 0; t < 5; ++t) {
-    uint32_t lo = 0;
-    for (int q = 0; q < 4; ++q) lo |= (uint32_t)(uint8_t)(o.mat[t * 5 + q] + bias) << (8 * q);
-    P.lo[t] = lo;
-    P.hi[t] = (uint32_t)(uint8_t)(o.mat[t * 5 + 4] + bias) | (uint32_t)(uint8_t)bias << 8;
-  }
-  P.shift = shift;
-  P.qmax = mx;
-  P.e_del = o.e_del;
-  P.oe_del = o.oe_del;
-  P.e_ins = o.e_ins;
-  P.oe_ins = o.oe_ins;
-  return P;
-}
-
-
-// Launch the given bins concurrently: fork the align2 streams off `st`,
-// deal the bins (in the given order) round-robin over them, join back.
-// counts_host: task count per bin when known (0 = unknown -> grid = capacity).
-int launch_align2_concurrent(bwagpu_ctx_t* ctx, hipStream_t st, const std::vector<int>& bins, const A2Args& base,
-                             const int32_t* list_off, const int32_t* counts_host, int32_t* d_counts,
-                             int32_t* d_cursors, size_t list_stride);
 
 int create_common(int device, const bwagpu_opt_t* opt, const bwagpu_bns_t* bns, bwagpu_ctx_t** out,
                   bwagpu_ctx_t** made) {
@@ -375,8 +336,6 @@ void destroy_ctx(bwagpu_ctx_t* ctx) {
     if (ctx->a2_join[i]) (void)hipEventDestroy(ctx->a2_join[i]);
   }
   if (ctx->a2_fork) (void)hipEventDestroy(ctx->a2_fork);
-  ctx->a2_tasks.release(); ctx->a2_q.release(); ctx->a2_t.release(); ctx->a2_out.release();
-  ctx->a2_scratch.release(); ctx->a2_lists.release(); ctx->a2_counts.release(); ctx->a2_boff.release();
   ctx->ch_slot.release_scratch();
   for (int k = 0; k < 2; ++k) {
     if (ctx->ch_cs.side[k]) (void)hipStreamSynchronize(ctx->ch_cs.side[k]);
@@ -385,7 +344,9 @@ void destroy_ctx(bwagpu_ctx_t* ctx) {
   }
   if (ctx->ch_cs.fork) (void)hipEventDestroy(ctx->ch_cs.fork);
   ctx->ch_slot.d_out.release(); ctx->ch_slot.d_n.release(); ctx->ch_slot.d_stats.release();
-  for (DevBuf* b : {&ctx->r2_tasks, &ctx->r2_q, &ctx->r2_out, &ctx->r2_cig, &ctx->r2_md, &ctx->r2_lists, &ctx->r2_z,
+  for (DevBuf* b : {&ctx->ex_tasks, &ctx->ex_list, &ctx->ex_q, &ctx->ex_t, &ctx->ex_res, &ctx->ex_stats, &ctx->a2_tasks,
+                    &ctx->a2_q, &ctx->a2_t, &ctx->a2_out, &ctx->a2_scratch, &ctx->a2_lists, &ctx->a2_counts, &ctx->a2_boff,
+                    &ctx->r2_tasks, &ctx->r2_q, &ctx->r2_out, &ctx->r2_cig, &ctx->r2_md, &ctx->r2_lists, &ctx->r2_z,
                     &ctx->r2_stats, &ctx->bwt_words, &ctx->sa_d, &ctx->sa_in, &ctx->sa_out, &ctx->occ_d, &ctx->sup_d, &ctx->sa_full, &ctx->sd_off,
                     &ctx->sd_seq, &ctx->sd_out, &ctx->sd_n, &ctx->sd_scratch, &ctx->sd_poff, &ctx->sd_pack,
                     &ctx->sd_heavy, &ctx->sd_dbg, &ctx->st_buf, &ctx->st_start, &ctx->st_q, &ctx->st_tasks, &ctx->st_lists,
@@ -566,16 +527,6 @@ int stage_and_check(bwagpu_ctx_t* ctx, const bwagpu_batch_t* b, char* h, const I
   for (int t = 0; t < nt; ++t) lm = std::max(lm, lmaxs[t]);
   *lq_max_out = (int)lm;
   return BWAGPU_OK;
-}
-
-// LDS row-buffer bytes per group for reads up to lq_max (see rows_needed)
-int tb_bytes_for(const DevOpt& o, int lq_max) {
-  const int eb = std::max(o.pen_clip5, o.pen_clip3);
-  const int cap = std::max(band_cap(lq_max, o.max_mat, eb, o.o_ins, o.e_ins),
-                           band_cap(lq_max, o.max_mat, eb, o.o_del, o.e_del));
-  const int we = std::min(o.w << 1, cap);
-  const int n = lq_max + we + 2;
-  return (n + 15) & ~15;
 }
 
 // BWAGPU_C2A_PATH=fast: the wave-per-read kernels (chain2aln_fast_kernel /
@@ -803,7 +754,6 @@ int enqueue_chain2aln(bwagpu_ctx_t* ctx, Slot& s, const DevBatch& db, int lq_max
 }
 
 }  // namespace
-
 
 extern "C" {
 
@@ -1163,468 +1113,6 @@ int bwagpu_chain2aln_device(bwagpu_ctx_t* ctx, const bwagpu_batch_t* db_in, bwag
   return enqueue_chain2aln(ctx, s, db, lq_bound, dev_out, dev_n, stats, st);
 }
 
-int bwagpu_extend_batch(bwagpu_ctx_t* ctx, int32_t n, const bwagpu_ext_task_t* tasks, const uint8_t* qpool,
-                        int64_t qpool_len, const uint8_t* tpool, int64_t tpool_len, bwagpu_ext_result_t* results) {
-  if (!ctx || n < 0 || (n && (!tasks || !results))) return BWAGPU_E_INVAL;
-  if (n == 0) return BWAGPU_OK;
-  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
-  // validate and bin on the host
-  // bins: the wave kernels by column segments, then the four-per-wave kernel
-  // (packed 16-bit DP) for the tasks it takes (extend4_kernel)
-  std::vector<int32_t> lists[kNumExtVariants + 1];
-  const bool quad = ctx->ext_form == 0;
-  bool t5 = false;
-  int lq_max = 1;
-  for (int32_t k = 0; k < n; ++k) {
-    const bwagpu_ext_task_t& t = tasks[k];
-    if (t.qlen < 0 || t.tlen < 0 || t.qoff < 0 || t.toff < 0 || t.qoff + t.qlen > qpool_len ||
-        t.toff + t.tlen > tpool_len || t.w < 0)
-      return fail(ctx, BWAGPU_E_INVAL, "task outside its pools");
-    if (t.qlen + 1 > kExtVariants[kNumExtVariants - 1].max_len()) return fail(ctx, BWAGPU_E_UNSUPPORTED, "qlen too long");
-    int v = kNumExtVariants - 1;
-    for (int i = kNumExtVariants - 1; i >= 0; --i)
-      if (t.qlen + 1 <= kExtVariants[i].max_len()) v = i;
-    if (quad && t.h0 > 0 && t.qlen >= 1 && t.qlen + 1 <= 256 &&
-        quad_bound_ok(ctx->opt, t.h0 + (long)t.qlen * ctx->opt.max_mat) && quad_rows_ok(ctx->opt, t.tlen)) {
-      bool nt = true;  // no N in the target rows
-      for (int64_t i = t.toff; i < t.toff + t.tlen && nt; ++i) nt = tpool[i] <= 3;
-      if (nt) v = kNumExtVariants;
-    }
-    lists[v].push_back(k);
-    lq_max = std::max(lq_max, t.qlen + 1);
-  }
-  for (int64_t i = 0; i < tpool_len && !t5; ++i) t5 = tpool[i] > 3;
-  for (int64_t i = 0; i < qpool_len; ++i)
-    if (qpool[i] > 4) return fail(ctx, BWAGPU_E_INVAL, "query base > 4");
-  for (int64_t i = 0; i < tpool_len; ++i)
-    if (tpool[i] > 4) return fail(ctx, BWAGPU_E_INVAL, "target base > 4");
-  // LDS rows needed per task (rows_needed on the host) -> per-variant max
-  Slot& s = ctx->slot[0];
-  hipStream_t st = nullptr;
-  HIPC(lazy_stream(s, &st), "hipStreamCreate");
-  DevBuf d_tasks, d_list, d_q, d_t, d_res, d_stats;
-  auto cleanup = [&]() {
-    d_tasks.release(); d_list.release(); d_q.release(); d_t.release(); d_res.release(); d_stats.release();
-  };
-  auto ck = [&](hipError_t e, const char* what) {
-    if (e != hipSuccess) {
-      cleanup();
-      return hip_fail(ctx, e, what);
-    }
-    return 0;
-  };
-  int rc;
-  if ((rc = ck(d_tasks.ensure(sizeof(bwagpu_ext_task_t) * n), "hipMalloc"))) return rc;
-  if ((rc = ck(d_list.ensure(sizeof(int32_t) * n), "hipMalloc"))) return rc;
-  if ((rc = ck(d_q.ensure((size_t)qpool_len + 1), "hipMalloc"))) return rc;
-  if ((rc = ck(d_t.ensure((size_t)tpool_len + 1), "hipMalloc"))) return rc;
-  if ((rc = ck(d_res.ensure(sizeof(bwagpu_ext_result_t) * n), "hipMalloc"))) return rc;
-  if ((rc = ck(d_stats.ensure(sizeof(int64_t) * ST_N), "hipMalloc"))) return rc;
-  if ((rc = ck(hipMemcpyAsync(d_tasks.p, tasks, sizeof(bwagpu_ext_task_t) * n, hipMemcpyHostToDevice, st), "H2D"))) return rc;
-  if (qpool_len && (rc = ck(hipMemcpyAsync(d_q.p, qpool, (size_t)qpool_len, hipMemcpyHostToDevice, st), "H2D"))) return rc;
-  if (tpool_len && (rc = ck(hipMemcpyAsync(d_t.p, tpool, (size_t)tpool_len, hipMemcpyHostToDevice, st), "H2D"))) return rc;
-  if ((rc = ck(hipMemsetAsync(d_stats.p, 0, sizeof(int64_t) * ST_N, st), "memset"))) return rc;
-  EventPair ev;
-  (void)ev.start(st);
-  int32_t off = 0;
-  std::vector<int32_t> all;
-  for (int v = 0; v <= kNumExtVariants; ++v) all.insert(all.end(), lists[v].begin(), lists[v].end());
-  if ((rc = ck(hipMemcpyAsync(d_list.p, all.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, st), "H2D"))) return rc;
-  for (int v = 0; v <= kNumExtVariants; ++v) {
-    const int32_t nv = (int32_t)lists[v].size();
-    if (nv) {
-      int rows = 16;
-      for (int32_t k : lists[v]) {
-        const bwagpu_ext_task_t& t = tasks[k];
-        int mi = band_cap(t.qlen, ctx->opt.max_mat, t.end_bonus, ctx->opt.o_ins, ctx->opt.e_ins);
-        int md = band_cap(t.qlen, ctx->opt.max_mat, t.end_bonus, ctx->opt.o_del, ctx->opt.e_del);
-        int we = std::min(t.w, std::min(mi, md));
-        rows = std::max(rows, std::min(t.tlen, t.qlen + we + 1));
-      }
-      const int tb = (rows + 2 + 15) & ~15;
-      const int gpb = v < kNumExtVariants ? kBlock / kExtVariants[v].G : 2 * kBlock / 32;
-      if ((size_t)tb * gpb > 64 * 1024) {
-        cleanup();
-        return fail(ctx, BWAGPU_E_UNSUPPORTED, "task needs too many LDS rows");
-      }
-      hipError_t e =
-          v < kNumExtVariants
-              ? launch_extend(v, t5, ctx->opt, n, d_tasks.as<bwagpu_ext_task_t>(), d_list.as<int32_t>() + off, nv,
-                              d_q.as<uint8_t>(), d_t.as<uint8_t>(), tb, d_res.as<bwagpu_ext_result_t>(),
-                              d_stats.as<int64_t>(), st)
-              : launch_extend4(ctx->opt, d_tasks.as<bwagpu_ext_task_t>(), d_list.as<int32_t>() + off, nv,
-                               d_q.as<uint8_t>(), d_t.as<uint8_t>(), tb, d_res.as<bwagpu_ext_result_t>(),
-                               d_stats.as<int64_t>(), st);
-      if ((rc = ck(e, "extend launch"))) return rc;
-    }
-    off += nv;
-  }
-  (void)ev.stop(st);
-  int64_t hs[ST_N];
-  if ((rc = ck(hipMemcpyAsync(results, d_res.p, sizeof(bwagpu_ext_result_t) * n, hipMemcpyDeviceToHost, st), "D2H"))) return rc;
-  if ((rc = ck(hipMemcpyAsync(hs, d_stats.p, sizeof(hs), hipMemcpyDeviceToHost, st), "D2H"))) return rc;
-  if ((rc = ck(hipStreamSynchronize(st), "extend batch"))) return rc;
-  s.last = bwagpu_stats_t{};
-  s.last.kernel_ms = ev.ms();
-  s.last.cells = hs[ST_CELLS];
-  s.last.rows = hs[ST_ROWS];
-  s.last.ext_calls = hs[ST_CALLS];
-  cleanup();
-  return BWAGPU_OK;
-}
-
-}  // extern "C"
-
-namespace {
-int launch_align2_concurrent(bwagpu_ctx_t* ctx, hipStream_t st, const std::vector<int>& bins, const A2Args& base,
-                             const int32_t* list_off, const int32_t* counts_host, int32_t* d_counts,
-                             int32_t* d_cursors, size_t list_stride) {
-  constexpr int NS = bwagpu_ctx::kA2Streams;
-  for (int i = 0; i < NS; ++i) {
-    if (!ctx->a2_st[i]) HIPC(hipStreamCreateWithFlags(&ctx->a2_st[i], hipStreamNonBlocking), "stream");
-    if (!ctx->a2_join[i]) HIPC(hipEventCreateWithFlags(&ctx->a2_join[i], hipEventDisableTiming), "event");
-  }
-  if (!ctx->a2_fork) HIPC(hipEventCreateWithFlags(&ctx->a2_fork, hipEventDisableTiming), "event");
-  const int used = std::min<int>(NS, (int)bins.size());
-  HIPC(hipEventRecord(ctx->a2_fork, st), "event");
-  for (int i = 0; i < used; ++i) HIPC(hipStreamWaitEvent(ctx->a2_st[i], ctx->a2_fork, 0), "stream wait");
-  for (size_t k = 0; k < bins.size(); ++k) {
-    const int b = bins[k];
-    A2Args a = base;
-    a.list = base.list + (list_off ? list_off[b] : (size_t)b * list_stride);
-    a.count = d_counts + b;
-    a.cursor = d_cursors + b;
-    HIPC(launch_align2(b, a, make_a2prof(ctx->opt, b >= kA2Buckets), counts_host ? counts_host[b] : 0,
-                       ctx->a2_st[k % used]),
-         "align2 launch");
-  }
-  for (int i = 0; i < used; ++i) {
-    HIPC(hipEventRecord(ctx->a2_join[i], ctx->a2_st[i]), "event");
-    HIPC(hipStreamWaitEvent(st, ctx->a2_join[i], 0), "stream wait");
-  }
-  return BWAGPU_OK;
-}
-}  // namespace
-
-extern "C" {
-
-// mem_reg2aln's CIGAR part (bwa/bwamem.c:1104-1174) per job.  Jobs are binned on
-// the host by query segments (kernel template) and by the size of their
-// direction matrix (ksw_global2's z, ncol x tlen bytes, ksw.c:511-512): the
-// matrix sits in LDS for jobs up to kR2ZSmall / kR2ZLarge bytes and in a
-// per-wave HBM slice beyond.
-namespace {
-constexpr int kR2ZSmall = 8 * 1024, kR2ZLarge = 24 * 1024;
-constexpr int kR2MaxRef = 8192;  // reference window bytes per job (LDS)
-}  // namespace
-
-int bwagpu_reg2aln_batch(bwagpu_ctx_t* ctx, int32_t n, const bwagpu_reg2aln_task_t* tasks, const uint8_t* qpool,
-                         int64_t qpool_len, int32_t max_ops, int32_t max_md, bwagpu_aln_t* out, uint32_t* cigar,
-                         char* md) {
-  if (!ctx || n < 0 || (n && (!tasks || !out || !cigar || !md)) || qpool_len < 0 || (qpool_len && !qpool) ||
-      max_ops < 1 || max_md < 1)
-    return BWAGPU_E_INVAL;
-  if (n == 0) return BWAGPU_OK;
-  const DevOpt& o = ctx->opt;
-  const int64_t l_pac = ctx->ref.l_pac, two = l_pac << 1;
-  const int wmax = o.w << 2;
-  // validate; bin by [query bucket][matrix class 0 LDS small, 1 LDS large, 2 HBM]
-  struct Bin {
-    std::vector<int32_t> ids;
-    int qmax = 0, rmax = 0;
-    int64_t zmax = 0;
-  };
-  Bin bins[kR2Buckets][3];
-  std::vector<int64_t> cost((size_t)n, 0);
-  for (int32_t k = 0; k < n; ++k) {
-    const bwagpu_reg2aln_task_t& t = tasks[k];
-    if (t.l_seq < 0 || t.qoff < 0 || t.qoff + t.l_seq > qpool_len)
-      return fail(ctx, BWAGPU_E_INVAL, "job's read outside the query pool");
-    int lq = 0, rl = 0, cls = 0;
-    int64_t zb = 0;
-    if (t.rb >= 0 && t.re >= 0) {
-      const int64_t beg = t.rb, end = t.re > two ? two : t.re;
-      const bool ok = t.qe - t.qb > 0 && t.rb < t.re && !(t.rb < l_pac && t.re > l_pac) &&
-                      (beg >= l_pac || end <= l_pac) && end - beg == t.re - t.rb;
-      if (ok) {
-        if (t.qb < 0 || t.qe > t.l_seq) return fail(ctx, BWAGPU_E_INVAL, "job's qb/qe outside its read");
-        lq = t.qe - t.qb;
-        if (lq > BWAGPU_MAX_READ_LEN) return fail(ctx, BWAGPU_E_UNSUPPORTED, "qe - qb > BWAGPU_MAX_READ_LEN");
-        if (t.re - t.rb > kR2MaxRef) return fail(ctx, BWAGPU_E_UNSUPPORTED, "re - rb > 8192");
-        rl = (int)(t.re - t.rb);
-        // the widest band any try can use: the first try's w2 (infer_bw,
-        // bwamem.c:1123-1126) doubled at most twice (1132), capped at
-        // opt->w << 2, then bwa.c:152-159
-        auto infer = [&](int q_, int r_) {
-          if (lq == rl && lq * o.a - t.truesc < (q_ + r_ - o.a) << 1) return 0;
-          const int w = (int)((double)(std::min(lq, rl) * o.a - t.truesc - q_) / r_ + 2.);
-          return std::max(w, std::abs(lq - rl));
-        };
-        int w2 = std::max(infer(o.o_del, o.e_del), infer(o.o_ins, o.e_ins));
-        if (w2 > o.w) w2 = std::min(w2, t.w);
-        w2 = std::min(w2, wmax);
-        const int w2max = (int)std::min<int64_t>((int64_t)w2 << 2, wmax);
-        const int half = (lq + 1) >> 1;
-        const int mi = (int)((double)(half * o.mat[0] - o.o_ins) / o.e_ins + 1.);
-        const int mdl = (int)((double)(half * o.mat[0] - o.o_del) / o.e_del + 1.);
-        const int mg = std::max(std::max(mi, mdl), 1), dl = std::abs(rl - lq);
-        const int wb = std::max(std::min((mg + dl + 1) >> 1, w2max), dl + 3);
-        zb = (int64_t)std::min(lq, 2 * wb + 1) * rl;
-        cls = zb <= kR2ZSmall ? 0 : (zb <= kR2ZLarge ? 1 : 2);
-      }
-    }
-    Bin& b = bins[r2_bucket_of(lq)][cls];
-    b.ids.push_back(k);
-    b.qmax = std::max(b.qmax, lq);
-    b.rmax = std::max(b.rmax, rl);
-    b.zmax = std::max(b.zmax, zb);
-    cost[(size_t)k] = zb + lq + rl;
-  }
-  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
-  hipStream_t st = nullptr;
-  HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
-  HIPC(ctx->r2_tasks.ensure(sizeof(bwagpu_reg2aln_task_t) * n), "hipMalloc");
-  HIPC(ctx->r2_q.ensure((size_t)qpool_len + 1), "hipMalloc");
-  HIPC(ctx->r2_out.ensure(sizeof(bwagpu_aln_t) * n), "hipMalloc");
-  HIPC(ctx->r2_cig.ensure(sizeof(uint32_t) * (size_t)n * max_ops), "hipMalloc");
-  HIPC(ctx->r2_md.ensure((size_t)n * max_md), "hipMalloc");
-  HIPC(ctx->r2_lists.ensure(sizeof(int32_t) * n), "hipMalloc");
-  HIPC(ctx->r2_stats.ensure(sizeof(int64_t) * ST_N), "hipMalloc");
-  std::vector<int32_t> all;
-  all.reserve((size_t)n);
-  for (auto& row : bins)
-    for (auto& b : row) {
-      // largest matrices first: the last claims are the small jobs
-      std::stable_sort(b.ids.begin(), b.ids.end(), [&](int32_t x, int32_t y) { return cost[x] > cost[y]; });
-      all.insert(all.end(), b.ids.begin(), b.ids.end());
-    }
-  HIPC(hipMemcpyAsync(ctx->r2_tasks.p, tasks, sizeof(bwagpu_reg2aln_task_t) * n, hipMemcpyHostToDevice, st), "H2D");
-  if (qpool_len) HIPC(hipMemcpyAsync(ctx->r2_q.p, qpool, (size_t)qpool_len, hipMemcpyHostToDevice, st), "H2D");
-  HIPC(hipMemcpyAsync(ctx->r2_lists.p, all.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, st), "H2D");
-  HIPC(hipMemsetAsync(ctx->r2_stats.p, 0, sizeof(int64_t) * ST_N, st), "memset");
-  // bins run concurrently on the context's side streams, largest first
-  constexpr int NS = bwagpu_ctx::kA2Streams;
-  for (int i = 0; i < NS; ++i) {
-    if (!ctx->a2_st[i]) HIPC(hipStreamCreateWithFlags(&ctx->a2_st[i], hipStreamNonBlocking), "stream");
-    if (!ctx->a2_join[i]) HIPC(hipEventCreateWithFlags(&ctx->a2_join[i], hipEventDisableTiming), "event");
-  }
-  if (!ctx->a2_fork) HIPC(hipEventCreateWithFlags(&ctx->a2_fork, hipEventDisableTiming), "event");
-  struct Launch {
-    int bk, cls;
-    int32_t off;
-    int64_t work;
-  };
-  std::vector<Launch> launches;
-  {
-    int32_t off = 0;
-    for (int bk = 0; bk < kR2Buckets; ++bk)
-      for (int cls = 0; cls < 3; ++cls) {
-        const Bin& b = bins[bk][cls];
-        if (b.ids.empty()) continue;
-        int64_t w = 0;
-        for (int32_t k : b.ids) w += cost[(size_t)k];
-        launches.push_back({bk, cls, off, w});
-        off += (int32_t)b.ids.size();
-      }
-  }
-  std::sort(launches.begin(), launches.end(), [](const Launch& x, const Launch& y) { return x.work > y.work; });
-  const int used = std::min<int>(NS, (int)launches.size());
-  EventPair ev;
-  HIPC(ev.start(st), "event");
-  HIPC(hipEventRecord(ctx->a2_fork, st), "event");
-  for (int i = 0; i < used; ++i) HIPC(hipStreamWaitEvent(ctx->a2_st[i], ctx->a2_fork, 0), "stream wait");
-  auto make_args = [&](const Launch& L, int& wpb) {
-    const Bin& b = bins[L.bk][L.cls];
-    R2AArgs a{};
-    a.tasks = ctx->r2_tasks.as<bwagpu_reg2aln_task_t>();
-    a.qpool = ctx->r2_q.as<uint8_t>();
-    a.list = ctx->r2_lists.as<int32_t>() + L.off;
-    a.n = (int)b.ids.size();
-    a.max_ops = max_ops;
-    a.max_md = max_md;
-    a.out = ctx->r2_out.as<bwagpu_aln_t>();
-    a.cigar = ctx->r2_cig.as<uint32_t>();
-    a.md = ctx->r2_md.as<char>();
-    a.stats = ctx->r2_stats.as<int64_t>();
-    a.qcap = (b.qmax + 16) & ~15;
-    a.rcap = (b.rmax + 16) & ~15;
-    a.ocap = a.qcap + a.rcap + 4;
-    int lpw = a.qcap + a.rcap + 4 * a.ocap;
-    if (L.cls < 2) lpw += L.cls == 0 ? kR2ZSmall : kR2ZLarge;
-    a.lds_per_wave = (lpw + 15) & ~15;
-    wpb = L.cls == 1 ? 1 : 4;  // LDS-heavy bins: one wave per workgroup packs LDS finer
-    a.zstride = L.cls == 2 ? ((b.zmax + 255) & ~(int64_t)255) : 0;
-    return a;
-  };
-  // grids first (HBM matrix slices: one per launched wave, at most 1 GiB per bin)
-  size_t zoff = 0;
-  for (Launch& L : launches) {
-    int wpb = 4;
-    const R2AArgs a = make_args(L, wpb);
-    if ((size_t)wpb * a.lds_per_wave > 160 * 1024)
-      return fail(ctx, BWAGPU_E_UNSUPPORTED, "reg2aln job needs more LDS than a workgroup has");
-    int waves = r2_resident_waves(kR2CD[L.bk], (size_t)wpb * a.lds_per_wave, wpb);
-    if (L.cls == 2) {
-      waves = (int)std::min<int64_t>(waves, std::max<int64_t>(4, ((int64_t)1 << 30) / a.zstride));
-      zoff += (size_t)a.zstride * waves;
-    }
-    L.work = waves;
-  }
-  HIPC(ctx->r2_z.ensure(std::max<size_t>(zoff, 256)), "hipMalloc(reg2aln matrices)");
-  zoff = 0;
-  for (size_t li = 0; li < launches.size(); ++li) {
-    const Launch& L = launches[li];
-    int wpb = 4;
-    R2AArgs a = make_args(L, wpb);
-    const int nb = a.n, waves = (int)L.work;
-    if (L.cls == 2) {
-      a.zglob = ctx->r2_z.as<uint8_t>() + zoff;
-      zoff += (size_t)a.zstride * waves;
-    }
-    const int blocks = std::max(1, std::min((nb + wpb - 1) / wpb, waves / wpb));
-    HIPC(launch_reg2aln(kR2CD[L.bk], o, ctx->ref, a, blocks, wpb, ctx->a2_st[li % used]), "reg2aln launch");
-  }
-  for (int i = 0; i < used; ++i) {
-    HIPC(hipEventRecord(ctx->a2_join[i], ctx->a2_st[i]), "event");
-    HIPC(hipStreamWaitEvent(st, ctx->a2_join[i], 0), "stream wait");
-  }
-  HIPC(ev.stop(st), "event");
-  HIPC(hipMemcpyAsync(out, ctx->r2_out.p, sizeof(bwagpu_aln_t) * n, hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipMemcpyAsync(cigar, ctx->r2_cig.p, sizeof(uint32_t) * (size_t)n * max_ops, hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipMemcpyAsync(md, ctx->r2_md.p, (size_t)n * max_md, hipMemcpyDeviceToHost, st), "D2H");
-  int64_t hst[ST_N];
-  HIPC(hipMemcpyAsync(hst, ctx->r2_stats.p, sizeof(hst), hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipStreamSynchronize(st), "reg2aln execution");
-  Slot& s0 = ctx->slot[0];
-  s0.last = bwagpu_stats_t{};
-  s0.last.kernel_ms = ev.ms();
-  s0.last.cells = hst[ST_CELLS];
-  s0.last.rows = hst[ST_ROWS];
-  s0.last.ext_calls = hst[ST_CALLS];
-  return BWAGPU_OK;
-}
-
-int bwagpu_align2_batch(bwagpu_ctx_t* ctx, int32_t n, const bwagpu_align2_task_t* tasks, const uint8_t* qpool,
-                        int64_t qpool_len, const uint8_t* tpool, int64_t tpool_len, bwagpu_kswr_t* results) {
-  if (!ctx || n < 0 || (n && (!tasks || !results)) || qpool_len < 0 || tpool_len < 0 ||
-      (qpool_len && !qpool) || (tpool_len && !tpool))
-    return BWAGPU_E_INVAL;
-  if (n == 0) return BWAGPU_OK;
-  if (const char* why = align2_opt_unsupported(ctx->opt)) return fail(ctx, BWAGPU_E_UNSUPPORTED, why);
-  // validate and bin on the host
-  std::vector<int32_t> lists[kA2Bins];
-  std::vector<int64_t> boff((size_t)n);
-  int64_t scratch = 0;
-  for (int32_t k = 0; k < n; ++k) {
-    const bwagpu_align2_task_t& t = tasks[k];
-    if (t.qlen < 0 || t.tlen < 0 || t.qoff < 0 || t.toff < 0 || t.qoff + t.qlen > qpool_len ||
-        t.toff + t.tlen > tpool_len)
-      return fail(ctx, BWAGPU_E_INVAL, "task outside its pools");
-    if (t.qlen > BWAGPU_MAX_READ_LEN) return fail(ctx, BWAGPU_E_UNSUPPORTED, "qlen > BWAGPU_MAX_READ_LEN");
-    const bool u8 = (t.xtra & BWAGPU_KSW_XBYTE) != 0;
-    if (!u8 && (int64_t)t.qlen * ctx->opt.max_mat > 32767)
-      return fail(ctx, BWAGPU_E_UNSUPPORTED, "i16 scores could saturate (qlen * max score > 32767)");
-    lists[a2_bin_of(t.qlen, u8)].push_back(k);
-    boff[(size_t)k] = scratch;
-    scratch += (int64_t)t.tlen + 1;
-  }
-  for (int64_t i = 0; i < qpool_len; ++i)
-    if (qpool[i] > 4) return fail(ctx, BWAGPU_E_INVAL, "query base > 4");
-  for (int64_t i = 0; i < tpool_len; ++i)
-    if (tpool[i] > 4) return fail(ctx, BWAGPU_E_INVAL, "target base > 4");
-  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
-  Slot& s = ctx->slot[0];
-  hipStream_t st = nullptr;
-  HIPC(lazy_stream(s, &st), "hipStreamCreate");
-  HIPC(ctx->a2_tasks.ensure(sizeof(bwagpu_align2_task_t) * n), "hipMalloc");
-  HIPC(ctx->a2_q.ensure((size_t)qpool_len + 1), "hipMalloc");
-  HIPC(ctx->a2_t.ensure((size_t)tpool_len + 1), "hipMalloc");
-  HIPC(ctx->a2_out.ensure(sizeof(bwagpu_kswr_t) * n), "hipMalloc");
-  HIPC(ctx->a2_scratch.ensure(sizeof(int2) * (size_t)scratch), "hipMalloc");
-  HIPC(ctx->a2_lists.ensure(sizeof(int32_t) * n), "hipMalloc");
-  // counts[kA2Bins] | cursors[kA2Bins] | stats[ST_N]
-  HIPC(ctx->a2_counts.ensure(sizeof(int32_t) * 2 * kA2Bins + sizeof(int64_t) * ST_N), "hipMalloc");
-  HIPC(ctx->a2_boff.ensure(sizeof(int64_t) * n), "hipMalloc");
-  std::vector<int32_t> all;
-  all.reserve((size_t)n);
-  int32_t counts[2 * kA2Bins] = {}, list_off[kA2Bins];
-  std::vector<std::pair<int64_t, int>> order;  // bins by total rows, largest first
-  for (int b = 0; b < kA2Bins; ++b) {
-    // longest target first inside a bin (rows ~ tlen): the last claims are the short tasks
-    std::stable_sort(lists[b].begin(), lists[b].end(),
-                     [&](int32_t x, int32_t y) { return tasks[x].tlen > tasks[y].tlen; });
-    counts[b] = (int32_t)lists[b].size();
-    list_off[b] = (int32_t)all.size();
-    all.insert(all.end(), lists[b].begin(), lists[b].end());
-    int64_t rows = 0;
-    for (int32_t k : lists[b]) rows += tasks[k].tlen;
-    if (counts[b]) order.push_back({rows * kA2CD[b % kA2Buckets], b});
-  }
-  std::sort(order.begin(), order.end(), [](const std::pair<int64_t, int>& x, const std::pair<int64_t, int>& y) {
-    return x.first > y.first;
-  });
-  std::vector<int> bins;
-  for (auto& o : order) bins.push_back(o.second);
-  int32_t* d_counts = ctx->a2_counts.as<int32_t>();
-  int64_t* d_stats = (int64_t*)(d_counts + 2 * kA2Bins);
-  HIPC(hipMemcpyAsync(ctx->a2_tasks.p, tasks, sizeof(bwagpu_align2_task_t) * n, hipMemcpyHostToDevice, st), "H2D");
-  if (qpool_len) HIPC(hipMemcpyAsync(ctx->a2_q.p, qpool, (size_t)qpool_len, hipMemcpyHostToDevice, st), "H2D");
-  if (tpool_len) HIPC(hipMemcpyAsync(ctx->a2_t.p, tpool, (size_t)tpool_len, hipMemcpyHostToDevice, st), "H2D");
-  HIPC(hipMemcpyAsync(ctx->a2_lists.p, all.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, st), "H2D");
-  HIPC(hipMemcpyAsync(d_counts, counts, sizeof(counts), hipMemcpyHostToDevice, st), "H2D");  // + zero cursors
-  HIPC(hipMemsetAsync(d_stats, 0, sizeof(int64_t) * ST_N, st), "memset");
-  HIPC(hipMemcpyAsync(ctx->a2_boff.p, boff.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice, st), "H2D");
-  EventPair ev;  // own events: slot 0's may time an in-flight chain2aln batch
-  HIPC(ev.start(st), "event");
-  {
-    A2Args base{ctx->a2_tasks.as<bwagpu_align2_task_t>(), ctx->a2_q.as<uint8_t>(), ctx->a2_t.as<uint8_t>(),
-                ctx->a2_out.as<bwagpu_kswr_t>(), ctx->a2_scratch.as<int2>(), ctx->a2_boff.as<int64_t>(),
-                ctx->a2_lists.as<int32_t>(), nullptr, nullptr, d_stats};
-    const int rc = launch_align2_concurrent(ctx, st, bins, base, list_off, counts, d_counts, d_counts + kA2Bins, 0);
-    if (rc) return rc;
-  }
-  HIPC(ev.stop(st), "event");
-  int64_t hs[ST_N];
-  HIPC(hipMemcpyAsync(results, ctx->a2_out.p, sizeof(bwagpu_kswr_t) * n, hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipMemcpyAsync(hs, d_stats, sizeof(hs), hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipStreamSynchronize(st), "align2 batch");
-  s.last = bwagpu_stats_t{};
-  s.last.kernel_ms = ev.ms();
-  s.last.cells = hs[ST_CELLS];
-  s.last.rows = hs[ST_ROWS];
-  s.last.ext_calls = hs[ST_CALLS];
-  return BWAGPU_OK;
-}
-
-int bwagpu_align2_device(bwagpu_ctx_t* ctx, int32_t n, const bwagpu_align2_task_t* dev_tasks,
-                         const uint8_t* dev_qpool, const uint8_t* dev_tpool, bwagpu_kswr_t* dev_results,
-                         void* dev_scratch, void* stream) {
-  if (!ctx || n < 0 || (n && (!dev_tasks || !dev_results || !dev_scratch))) return BWAGPU_E_INVAL;
-  if (n == 0) return BWAGPU_OK;
-  if (const char* why = align2_opt_unsupported(ctx->opt)) return fail(ctx, BWAGPU_E_UNSUPPORTED, why);
-  hipStream_t st = nullptr;
-  if (int rc = entry_stream(ctx, stream, &st)) return rc;
-  HIPC(ctx->a2_lists.ensure(sizeof(int32_t) * (size_t)kA2Bins * n), "hipMalloc");
-  HIPC(ctx->a2_boff.ensure(sizeof(int64_t) * n), "hipMalloc");
-  // counts[kA2Bins] | cursors[kA2Bins] | scratch cursor (u64) | stats[ST_N]
-  const size_t cbytes = sizeof(int32_t) * 2 * kA2Bins + sizeof(int64_t) * (1 + ST_N);
-  HIPC(ctx->a2_counts.ensure(cbytes), "hipMalloc");
-  int32_t* d_counts = ctx->a2_counts.as<int32_t>();
-  unsigned long long* cursor = (unsigned long long*)(d_counts + 2 * kA2Bins);
-  int64_t* d_stats = (int64_t*)(cursor + 1);
-  HIPC(hipMemsetAsync(d_counts, 0, cbytes, st), "memset");
-  HIPC(launch_align2_bins(dev_tasks, n, ctx->a2_lists.as<int32_t>(), d_counts, ctx->a2_boff.as<int64_t>(), cursor,
-                          dev_results, d_stats, st),
-       "align2 bin launch");
-  // counts are on the device only: every bin's kernel is launched with a
-  // resident-capacity grid; an empty bin's waves exit on their first claim
-  std::vector<int> bins;
-  for (int b : {2, 3, 10, 11, 1, 9, 0, 8, 4, 12, 5, 13, 6, 14, 7, 15}) bins.push_back(b);
-  A2Args base{dev_tasks, dev_qpool, dev_tpool, dev_results, (int2*)dev_scratch, ctx->a2_boff.as<int64_t>(),
-              ctx->a2_lists.as<int32_t>(), nullptr, nullptr, d_stats};
-  return launch_align2_concurrent(ctx, st, bins, base, nullptr, nullptr, d_counts, d_counts + kA2Bins, (size_t)n);
-}
-
 int bwagpu_debug_set_trace(bwagpu_ctx_t* ctx, void* dev_ptr) {
   if (!ctx) return BWAGPU_E_INVAL;
   HIPC(hipSetDevice(ctx->device), "hipSetDevice");
@@ -1639,7 +1127,6 @@ int bwagpu_debug_fail_wait(bwagpu_ctx_t* ctx, int after_n_waits, int code) {
   ctx->fail_code = code;
   return BWAGPU_OK;
 }
-
 
 int bwagpu_debug_occupancy(bwagpu_ctx_t* ctx, void* stream, int64_t* out) {
   if (!ctx || !out) return BWAGPU_E_INVAL;
@@ -2055,83 +1542,6 @@ extern "C" int bwagpu_set_device_read_len(bwagpu_ctx_t* ctx, int32_t max_len) {
 extern "C" int bwagpu_debug_sup_shift(bwagpu_ctx_t* ctx, int32_t shift) {
   if (!ctx || shift < 7 || shift > 32) return BWAGPU_E_INVAL;  // a superblock is whole 128-position bwa blocks
   ctx->sup_shift = shift;
-  return BWAGPU_OK;
-}
-
-// The FPGA back end's own job (sw_top, xlnx/XCLAgent.cpp:89-106) on its wire
-// format: the host walks the record chain (one load per read record — the
-// "end" words of packReadData, FPGAPipeline.cpp:258,336) and checks lengths;
-// the device decodes and checks everything else (stream_decode_kernel) and
-// extends every task (stream_ext_kernel).  Device-found problems come back as
-// BWAGPU_E_RESULTS, the fpgaResultsError of processOutput's checks
-// (FPGAPipeline.cpp:38-74).
-extern "C" int bwagpu_sw_stream(bwagpu_ctx_t* ctx, const int32_t* i_buf, int64_t i_words, int16_t* o_buf,
-                                int32_t o_cap_tasks, int32_t* o_tasks) {
-  if (!ctx || !o_tasks || i_words < 0 || o_cap_tasks < 0 || (i_words && !i_buf) || (o_cap_tasks && !o_buf))
-    return BWAGPU_E_INVAL;
-  *o_tasks = 0;
-  if (i_words == 0) return BWAGPU_OK;
-  std::vector<int64_t> starts;
-  int lq_max = 1;
-  for (int64_t p = 0; p < i_words;) {
-    const int64_t end = i_buf[p];
-    if (end <= p + 2 || end > i_words) return fail(ctx, BWAGPU_E_INVAL, "stream: a record's end word is out of range");
-    const int lq = i_buf[p + 1];
-    if (lq < 0) return fail(ctx, BWAGPU_E_INVAL, "stream: negative read length");
-    if (lq > BWAGPU_MAX_READ_LEN) return fail(ctx, BWAGPU_E_UNSUPPORTED, "stream: read longer than BWAGPU_MAX_READ_LEN");
-    lq_max = std::max(lq_max, lq);
-    starts.push_back(p);
-    p = end;
-  }
-  const int tb = tb_bytes_for(ctx->opt, lq_max);
-  if ((size_t)(kBlock / 64) * 2 * tb > 64 * 1024)
-    return fail(ctx, BWAGPU_E_UNSUPPORTED, "LDS row buffer too large for these options (w, pen_clip, read length)");
-  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
-  hipStream_t st = nullptr;
-  HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
-  const size_t cap = (size_t)std::max(o_cap_tasks, 1), nr = starts.size();
-  HIPC(ctx->st_buf.ensure(sizeof(int32_t) * (size_t)i_words), "hipMalloc");
-  HIPC(ctx->st_start.ensure(sizeof(int64_t) * nr), "hipMalloc");
-  HIPC(ctx->st_q.ensure(8 * (size_t)i_words), "hipMalloc");
-  HIPC(ctx->st_tasks.ensure(sizeof(StreamTask) * cap), "hipMalloc");
-  HIPC(ctx->st_lists.ensure(sizeof(int32_t) * kSpecBins * cap), "hipMalloc");
-  HIPC(ctx->st_seen.ensure(sizeof(int32_t) * cap), "hipMalloc");
-  HIPC(ctx->st_ctr.ensure(sizeof(int32_t) * kStrCtrWords), "hipMalloc");
-  HIPC(ctx->st_out.ensure(sizeof(int32_t) * 5 * cap), "hipMalloc");
-  HIPC(hipMemcpyAsync(ctx->st_buf.p, i_buf, sizeof(int32_t) * (size_t)i_words, hipMemcpyHostToDevice, st), "H2D");
-  HIPC(hipMemcpyAsync(ctx->st_start.p, starts.data(), sizeof(int64_t) * nr, hipMemcpyHostToDevice, st), "H2D");
-  HIPC(hipMemsetAsync(ctx->st_seen.p, 0, sizeof(int32_t) * cap, st), "memset");
-  HIPC(hipMemsetAsync(ctx->st_ctr.p, 0, sizeof(int32_t) * kStrCtrWords, st), "memset");
-  StreamArgs a;
-  a.buf = ctx->st_buf.as<int32_t>();
-  a.rstart = ctx->st_start.as<int64_t>();
-  a.n_reads = (int32_t)nr;
-  a.cap = (int32_t)cap;
-  a.l_pac = ctx->ref.l_pac;
-  a.qpool = ctx->st_q.as<uint8_t>();
-  a.tasks = ctx->st_tasks.as<StreamTask>();
-  a.lists = ctx->st_lists.as<int32_t>();
-  a.seen = ctx->st_seen.as<int32_t>();
-  a.ctr = ctx->st_ctr.as<int32_t>();
-  a.out = ctx->st_out.as<int32_t>();
-  if (o_cap_tasks == 0) a.cap = 0;  // every task index is then out of range
-  HIPC(launch_sw_stream(ctx->opt, ctx->ref, a, tb, st), "sw_stream launch");
-  int32_t c[8];
-  HIPC(hipMemcpyAsync(c, ctx->st_ctr.p, sizeof c, hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipStreamSynchronize(st), "sync");
-  if (c[kStrErr]) {
-    const int e = c[kStrErr];
-    return fail(ctx, BWAGPU_E_RESULTS,
-                std::string("stream: ") + (e & STR_ERR_RECORD ? "a record does not end at its end word; " : "") +
-                    (e & STR_ERR_TASK ? "task index out of range; " : "") +
-                    (e & STR_ERR_DUP ? "task index repeated; " : "") +
-                    (e & STR_ERR_SEED ? "seed outside its read or window; " : "") +
-                    (e & STR_ERR_BASE ? "base > 4; " : ""));
-  }
-  if (c[kStrDecoded] != c[kStrMax]) return fail(ctx, BWAGPU_E_RESULTS, "stream: task indices are not 0..n-1");
-  const int32_t n = c[kStrMax];
-  if (n) HIPC(hipMemcpy(o_buf, ctx->st_out.p, sizeof(int32_t) * 5 * (size_t)n, hipMemcpyDeviceToHost), "D2H");
-  *o_tasks = n;
   return BWAGPU_OK;
 }
 

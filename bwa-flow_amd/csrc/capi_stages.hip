@@ -20,11 +20,6 @@
 
 using namespace bwagpu;
 
-#define TRY(call)                   \
-  do {                              \
-    if (int rc_ = (call)) return rc_; \
-  } while (0)
-
 // the post-processing pass over read spans in device memory (regpost.hip)
 int bwagpu::enqueue_regpost(bwagpu_ctx_t* ctx, const bwagpu_postopt_t& po, int32_t flags, int64_t id0, int32_t n_reads,
                             const int64_t* seq_off, const uint8_t* seq, const int64_t* reg_off, const int32_t* rco,

@@ -1,0 +1,387 @@
+// capi_tasks.hip — the entries that take a list of tasks or a wire stream.  A blocking one
+// (but reg2aln_batch: DESIGN.md §19) is its plan (task_host.h), then HostCall (ctx.h).  The plan is
+// declared first, so it outlives every copy out of it: an entry that gives up
+// half way leaves through HostCall's destructor, which synchronises.  The
+// lists, counts, boff, starts and stats words are bookkeeping: plain copies.
+#include <hip/hip_runtime.h>
+
+#include "align2.h"
+#include "ctx.h"
+#include "engine.h"
+#include "reg2aln.h"
+
+using namespace bwagpu;
+
+namespace {
+
+// ksw_qinit's profile (ksw.c:69-108) as v_perm byte pools, see A2Prof
+A2Prof make_a2prof(const DevOpt& o, bool u8) {
+  int mn = 127, mx = 0;
+  for (int i = 0; i < 25; ++i) {
+    mn = std::min<int>(mn, o.mat[i]);
+    mx = std::max<int>(mx, o.mat[i]);
+  }
+  const int shift = (256 - (mn & 0xff)) & 0xff;
+  const int bias = u8 ? shift : 128;
+  A2Prof P{};
+  P.shift = shift, P.qmax = mx, P.e_del = o.e_del, P.oe_del = o.oe_del, P.e_ins = o.e_ins, P.oe_ins = o.oe_ins;
+  for (int t = 0; t < 5; ++t) {
+    uint32_t lo = 0;
+    for (int q = 0; q < 4; ++q) lo |= (uint32_t)(uint8_t)(o.mat[t * 5 + q] + bias) << (8 * q);
+    P.lo[t] = lo;
+    P.hi[t] = (uint32_t)(uint8_t)(o.mat[t * 5 + 4] + bias) | (uint32_t)(uint8_t)bias << 8;
+  }
+  return P;
+}
+
+// Launch the given bins concurrently: fork the side streams off `st`, deal the
+// bins (in the given order) round-robin over them, join back.
+// counts_host: task count per bin when known (0 = unknown -> grid = capacity).
+int launch_align2_concurrent(bwagpu_ctx_t* ctx, hipStream_t st, const std::vector<int>& bins, const A2Args& base,
+                             const int32_t* list_off, const int32_t* counts_host, int32_t* d_counts,
+                             int32_t* d_cursors, size_t list_stride) {
+  int used = 0;
+  if (int rc = side_fork(ctx, st, bins.size(), &used)) return rc;
+  for (size_t k = 0; k < bins.size(); ++k) {
+    const int b = bins[k];
+    A2Args a = base;
+    a.list = base.list + (list_off ? list_off[b] : (size_t)b * list_stride);
+    a.count = d_counts + b;
+    a.cursor = d_cursors + b;
+    HIPC(launch_align2(b, a, make_a2prof(ctx->opt, b >= kA2Buckets), counts_host ? counts_host[b] : 0,
+                       ctx->a2_st[k % used]),
+         "align2 launch");
+  }
+  return side_join(ctx, st, used);
+}
+
+}  // namespace
+
+extern "C" {
+
+int bwagpu_extend_batch(bwagpu_ctx_t* ctx, int32_t n, const bwagpu_ext_task_t* tasks, const uint8_t* qpool,
+                        int64_t qpool_len, const uint8_t* tpool, int64_t tpool_len, bwagpu_ext_result_t* results) {
+  if (!ctx) return BWAGPU_E_INVAL;
+  ExtendPlan plan;
+  const char* why = "";
+  if (int rc = extend_plan(ctx->opt, ctx->ext_form == 0, n, tasks, qpool, qpool_len, tpool, tpool_len, results, &plan,
+                           &why))
+    return refuse(ctx, rc, why);
+  if (n == 0) return BWAGPU_OK;
+  HostCall h(ctx);
+  TRY(h.begin());
+  hipStream_t st = h.st;
+  TRY(h.up(ctx->ex_tasks, tasks, sizeof(bwagpu_ext_task_t) * n));
+  TRY(h.up(ctx->ex_q, qpool, (size_t)qpool_len, 1));
+  TRY(h.up(ctx->ex_t, tpool, (size_t)tpool_len, 1));
+  TRY(h.reserve(ctx->ex_list, sizeof(int32_t) * n));
+  TRY(h.reserve(ctx->ex_res, sizeof(bwagpu_ext_result_t) * n));
+  TRY(h.reserve(ctx->ex_stats, sizeof(int64_t) * ST_N));
+  HIPC(hipMemcpyAsync(ctx->ex_list.p, plan.all.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, st), "H2D");
+  HIPC(hipMemsetAsync(ctx->ex_stats.p, 0, sizeof(int64_t) * ST_N, st), "memset");
+  TRY(h.start());
+  for (int v = 0; v < kExtLists; ++v) {
+    if (!plan.count[v]) continue;
+    const int32_t* list = ctx->ex_list.as<int32_t>() + plan.off[v];
+    HIPC(v < kNumExtVariants
+             ? launch_extend(v, plan.t5, ctx->opt, n, ctx->ex_tasks.as<bwagpu_ext_task_t>(), list, plan.count[v],
+                             ctx->ex_q.as<uint8_t>(), ctx->ex_t.as<uint8_t>(), plan.tb[v],
+                             ctx->ex_res.as<bwagpu_ext_result_t>(), ctx->ex_stats.as<int64_t>(), st)
+             : launch_extend4(ctx->opt, ctx->ex_tasks.as<bwagpu_ext_task_t>(), list, plan.count[v],
+                              ctx->ex_q.as<uint8_t>(), ctx->ex_t.as<uint8_t>(), plan.tb[v],
+                              ctx->ex_res.as<bwagpu_ext_result_t>(), ctx->ex_stats.as<int64_t>(), st),
+         "extend launch");
+  }
+  TRY(h.stop());
+  TRY(h.down(results, ctx->ex_res, sizeof(bwagpu_ext_result_t) * n));
+  return h.finish("extend batch", ctx->ex_stats.as<int64_t>());
+}
+
+int bwagpu_reg2aln_batch(bwagpu_ctx_t* ctx, int32_t n, const bwagpu_reg2aln_task_t* tasks, const uint8_t* qpool,
+                         int64_t qpool_len, int32_t max_ops, int32_t max_md, bwagpu_aln_t* out, uint32_t* cigar,
+                         char* md) {
+  if (!ctx || n < 0 || (n && (!tasks || !out || !cigar || !md)) || qpool_len < 0 || (qpool_len && !qpool) ||
+      max_ops < 1 || max_md < 1)
+    return BWAGPU_E_INVAL;
+  if (n == 0) return BWAGPU_OK;
+  const DevOpt& o = ctx->opt;
+  const int64_t l_pac = ctx->ref.l_pac, two = l_pac << 1;
+  const int wmax = o.w << 2;
+  // validate; bin by [query bucket][matrix class 0 LDS small, 1 LDS large, 2 HBM]
+  struct Bin {
+    std::vector<int32_t> ids;
+    int qmax = 0, rmax = 0;
+    int64_t zmax = 0;
+  };
+  Bin bins[kR2Buckets][3];
+  std::vector<int64_t> cost((size_t)n, 0);
+  for (int32_t k = 0; k < n; ++k) {
+    const bwagpu_reg2aln_task_t& t = tasks[k];
+    if (t.l_seq < 0 || t.qoff < 0 || t.qoff > qpool_len - t.l_seq)
+      return fail(ctx, BWAGPU_E_INVAL, "job's read outside the query pool");
+    int lq = 0, rl = 0, cls = 0;
+    int64_t zb = 0;
+    if (t.rb >= 0 && t.re >= 0) {
+      const int64_t beg = t.rb, end = t.re > two ? two : t.re;
+      const bool ok = t.qe > t.qb && t.rb < t.re && !(t.rb < l_pac && t.re > l_pac) &&
+                      (beg >= l_pac || end <= l_pac) && end - beg == t.re - t.rb;
+      if (ok) {
+        if (t.qb < 0 || t.qe > t.l_seq) return fail(ctx, BWAGPU_E_INVAL, "job's qb/qe outside its read");
+        lq = t.qe - t.qb;
+        if (lq > BWAGPU_MAX_READ_LEN) return fail(ctx, BWAGPU_E_UNSUPPORTED, "qe - qb > BWAGPU_MAX_READ_LEN");
+        if (t.re - t.rb > kR2MaxRef) return fail(ctx, BWAGPU_E_UNSUPPORTED, "re - rb > 8192");
+        rl = (int)(t.re - t.rb);
+        // the widest band any try can use: the first try's w2 (infer_bw,
+        // bwamem.c:1123-1126) doubled at most twice (1132), capped at
+        // opt->w << 2, then bwa.c:152-159
+        auto infer = [&](int q_, int r_) {
+          if (lq == rl && lq * o.a - t.truesc < (q_ + r_ - o.a) * 2) return 0;
+          const int w = (int)((double)(std::min(lq, rl) * o.a - t.truesc - q_) / r_ + 2.);
+          return std::max(w, std::abs(lq - rl));
+        };
+        int w2 = std::max(infer(o.o_del, o.e_del), infer(o.o_ins, o.e_ins));
+        if (w2 > o.w) w2 = std::min(w2, t.w);
+        w2 = std::min(w2, wmax);
+        const int w2max = (int)std::min<int64_t>((int64_t)w2 * 4, wmax);
+        const int half = (lq + 1) >> 1;
+        const int mi = (int)((double)(half * o.mat[0] - o.o_ins) / o.e_ins + 1.);
+        const int mdl = (int)((double)(half * o.mat[0] - o.o_del) / o.e_del + 1.);
+        const int mg = std::max(std::max(mi, mdl), 1), dl = std::abs(rl - lq);
+        const int wb = std::max(std::min((mg + dl + 1) >> 1, w2max), dl + 3);
+        zb = (int64_t)std::min(lq, 2 * wb + 1) * rl;
+        cls = zb <= kR2ZSmall ? 0 : (zb <= kR2ZLarge ? 1 : 2);
+      }
+    }
+    Bin& b = bins[r2_bucket_of(lq)][cls];
+    b.ids.push_back(k);
+    b.qmax = std::max(b.qmax, lq);
+    b.rmax = std::max(b.rmax, rl);
+    b.zmax = std::max(b.zmax, zb);
+    cost[(size_t)k] = zb + lq + rl;
+  }
+  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
+  hipStream_t st = nullptr;
+  HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
+  HIPC(ctx->r2_tasks.ensure(sizeof(bwagpu_reg2aln_task_t) * n), "hipMalloc");
+  HIPC(ctx->r2_q.ensure((size_t)qpool_len + 1), "hipMalloc");
+  HIPC(ctx->r2_out.ensure(sizeof(bwagpu_aln_t) * n), "hipMalloc");
+  HIPC(ctx->r2_cig.ensure(sizeof(uint32_t) * (size_t)n * max_ops), "hipMalloc");
+  HIPC(ctx->r2_md.ensure((size_t)n * max_md), "hipMalloc");
+  HIPC(ctx->r2_lists.ensure(sizeof(int32_t) * n), "hipMalloc");
+  HIPC(ctx->r2_stats.ensure(sizeof(int64_t) * ST_N), "hipMalloc");
+  std::vector<int32_t> all;
+  all.reserve((size_t)n);
+  for (auto& row : bins)
+    for (auto& b : row) {
+      // largest matrices first: the last claims are the small jobs
+      std::stable_sort(b.ids.begin(), b.ids.end(), [&](int32_t x, int32_t y) { return cost[x] > cost[y]; });
+      all.insert(all.end(), b.ids.begin(), b.ids.end());
+    }
+  HIPC(hipMemcpyAsync(ctx->r2_tasks.p, tasks, sizeof(bwagpu_reg2aln_task_t) * n, hipMemcpyHostToDevice, st), "H2D");
+  if (qpool_len) HIPC(hipMemcpyAsync(ctx->r2_q.p, qpool, (size_t)qpool_len, hipMemcpyHostToDevice, st), "H2D");
+  HIPC(hipMemcpyAsync(ctx->r2_lists.p, all.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, st), "H2D");
+  HIPC(hipMemsetAsync(ctx->r2_stats.p, 0, sizeof(int64_t) * ST_N, st), "memset");
+  // bins run concurrently on the context's side streams, largest first
+  struct Launch { int bk, cls; int32_t off; int64_t work; };
+  std::vector<Launch> launches;
+  int32_t off = 0;
+  for (int bk = 0; bk < kR2Buckets; ++bk)
+    for (int cls = 0; cls < 3; ++cls) {
+      const Bin& b = bins[bk][cls];
+      if (b.ids.empty()) continue;
+      int64_t w = 0;
+      for (int32_t k : b.ids) w += cost[(size_t)k];
+      launches.push_back({bk, cls, off, w});
+      off += (int32_t)b.ids.size();
+    }
+  std::sort(launches.begin(), launches.end(), [](const Launch& x, const Launch& y) { return x.work > y.work; });
+  EventPair ev;
+  HIPC(ev.start(st), "event");
+  int used = 0;
+  TRY(side_fork(ctx, st, launches.size(), &used));
+  auto make_args = [&](const Launch& L, int& wpb) {
+    const Bin& b = bins[L.bk][L.cls];
+    R2AArgs a{};
+    a.tasks = ctx->r2_tasks.as<bwagpu_reg2aln_task_t>(), a.qpool = ctx->r2_q.as<uint8_t>();
+    a.list = ctx->r2_lists.as<int32_t>() + L.off, a.n = (int)b.ids.size(), a.max_ops = max_ops, a.max_md = max_md;
+    a.out = ctx->r2_out.as<bwagpu_aln_t>(), a.cigar = ctx->r2_cig.as<uint32_t>(), a.md = ctx->r2_md.as<char>();
+    a.stats = ctx->r2_stats.as<int64_t>();
+    a.qcap = (b.qmax + 16) & ~15;
+    a.rcap = (b.rmax + 16) & ~15;
+    a.ocap = a.qcap + a.rcap + 4;
+    int lpw = a.qcap + a.rcap + 4 * a.ocap;
+    if (L.cls < 2) lpw += L.cls == 0 ? kR2ZSmall : kR2ZLarge;
+    a.lds_per_wave = (lpw + 15) & ~15;
+    wpb = L.cls == 1 ? 1 : 4;  // LDS-heavy bins: one wave per workgroup packs LDS finer
+    a.zstride = L.cls == 2 ? ((b.zmax + 255) & ~(int64_t)255) : 0;
+    return a;
+  };
+  // grids first (HBM matrix slices: one per launched wave, at most 1 GiB per bin)
+  size_t zoff = 0;
+  for (Launch& L : launches) {
+    int wpb = 4;
+    const R2AArgs a = make_args(L, wpb);
+    if ((size_t)wpb * a.lds_per_wave > 160 * 1024)
+      return fail(ctx, BWAGPU_E_UNSUPPORTED, "reg2aln job needs more LDS than a workgroup has");
+    int waves = r2_resident_waves(kR2CD[L.bk], (size_t)wpb * a.lds_per_wave, wpb);
+    if (L.cls == 2) {
+      waves = (int)std::min<int64_t>(waves, std::max<int64_t>(4, ((int64_t)1 << 30) / a.zstride));
+      zoff += (size_t)a.zstride * waves;
+    }
+    L.work = waves;
+  }
+  HIPC(ctx->r2_z.ensure(std::max<size_t>(zoff, 256)), "hipMalloc(reg2aln matrices)");
+  zoff = 0;
+  for (size_t li = 0; li < launches.size(); ++li) {
+    const Launch& L = launches[li];
+    int wpb = 4;
+    R2AArgs a = make_args(L, wpb);
+    const int nb = a.n, waves = (int)L.work;
+    if (L.cls == 2) {
+      a.zglob = ctx->r2_z.as<uint8_t>() + zoff;
+      zoff += (size_t)a.zstride * waves;
+    }
+    const int blocks = std::max(1, std::min((nb + wpb - 1) / wpb, waves / wpb));
+    HIPC(launch_reg2aln(kR2CD[L.bk], o, ctx->ref, a, blocks, wpb, ctx->a2_st[li % used]), "reg2aln launch");
+  }
+  TRY(side_join(ctx, st, used));
+  HIPC(ev.stop(st), "event");
+  HIPC(hipMemcpyAsync(out, ctx->r2_out.p, sizeof(bwagpu_aln_t) * n, hipMemcpyDeviceToHost, st), "D2H");
+  HIPC(hipMemcpyAsync(cigar, ctx->r2_cig.p, sizeof(uint32_t) * (size_t)n * max_ops, hipMemcpyDeviceToHost, st), "D2H");
+  HIPC(hipMemcpyAsync(md, ctx->r2_md.p, (size_t)n * max_md, hipMemcpyDeviceToHost, st), "D2H");
+  int64_t hst[ST_N];
+  HIPC(hipMemcpyAsync(hst, ctx->r2_stats.p, sizeof(hst), hipMemcpyDeviceToHost, st), "D2H");
+  HIPC(hipStreamSynchronize(st), "reg2aln execution");
+  bwagpu_stats_t& last = ctx->slot[0].last = bwagpu_stats_t{};
+  last.kernel_ms = ev.ms(), last.cells = hst[ST_CELLS], last.rows = hst[ST_ROWS], last.ext_calls = hst[ST_CALLS];
+  last.h2d_bytes = (int64_t)sizeof(bwagpu_reg2aln_task_t) * n + qpool_len;
+  last.d2h_bytes = (int64_t)n * ((int64_t)sizeof(bwagpu_aln_t) + 4 * (int64_t)max_ops + max_md);
+  return BWAGPU_OK;
+}
+
+int bwagpu_align2_batch(bwagpu_ctx_t* ctx, int32_t n, const bwagpu_align2_task_t* tasks, const uint8_t* qpool,
+                        int64_t qpool_len, const uint8_t* tpool, int64_t tpool_len, bwagpu_kswr_t* results) {
+  if (!ctx) return BWAGPU_E_INVAL;
+  Align2Plan plan;
+  const char* why = "";
+  if (int rc = align2_plan(ctx->opt, n, tasks, qpool, qpool_len, tpool, tpool_len, results, &plan, &why))
+    return refuse(ctx, rc, why);
+  if (n == 0) return BWAGPU_OK;
+  HostCall h(ctx);
+  TRY(h.begin());
+  hipStream_t st = h.st;
+  TRY(h.up(ctx->a2_tasks, tasks, sizeof(bwagpu_align2_task_t) * n));
+  TRY(h.up(ctx->a2_q, qpool, (size_t)qpool_len, 1));
+  TRY(h.up(ctx->a2_t, tpool, (size_t)tpool_len, 1));
+  TRY(h.reserve(ctx->a2_out, sizeof(bwagpu_kswr_t) * n));
+  TRY(h.reserve(ctx->a2_scratch, sizeof(int2) * (size_t)plan.scratch));
+  TRY(h.reserve(ctx->a2_lists, sizeof(int32_t) * n));
+  // counts[kA2Bins] | cursors[kA2Bins] | stats[ST_N]
+  TRY(h.reserve(ctx->a2_counts, sizeof(int32_t) * 2 * kA2Bins + sizeof(int64_t) * ST_N));
+  TRY(h.reserve(ctx->a2_boff, sizeof(int64_t) * n));
+  int32_t* d_counts = ctx->a2_counts.as<int32_t>();
+  int64_t* d_stats = (int64_t*)(d_counts + 2 * kA2Bins);
+  HIPC(hipMemcpyAsync(ctx->a2_lists.p, plan.all.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, st), "H2D");
+  HIPC(hipMemcpyAsync(d_counts, plan.counts, sizeof plan.counts, hipMemcpyHostToDevice, st), "H2D");  // + zero cursors
+  HIPC(hipMemsetAsync(d_stats, 0, sizeof(int64_t) * ST_N, st), "memset");
+  HIPC(hipMemcpyAsync(ctx->a2_boff.p, plan.boff.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice, st), "H2D");
+  TRY(h.start());
+  const A2Args base{ctx->a2_tasks.as<bwagpu_align2_task_t>(), ctx->a2_q.as<uint8_t>(), ctx->a2_t.as<uint8_t>(),
+                    ctx->a2_out.as<bwagpu_kswr_t>(), ctx->a2_scratch.as<int2>(), ctx->a2_boff.as<int64_t>(),
+                    ctx->a2_lists.as<int32_t>(), nullptr, nullptr, d_stats};
+  TRY(launch_align2_concurrent(ctx, st, plan.bins, base, plan.list_off, plan.counts, d_counts, d_counts + kA2Bins, 0));
+  TRY(h.stop());
+  TRY(h.down(results, ctx->a2_out, sizeof(bwagpu_kswr_t) * n));
+  return h.finish("align2 batch", d_stats);
+}
+
+int bwagpu_align2_device(bwagpu_ctx_t* ctx, int32_t n, const bwagpu_align2_task_t* dev_tasks,
+                         const uint8_t* dev_qpool, const uint8_t* dev_tpool, bwagpu_kswr_t* dev_results,
+                         void* dev_scratch, void* stream) {
+  if (!ctx || n < 0 || (n && (!dev_tasks || !dev_results || !dev_scratch))) return BWAGPU_E_INVAL;
+  if (n == 0) return BWAGPU_OK;
+  if (const char* why = align2_opt_unsupported(ctx->opt)) return fail(ctx, BWAGPU_E_UNSUPPORTED, why);
+  hipStream_t st = nullptr;
+  if (int rc = entry_stream(ctx, stream, &st)) return rc;
+  HIPC(ctx->a2_lists.ensure(sizeof(int32_t) * (size_t)kA2Bins * n), "hipMalloc");
+  HIPC(ctx->a2_boff.ensure(sizeof(int64_t) * n), "hipMalloc");
+  // counts[kA2Bins] | cursors[kA2Bins] | scratch cursor (u64) | stats[ST_N]
+  const size_t cbytes = sizeof(int32_t) * 2 * kA2Bins + sizeof(int64_t) * (1 + ST_N);
+  HIPC(ctx->a2_counts.ensure(cbytes), "hipMalloc");
+  int32_t* d_counts = ctx->a2_counts.as<int32_t>();
+  unsigned long long* cursor = (unsigned long long*)(d_counts + 2 * kA2Bins);
+  int64_t* d_stats = (int64_t*)(cursor + 1);
+  HIPC(hipMemsetAsync(d_counts, 0, cbytes, st), "memset");
+  HIPC(launch_align2_bins(dev_tasks, n, ctx->a2_lists.as<int32_t>(), d_counts, ctx->a2_boff.as<int64_t>(), cursor,
+                          dev_results, d_stats, st),
+       "align2 bin launch");
+  // counts are on the device only: every bin's kernel is launched with a
+  // resident-capacity grid; an empty bin's waves exit on their first claim
+  const std::vector<int> bins{2, 3, 10, 11, 1, 9, 0, 8, 4, 12, 5, 13, 6, 14, 7, 15};
+  A2Args base{dev_tasks, dev_qpool, dev_tpool, dev_results, (int2*)dev_scratch, ctx->a2_boff.as<int64_t>(),
+              ctx->a2_lists.as<int32_t>(), nullptr, nullptr, d_stats};
+  return launch_align2_concurrent(ctx, st, bins, base, nullptr, nullptr, d_counts, d_counts + kA2Bins, (size_t)n);
+}
+
+// The FPGA back end's own job (sw_top, xlnx/XCLAgent.cpp:89-106) on its wire
+// format: the host walks the record chain and checks lengths (stream_plan);
+// the device decodes and checks everything else (stream_decode_kernel) and
+// extends every task (stream_ext_kernel).  Device-found problems come back as
+// BWAGPU_E_RESULTS, the fpgaResultsError of processOutput's checks
+// (FPGAPipeline.cpp:38-74).
+int bwagpu_sw_stream(bwagpu_ctx_t* ctx, const int32_t* i_buf, int64_t i_words, int16_t* o_buf, int32_t o_cap_tasks,
+                     int32_t* o_tasks) {
+  if (!ctx || !o_tasks || i_words < 0 || o_cap_tasks < 0 || (i_words && !i_buf) || (o_cap_tasks && !o_buf))
+    return BWAGPU_E_INVAL;
+  *o_tasks = 0;
+  if (i_words == 0) return BWAGPU_OK;
+  StreamPlan plan;
+  const char* why = "";
+  if (int rc = stream_plan(i_buf, i_words, &plan, &why)) return refuse(ctx, rc, why);
+  const int tb = tb_bytes_for(ctx->opt, plan.lq_max);
+  if ((size_t)(kBlock / 64) * 2 * tb > 64 * 1024)
+    return fail(ctx, BWAGPU_E_UNSUPPORTED, "LDS row buffer too large for these options (w, pen_clip, read length)");
+  int32_t c[8];
+  HostCall h(ctx);
+  TRY(h.begin());
+  hipStream_t st = h.st;
+  const size_t cap = (size_t)std::max(o_cap_tasks, 1), nr = plan.starts.size();
+  TRY(h.up(ctx->st_buf, i_buf, sizeof(int32_t) * (size_t)i_words));
+  TRY(h.reserve(ctx->st_start, sizeof(int64_t) * nr));
+  TRY(h.reserve(ctx->st_q, 8 * (size_t)i_words));
+  TRY(h.reserve(ctx->st_tasks, sizeof(StreamTask) * cap));
+  TRY(h.reserve(ctx->st_lists, sizeof(int32_t) * kSpecBins * cap));
+  TRY(h.reserve(ctx->st_seen, sizeof(int32_t) * cap));
+  TRY(h.reserve(ctx->st_ctr, sizeof(int32_t) * kStrCtrWords));
+  TRY(h.reserve(ctx->st_out, sizeof(int32_t) * 5 * cap));
+  HIPC(hipMemcpyAsync(ctx->st_start.p, plan.starts.data(), sizeof(int64_t) * nr, hipMemcpyHostToDevice, st), "H2D");
+  HIPC(hipMemsetAsync(ctx->st_seen.p, 0, sizeof(int32_t) * cap, st), "memset");
+  HIPC(hipMemsetAsync(ctx->st_ctr.p, 0, sizeof(int32_t) * kStrCtrWords, st), "memset");
+  StreamArgs a{};
+  a.buf = ctx->st_buf.as<int32_t>(), a.rstart = ctx->st_start.as<int64_t>(), a.n_reads = (int32_t)nr;
+  a.cap = o_cap_tasks, a.l_pac = ctx->ref.l_pac;  // cap 0: every task index is then out of range
+  a.qpool = ctx->st_q.as<uint8_t>(), a.tasks = ctx->st_tasks.as<StreamTask>(), a.lists = ctx->st_lists.as<int32_t>();
+  a.seen = ctx->st_seen.as<int32_t>(), a.ctr = ctx->st_ctr.as<int32_t>(), a.out = ctx->st_out.as<int32_t>();
+  TRY(h.start());
+  HIPC(launch_sw_stream(ctx->opt, ctx->ref, a, tb, st), "sw_stream launch");
+  TRY(h.stop());
+  HIPC(hipMemcpyAsync(c, ctx->st_ctr.p, sizeof c, hipMemcpyDeviceToHost, st), "D2H");
+  HIPC(hipStreamSynchronize(st), "sync");  // the counters say how many records come back
+  if (c[kStrErr]) {
+    const int e = c[kStrErr];
+    return fail(ctx, BWAGPU_E_RESULTS,
+                std::string("stream: ") + (e & STR_ERR_RECORD ? "a record does not end at its end word; " : "") +
+                    (e & STR_ERR_TASK ? "task index out of range; " : "") +
+                    (e & STR_ERR_DUP ? "task index repeated; " : "") +
+                    (e & STR_ERR_SEED ? "seed outside its read or window; " : "") +
+                    (e & STR_ERR_BASE ? "base > 4; " : ""));
+  }
+  if (c[kStrDecoded] != c[kStrMax]) return fail(ctx, BWAGPU_E_RESULTS, "stream: task indices are not 0..n-1");
+  const int32_t n = c[kStrMax];
+  TRY(h.down(o_buf, ctx->st_out, sizeof(int32_t) * 5 * (size_t)n));
+  TRY(h.finish("sync"));
+  *o_tasks = n;
+  return BWAGPU_OK;
+}
+
+}  // extern "C"

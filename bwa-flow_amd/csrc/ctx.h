@@ -1,7 +1,7 @@
 // ctx.h — what the translation units of the C ABI share (capi.hip,
-// capi_stages.hip): the context and its slots, grow-only buffers, the error
-// path, and the scaffold of a blocking host-buffer entry.  Internal: nothing
-// here is part of include/bwagpu.h.
+// capi_stages.hip, capi_tasks.hip): the context and its slots, grow-only
+// buffers, the error path, and the scaffold of a blocking host-buffer entry.
+// Internal: nothing here is part of include/bwagpu.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -18,53 +18,33 @@
 #include "rescue.h"
 #include "seed.h"
 #include "stage_host.h"
+#include "task_host.h"
 
 namespace bwagpu {
 
-struct DevBuf {  // grow-only device buffer
+template <bool kPinned>
+struct GrowBuf {  // grow-only device buffer, or pinned host buffer
   void* p = nullptr;
   size_t cap = 0;
   hipError_t ensure(size_t n) {
     if (n <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t want = std::max<size_t>(n + n / 4, 4096);
-    hipError_t e = hipMalloc(&p, want);
+    release();
+    const size_t want = std::max<size_t>(n + n / 4, 4096);
+    const hipError_t e = kPinned ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want);
     if (e == hipSuccess) cap = want;
+    else p = nullptr;
     return e;
   }
   void release() {
-    if (p) (void)hipFree(p);
+    if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p));
     p = nullptr;
     cap = 0;
   }
   template <class T>
   T* as() const { return (T*)p; }
 };
-
-struct HostBuf {  // grow-only pinned host buffer
-  void* p = nullptr;
-  size_t cap = 0;
-  unsigned flags = hipHostMallocDefault;
-  hipError_t ensure(size_t n) {
-    if (n <= cap) return hipSuccess;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t want = std::max<size_t>(n + n / 4, 4096);
-    hipError_t e = hipHostMalloc(&p, want, flags);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <class T>
-  T* as() const { return (T*)p; }
-};
+using DevBuf = GrowBuf<false>;
+using HostBuf = GrowBuf<true>;
 
 struct Slot {
   // created on first use (lazy_stream): the device entry runs on the caller's
@@ -174,6 +154,8 @@ struct bwagpu_ctx {
   // submit/wait path's slots never share scratch with the device entry, so the
   // two entry points may run concurrently on one context
   Slot dev_scratch[BWAGPU_NUM_SLOTS];
+  // bare ksw_extend2 task lists (bwagpu_extend_batch): grow-only, reused across calls
+  DevBuf ex_tasks, ex_list, ex_q, ex_t, ex_res, ex_stats;
   // ksw_align2 batches (bwagpu_align2_*): grow-only, reused across calls
   DevBuf a2_tasks, a2_q, a2_t, a2_out, a2_scratch, a2_lists, a2_counts, a2_boff;
   // mem_reg2aln batches (bwagpu_reg2aln_batch)
@@ -262,22 +244,41 @@ inline int hip_fail(bwagpu_ctx_t* c, hipError_t e, const char* what) {
     hipError_t e_ = (call);                          \
     if (e_ != hipSuccess) return hip_fail(ctx, e_, what); \
   } while (0)
+#define TRY(call)                     \
+  do {                                \
+    if (int rc_ = (call)) return rc_; \
+  } while (0)
 
-// scoring limits of the align2 kernels (reasons are the E_UNSUPPORTED text)
-inline const char* align2_opt_unsupported(const DevOpt& o) {
-  if (o.o_ins <= 0)
-    return "ksw_align2 with o_ins == 0: the reference's lazy-F early exit (ksw.c:180) then depends on "
-           "its SIMD lane order; run it on the CPU";
-  if (o.max_mat <= 0) return "ksw_align2 needs a positive match score (ksw.c:216 divides by it)";
-  if (o.o_ins > 65535 || o.e_ins > 65535 || o.o_del > 65535 || o.e_del > 65535) return "gap penalty > 65535";
-  return nullptr;
-}
+// a plan's refusal (stage_host.h, task_host.h): a bad argument has no text
+inline int refuse(bwagpu_ctx_t* c, int code, const char* why) { return why && *why ? fail(c, code, why) : code; }
 
 // the stream of a _device entry: the caller's, or slot[0]'s when it passes none
 inline int entry_stream(bwagpu_ctx_t* ctx, void* stream, hipStream_t* st) {
   HIPC(hipSetDevice(ctx->device), "hipSetDevice");
   *st = (hipStream_t)stream;
   if (!*st) HIPC(lazy_stream(ctx->slot[0], st), "hipStreamCreate");
+  return BWAGPU_OK;
+}
+
+// The context's side streams (a2_st): the launches of one call run concurrently on up to kA2Streams
+// of them.  side_fork makes `used` = min(kA2Streams, n_launches) of them wait for what `st` holds
+// so far, launch k then goes to a2_st[k % used], and side_join makes `st` wait for them all.
+inline int side_fork(bwagpu_ctx_t* ctx, hipStream_t st, size_t n_launches, int* used) {
+  for (int i = 0; i < bwagpu_ctx::kA2Streams; ++i) {  // created on first use
+    if (!ctx->a2_st[i]) HIPC(hipStreamCreateWithFlags(&ctx->a2_st[i], hipStreamNonBlocking), "stream");
+    if (!ctx->a2_join[i]) HIPC(hipEventCreateWithFlags(&ctx->a2_join[i], hipEventDisableTiming), "event");
+  }
+  if (!ctx->a2_fork) HIPC(hipEventCreateWithFlags(&ctx->a2_fork, hipEventDisableTiming), "event");
+  *used = (int)std::min<size_t>(bwagpu_ctx::kA2Streams, n_launches);
+  HIPC(hipEventRecord(ctx->a2_fork, st), "event");
+  for (int i = 0; i < *used; ++i) HIPC(hipStreamWaitEvent(ctx->a2_st[i], ctx->a2_fork, 0), "stream wait");
+  return BWAGPU_OK;
+}
+inline int side_join(bwagpu_ctx_t* ctx, hipStream_t st, int used) {
+  for (int i = 0; i < used; ++i) {
+    HIPC(hipEventRecord(ctx->a2_join[i], ctx->a2_st[i]), "event");
+    HIPC(hipStreamWaitEvent(st, ctx->a2_join[i], 0), "stream wait");
+  }
   return BWAGPU_OK;
 }
 
@@ -322,7 +323,7 @@ struct HostCall {
   Staging& g;
   hipStream_t st = nullptr;
   EventPair ev;
-  int64_t h2d = 0, d2h = 0;
+  int64_t h2d = 0, d2h = 0, hs[ST_N] = {};
   std::vector<int64_t> roff, soff, ooff;  // rebased offsets: pageable, alive until uploaded()
   bool open = false;                      // between begin() and finish()
 
@@ -339,12 +340,11 @@ struct HostCall {
     open = true;
     return BWAGPU_OK;
   }
-  int reserve(DevBuf& b, size_t bytes) {  // at least one element, so that the kernels get a pointer
-    HIPC(b.ensure(std::max<size_t>(bytes, 1)), "hipMalloc");
-    return BWAGPU_OK;
-  }
-  int up(DevBuf& b, const void* src, size_t bytes) {
-    if (int rc = reserve(b, bytes)) return rc;
+  int done(hipError_t e, const char* what) { return e == hipSuccess ? BWAGPU_OK : hip_fail(ctx, e, what); }
+  // at least one element, so that the kernels get a pointer
+  int reserve(DevBuf& b, size_t bytes) { return done(b.ensure(std::max<size_t>(bytes, 1)), "hipMalloc"); }
+  int up(DevBuf& b, const void* src, size_t bytes, size_t slack = 0) {  // slack: bytes a kernel may read past the end
+    if (int rc = reserve(b, bytes + slack)) return rc;
     if (bytes) HIPC(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st), "H2D");
     h2d += (int64_t)bytes;
     return BWAGPU_OK;
@@ -367,8 +367,7 @@ struct HostCall {
   int up_seq(const StagePlan& plan, size_t nr, const int64_t* seq_off, const uint8_t* seq) {
     soff.resize(nr + 1);
     for (size_t r = 0; r <= nr; ++r) soff[r] = seq_off[r] - plan.seq_lo;
-    if (int rc = reserve(g.seq, (size_t)(plan.seq_hi - plan.seq_lo) + 1)) return rc;
-    if (int rc = up(g.seq, seq + plan.seq_lo, (size_t)(plan.seq_hi - plan.seq_lo))) return rc;
+    if (int rc = up(g.seq, seq + plan.seq_lo, (size_t)(plan.seq_hi - plan.seq_lo), 1)) return rc;
     return up(g.seq_off, soff.data(), sizeof(int64_t) * (nr + 1));
   }
   // the output spans' offsets into out_regs[plan.out_lo, plan.out_hi) -> g.out_off; g.out_regs is reserved
@@ -378,19 +377,11 @@ struct HostCall {
     if (int rc = reserve(g.out_regs, sizeof(bwagpu_alnreg_t) * (size_t)(plan.out_hi - plan.out_lo))) return rc;
     return up(g.out_off, ooff.data(), sizeof(int64_t) * (nr + 1));
   }
-  int uploaded() {  // the sources of the uploads may be pageable locals
-    HIPC(hipStreamSynchronize(st), "H2D");
-    return BWAGPU_OK;
-  }
-  int start() {
-    HIPC(ev.start(st), "event");
-    return BWAGPU_OK;
-  }
-  int stop() {
-    HIPC(ev.stop(st), "event");
-    return BWAGPU_OK;
-  }
-  int finish(const char* what) {
+  int uploaded() { return done(hipStreamSynchronize(st), "H2D"); }  // the sources of the uploads may be pageable locals
+  int start() { return done(ev.start(st), "event"); }
+  int stop() { return done(ev.stop(st), "event"); }
+  int finish(const char* what, const int64_t* d_stats = nullptr) {  // d_stats: the ST_* words the kernels added up
+    if (d_stats) HIPC(hipMemcpyAsync(hs, d_stats, sizeof hs, hipMemcpyDeviceToHost, st), "D2H");
     HIPC(hipStreamSynchronize(st), what);
     open = false;
     bwagpu_stats_t& last = ctx->slot[0].last;
@@ -398,6 +389,9 @@ struct HostCall {
     last.kernel_ms = ev.ms();
     last.h2d_bytes = h2d;
     last.d2h_bytes = d2h;
+    last.cells = hs[ST_CELLS];
+    last.rows = hs[ST_ROWS];
+    last.ext_calls = hs[ST_CALLS];
     return BWAGPU_OK;
   }
 };

@@ -6,22 +6,9 @@
 
 #include "bwagpu.h"
 #include "bwagpu_debug.h"
+#include "pure.h"
 
 namespace bwagpu {
-
-// Scoring parameters in the form the kernels use (from bwagpu_opt_t).
-struct DevOpt {
-  int a, o_del, e_del, o_ins, e_ins, oe_del, oe_ins;
-  int pen_clip5, pen_clip3, w, zdrop, max_mat;
-  int row_bound;  // extend_quad ends a call once no later row can change its outputs
-  int8_t mat[28];
-  // query profile words: qprof[q] byte t = mat[t*5 + q] (t = target base 0..3),
-  // qprof4[q] = mat[20 + q] (target N; only bare task lists can hold one —
-  // targets fetched from the pac are 0..3).  Kernel arguments, so the DP picks
-  // its scores with register selects instead of loads.
-  uint32_t qprof[5];
-  int32_t qprof4[5];
-};
 
 // One read in processing order (chain2aln_fast_kernel), written after the sort.
 struct ReadDesc {
@@ -64,28 +51,16 @@ struct DevRef {
 enum { ST_CELLS = 0, ST_ROWS = 1, ST_CALLS = 2, ST_ERR = 3, ST_N = 4 };
 enum { ERR_RID = 1, ERR_LEN = 2 };
 
-// Kernel variants: G lanes per read ("group"), C = max DP columns per lane.
-// A read of length l needs G*C >= l (+1 column for eh[qlen], qlen <= l-1).
-enum { VK_FAST = 0, VK_GENERIC = 1 };
-struct Variant {
-  int G, C;
-  int kind;  // VK_FAST: chain2aln_fast_kernel (wave per read), VK_GENERIC: chain2aln_kernel
-  __host__ __device__ int max_len() const { return G * C; }
-};
 // limits of the fast kernel: one lane (slot) per seed / chain / region of a read
 constexpr int kFastMaxSeeds = 32;
 constexpr int kFastMaxChains = 32;
 constexpr int kSeqLds = 256;  // LDS bytes for the read's bases (fast variants: lq <= 256)
 constexpr int kNumVariants = 3;
 extern const Variant kVariants[kNumVariants];
-// bare ksw_extend2 task lists (bwagpu_extend_batch): wave kernels by columns
-constexpr int kNumExtVariants = 3;
-extern const Variant kExtVariants[kNumExtVariants];
 // read-order counters: [0..15] per-variant counts, [16 + 8v + xcc] queue heads
 // (generic kernel), [kHistOff ..) the read-order histogram
 constexpr int kHistOff = 128;
 constexpr int kCountWords = kHistOff + kNumVariants * 256;
-constexpr int kBlock = 256;  // threads per workgroup (4 waves)
 
 // host-side launchers (sw_kernels.hip)
 hipError_t launch_chain_prep(const DevOpt& o, const DevRef& ref, const DevBatch& b, ChainWin* win, uint64_t* srt,
@@ -256,20 +231,12 @@ int set_ext_form(int form);
 // (<32,5,true>), 5 = four per wave (<32,8,false>), 2 = two per wave
 // (spec_ext2_kernel<5>)
 int ext_kernel_for(const DevOpt& o, int form, int tb_bytes);
-bool quad_scores_ok(const DevOpt& o, int lq);
-bool quad_bound_ok(const DevOpt& o, long hb);
-bool quad_rows_ok(const DevOpt& o, long rows);
-bool quad_key8_ok(const DevOpt& o, int lq);
-int ext_form();
 hipError_t launch_spec_clear(const SpecArgs& a, int n_reads, int n_seeds, hipStream_t st);
 hipError_t launch_spec_chain2aln(const DevOpt& o, const DevRef& ref, const DevBatch& b, const SpecArgs& a,
                                  int tb_bytes, int lq_max, hipStream_t st, const SpecStreams& ss);
 // LDS bytes per workgroup of the largest spec launch; regions the redo pass
 // holds in LDS for target rows of tb_bytes (must stay > 0)
 size_t spec_select_lds(int tb_bytes);
-// the lane kernel for short extension tasks (spec_extl_kernel): 0 off, 1 before
-// the pair kernel, 2 beside it on the side stream; process-wide; returns the
-// previous mode (mode < 0: query only)
 int spec_redo_cap(int tb_bytes);
 
 // ---------------------------------------------------------------- FPGA wire format
@@ -304,12 +271,5 @@ hipError_t launch_sw_stream(const DevOpt& o, const DevRef& ref, const StreamArgs
 // diagnostics: per-read trace buffer (device pointer, 8 x u32 per read; NULL = off)
 hipError_t set_trace(void* dev_ptr);
 hipError_t set_trace_spec(void* dev_ptr);  // spec.hip's copy of the trace pointer
-
-// rows a task can touch: the band is empty once i - w >= qlen (ksw.c:417-419),
-// so rows i <= qlen + w are the most ever read (the last one only to break)
-__host__ __device__ inline int band_cap(int qlen, int max_mat, int end_bonus, int o, int e) {
-  int l = (int)((double)(qlen * max_mat + end_bonus - o) / e + 1.);
-  return l > 1 ? l : 1;
-}
 
 }  // namespace bwagpu

@@ -1,0 +1,124 @@
+// pure.h — the scoring options, kernel tables and arithmetic that the kernels'
+// launchers and the host-side plans (task_host.h) share.  Plain C++: compiles
+// without HIP.  engine.h, align2.h and reg2aln.h include it.
+#pragma once
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "bwagpu.h"
+
+#ifdef __HIPCC__
+#define BWAGPU_HD __host__ __device__
+#else
+#define BWAGPU_HD
+#endif
+
+namespace bwagpu {
+
+// Scoring parameters in the form the kernels use (from bwagpu_opt_t).
+struct DevOpt {
+  int a, o_del, e_del, o_ins, e_ins, oe_del, oe_ins;
+  int pen_clip5, pen_clip3, w, zdrop, max_mat;
+  int row_bound;  // extend_quad ends a call once no later row can change its outputs
+  int8_t mat[28];
+  // query profile words: qprof[q] byte t = mat[t*5 + q] (t = target base 0..3),
+  // qprof4[q] = mat[20 + q] (target N; only bare task lists can hold one —
+  // targets fetched from the pac are 0..3).  Kernel arguments, so the DP picks
+  // its scores with register selects instead of loads.
+  uint32_t qprof[5];
+  int32_t qprof4[5];
+};
+
+// Kernel variants: G lanes per read ("group"), C = max DP columns per lane.
+// A read of length l needs G*C >= l (+1 column for eh[qlen], qlen <= l-1).
+enum { VK_FAST = 0, VK_GENERIC = 1 };
+struct Variant {
+  int G, C;
+  int kind;  // VK_FAST: chain2aln_fast_kernel (wave per read), VK_GENERIC: chain2aln_kernel
+  BWAGPU_HD constexpr int max_len() const { return G * C; }
+};
+// bare ksw_extend2 task lists (bwagpu_extend_batch): wave kernels by columns
+constexpr int kNumExtVariants = 3;
+inline constexpr Variant kExtVariants[kNumExtVariants] = {{64, 3, VK_FAST}, {64, 4, VK_FAST}, {64, 16, VK_GENERIC}};
+constexpr int kBlock = 256;  // threads per workgroup (4 waves)
+
+// rows a task can touch: the band is empty once i - w >= qlen (ksw.c:417-419),
+// so rows i <= qlen + w are the most ever read (the last one only to break)
+BWAGPU_HD inline int band_cap(int qlen, int max_mat, int end_bonus, int o, int e) {
+  int l = (int)((double)(qlen * max_mat + end_bonus - o) / e + 1.);
+  return l > 1 ? l : 1;
+}
+
+// LDS row-buffer bytes per group for reads up to lq_max (see rows_needed)
+inline int tb_bytes_for(const DevOpt& o, int lq_max) {
+  const int eb = std::max(o.pen_clip5, o.pen_clip3);
+  const int cap = std::max(band_cap(lq_max, o.max_mat, eb, o.o_ins, o.e_ins),
+                           band_cap(lq_max, o.max_mat, eb, o.o_del, o.e_del));
+  const int we = std::min(o.w << 1, cap);
+  const int n = lq_max + we + 2;
+  return (n + 15) & ~15;
+}
+
+// the packed ranges (extend_quad) for reads up to lq: H <= lq * max(mat) < 4096
+// (the row-max key H << KS | c, KS <= 3), H * 2^sk + 128 < 2^15 (2^sk >
+// max(mat)), and the scan values H + 33 * CPL * e_ins < 2^15
+inline bool quad_bound_ok(const DevOpt& o, long hb) {  // hb: a bound on every H of the call
+  if (o.max_mat < 1 || o.max_mat > 15) return false;
+  const int sk = 32 - __builtin_clz((unsigned)o.max_mat);
+  for (int k = 0; k < 25; ++k)
+    if (o.mat[k] < -127 || o.mat[k] > 127) return false;
+  return hb < 4096 && (hb << sk) + 128 < 32768 && hb + 33L * 8 * o.e_ins < 32768 && o.o_del + 128L < 32768 &&
+         o.oe_ins + 128L < 32768 && o.e_del < 32768;
+}
+inline bool quad_scores_ok(const DevOpt& o, int lq) { return quad_bound_ok(o, (long)lq * o.max_mat); }
+// the 8-bit-column row-max key (extend_quad<.., true>): every H of reads up to lq < 256
+inline bool quad_key8_ok(const DevOpt& o, int lq) { return (long)lq * o.max_mat <= 255; }
+// the packed row-end state for calls of up to `rows` target rows: i, |i - j|
+// and the z-drop term max((di - dj) e_del, (dj - di) e_ins) (di <= rows,
+// dj <= 256) within 16 bits beside H < 4096
+inline bool quad_rows_ok(const DevOpt& o, long rows) {
+  return rows >= 0 && rows < 16384 && (rows + 256) * std::max(o.e_del, o.e_ins) < 28672;
+}
+
+// ksw_align2 (align2.hip).  Segment-count buckets: one compiled kernel per
+// (bucket, u8/i16).  A task's bucket is that of its first pass
+// (p*ceil(qlen/p) columns over 64 lanes); its reverse pass has fewer columns
+// and reuses the same body.
+constexpr int kA2Buckets = 8;
+inline constexpr int kA2CD[kA2Buckets] = {1, 2, 3, 4, 6, 8, 12, 16};
+constexpr int kA2Bins = 2 * kA2Buckets;  // bins [0, 8): i16, [8, 16): u8
+
+BWAGPU_HD inline int a2_bin_of(int qlen, bool u8) {
+  const int p = u8 ? 16 : 8;
+  const int ncol = (qlen + p - 1) / p * p;
+  const int cd = ncol > 64 ? (ncol + 63) / 64 : 1;
+  const int b = cd <= 4 ? cd - 1 : cd <= 6 ? 4 : cd <= 8 ? 5 : cd <= 12 ? 6 : 7;
+  return (u8 ? kA2Buckets : 0) + b;
+}
+
+// scoring limits of the align2 kernels (reasons are the E_UNSUPPORTED text)
+inline const char* align2_opt_unsupported(const DevOpt& o) {
+  if (o.o_ins <= 0)
+    return "ksw_align2 with o_ins == 0: the reference's lazy-F early exit (ksw.c:180) then depends on "
+           "its SIMD lane order; run it on the CPU";
+  if (o.max_mat <= 0) return "ksw_align2 needs a positive match score (ksw.c:216 divides by it)";
+  if (o.o_ins > 65535 || o.e_ins > 65535 || o.o_del > 65535 || o.e_del > 65535) return "gap penalty > 65535";
+  return nullptr;
+}
+
+// mem_reg2aln's CIGAR (reg2aln.hip).  Query-length buckets: one compiled
+// kernel per strided segment count CD (eh[] slots 0..qlen over 64 lanes:
+// qlen + 1 <= 64 * CD)
+constexpr int kR2Buckets = 6;
+inline constexpr int kR2CD[kR2Buckets] = {1, 2, 3, 4, 8, 16};
+BWAGPU_HD inline int r2_bucket_of(int qlen) {
+  const int cd = (qlen + 64) >> 6;
+  return cd <= 4 ? cd - 1 : (cd <= 8 ? 4 : 5);
+}
+// a job's direction matrix (ksw_global2's z, ncol x tlen bytes, ksw.c:511-512)
+// sits in LDS up to kR2ZSmall / kR2ZLarge bytes and in a per-wave HBM slice beyond
+constexpr int kR2ZSmall = 8 * 1024, kR2ZLarge = 24 * 1024;
+constexpr int kR2MaxRef = 8192;  // reference window bytes per job (LDS)
+
+}  // namespace bwagpu

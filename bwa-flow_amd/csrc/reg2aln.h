@@ -1,5 +1,5 @@
 // reg2aln.h — internal declarations of the batched mem_reg2aln CIGAR kernels
-// (reg2aln.hip) shared with the C ABI (capi.hip).  Not part of the ABI.
+// (reg2aln.hip) shared with the C ABI (capi_tasks.hip).  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -9,14 +9,7 @@
 
 namespace bwagpu {
 
-// Query-length buckets: one compiled kernel per strided segment count CD
-// (eh[] slots 0..qlen over 64 lanes: qlen + 1 <= 64 * CD)
-constexpr int kR2Buckets = 6;
-extern const int kR2CD[kR2Buckets];  // {1, 2, 3, 4, 8, 16}
-__host__ __device__ inline int r2_bucket_of(int qlen) {
-  const int cd = (qlen + 64) >> 6;
-  return cd <= 4 ? cd - 1 : (cd <= 8 ? 4 : 5);
-}
+// (the buckets, kR2CD, r2_bucket_of and the matrix classes: pure.h)
 
 struct R2AArgs {
   const bwagpu_reg2aln_task_t* tasks;

@@ -346,8 +346,6 @@ __global__ void __launch_bounds__(256) reg2aln_kernel(DevOpt o, DevRef ref, R2AA
   }
 }
 
-const int kR2CD[kR2Buckets] = {1, 2, 3, 4, 8, 16};
-
 int r2_resident_waves(int cd, size_t lds_per_block, int wpb) {
   int dev = 0, ncu = 0, per = 0;
   if (hipGetDevice(&dev) != hipSuccess) return 4096;

@@ -2923,7 +2923,6 @@ static bool ext_producer() {
   return on;
 }
 static std::atomic<int> g_ext_form{0};
-int ext_form() { return g_ext_form.load(std::memory_order_relaxed); }
 int ext_kernel_for(const DevOpt& o, int form, int tb_bytes) {  // launch_ext_round's choice, first bin
   const bool quad = form != 1 && quad_scores_ok(o, kSpecBinLen[1]) && quad_rows_ok(o, tb_bytes);
   const bool key8 = quad && quad_key8_ok(o, kSpecBinLen[0]);
@@ -2936,26 +2935,6 @@ int set_ext_form(int form) {  // the default of contexts made later; -> the prev
   const int prev = g_ext_form.load(std::memory_order_relaxed);
   if (form >= 0) g_ext_form.store(form > 2 ? 1 : form, std::memory_order_relaxed);
   return prev;
-}
-// the packed ranges (extend_quad) for reads up to lq: H <= lq * max(mat) < 4096
-// (the row-max key H << KS | c, KS <= 3), H * 2^sk + 128 < 2^15 (2^sk >
-// max(mat)), and the scan values H + 33 * CPL * e_ins < 2^15
-bool quad_bound_ok(const DevOpt& o, long hb) {  // hb: a bound on every H of the call
-  if (o.max_mat < 1 || o.max_mat > 15) return false;
-  const int sk = 32 - __builtin_clz((unsigned)o.max_mat);
-  for (int k = 0; k < 25; ++k)
-    if (o.mat[k] < -127 || o.mat[k] > 127) return false;
-  return hb < 4096 && (hb << sk) + 128 < 32768 && hb + 33L * 8 * o.e_ins < 32768 && o.o_del + 128L < 32768 &&
-         o.oe_ins + 128L < 32768 && o.e_del < 32768;
-}
-bool quad_scores_ok(const DevOpt& o, int lq) { return quad_bound_ok(o, (long)lq * o.max_mat); }
-// the 8-bit-column row-max key (extend_quad<.., true>): every H of reads up to lq < 256
-bool quad_key8_ok(const DevOpt& o, int lq) { return (long)lq * o.max_mat <= 255; }
-// the packed row-end state for calls of up to `rows` target rows: i, |i - j|
-// and the z-drop term max((di - dj) e_del, (dj - di) e_ins) (di <= rows,
-// dj <= 256) within 16 bits beside H < 4096
-bool quad_rows_ok(const DevOpt& o, long rows) {
-  return rows >= 0 && rows < 16384 && (rows + 256) * std::max(o.e_del, o.e_ins) < 28672;
 }
 
 // one side launch of the phased extension for list l: G calls per group

@@ -32,7 +32,6 @@
 namespace bwagpu {
 
 const Variant kVariants[kNumVariants] = {{64, 3, VK_FAST}, {64, 4, VK_FAST}, {64, 16, VK_GENERIC}};
-const Variant kExtVariants[kNumExtVariants] = {{64, 3, VK_FAST}, {64, 4, VK_FAST}, {64, 16, VK_GENERIC}};
 
 // Optional per-read trace (bwagpu_debug_set_trace): 8 words per read index:
 // start/end s_memrealtime (100 MHz), DP rows, DP cells, HW_ID, XCC_ID.

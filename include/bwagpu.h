@@ -389,6 +389,21 @@ int bwagpu_chain2aln_device(bwagpu_ctx_t *ctx, const bwagpu_batch_t *dev_batch,
    regions.  The per-read path (BWAGPU_C2A_PATH=fast) ignores it. */
 int bwagpu_set_device_read_len(bwagpu_ctx_t *ctx, int32_t max_len);
 
+/* The blocking task-list entries below (host buffers) validate every task
+   before anything is enqueued: a task outside its pools or a negative or
+   NULL-with-length pool returns BWAGPU_E_INVAL, the first bad task in task
+   order decides; bwagpu_extend_batch and bwagpu_align2_batch also refuse a
+   pool base over 4 that way (bwagpu_sw_stream: BWAGPU_E_RESULTS, from the device).  bwagpu_last_stats(ctx, 0) after a good call:
+   kernel_ms of the launches, the kernels' cells / rows / ext_calls, and the
+   caller's arrays that moved:
+     bwagpu_extend_batch   h2d_bytes = n_tasks * sizeof(bwagpu_ext_task_t) + qpool_len + tpool_len
+                           d2h_bytes = n_tasks * sizeof(bwagpu_ext_result_t)
+     bwagpu_align2_batch   h2d_bytes = n_tasks * sizeof(bwagpu_align2_task_t) + qpool_len + tpool_len
+                           d2h_bytes = n_tasks * sizeof(bwagpu_kswr_t)
+     bwagpu_reg2aln_batch  h2d_bytes = n_tasks * sizeof(bwagpu_reg2aln_task_t) + qpool_len
+                           d2h_bytes = n_tasks * (sizeof(bwagpu_aln_t) + 4 * max_ops + max_md)
+     bwagpu_sw_stream      h2d_bytes = 4 * i_words, d2h_bytes = 20 * *o_tasks (cells / rows /
+                           ext_calls are 0) */
 int bwagpu_extend_batch(bwagpu_ctx_t *ctx, int32_t n_tasks, const bwagpu_ext_task_t *tasks,
                         const uint8_t *qpool, int64_t qpool_len, const uint8_t *tpool,
                         int64_t tpool_len, bwagpu_ext_result_t *results);

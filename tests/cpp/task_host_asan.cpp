@@ -1,0 +1,440 @@
+// task_host_asan.cpp — the host-side plans of bwagpu_extend_batch,
+// bwagpu_align2_batch and bwagpu_sw_stream
+// (bwa-flow_amd/csrc/task_host.h) under the host sanitizers.  Stand-alone: no
+// GPU, no HIP, not loaded into any other process.
+//
+//   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
+//       -I include -I bwa-flow_amd/csrc tests/cpp/task_host_asan.cpp -o task_host_asan && ./task_host_asan
+//
+// The task, base and output arrays handed to a plan are heap allocations of
+// exactly the size the ABI promises, so a read past the end is an
+// AddressSanitizer report.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <limits>
+#include <random>
+#include <vector>
+
+#include "task_host.h"
+
+using namespace bwagpu;
+
+static int g_fail = 0;
+#define EXPECT(cond)                                              \
+  do {                                                            \
+    if (!(cond)) {                                                \
+      std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); \
+      ++g_fail;                                                   \
+    }                                                             \
+  } while (0)
+
+static const int64_t I64MAX = std::numeric_limits<int64_t>::max();
+static const int32_t I32MAX = std::numeric_limits<int32_t>::max();
+
+template <class T>
+struct Exact {  // an exact-size heap copy: a vector's capacity may exceed its size
+  T* p;
+  explicit Exact(const std::vector<T>& v) : p((T*)std::malloc(v.size() ? v.size() * sizeof(T) : 1)) {
+    if (!v.empty()) std::memcpy(p, v.data(), v.size() * sizeof(T));
+  }
+  ~Exact() { std::free(p); }
+  Exact(const Exact&) = delete;
+};
+
+static DevOpt default_opt() {  // bwa mem's defaults: -A1 -B4 -O6 -E1 -L5 -w100 -d100
+  DevOpt o{};
+  o.a = 1, o.o_del = o.o_ins = 6, o.e_del = o.e_ins = 1, o.oe_del = o.oe_ins = 7;
+  o.pen_clip5 = o.pen_clip3 = 5, o.w = 100, o.zdrop = 100, o.max_mat = 1, o.row_bound = 1;
+  for (int i = 0; i < 5; ++i)
+    for (int j = 0; j < 5; ++j) o.mat[i * 5 + j] = (i == 4 || j == 4) ? -1 : (i == j ? 1 : -4);
+  return o;
+}
+
+static bool is(const char* why, const char* text) { return why && !std::strcmp(why, text); }
+
+static bool is_permutation_of_n(const std::vector<int32_t>& all, size_t n) {
+  std::vector<char> seen(n, 0);
+  if (all.size() != n) return false;
+  for (int32_t k : all) {
+    if (k < 0 || (size_t)k >= n || seen[(size_t)k]) return false;
+    seen[(size_t)k] = 1;
+  }
+  return true;
+}
+
+// ---------------------------------------------------------------- extend
+struct Ext {
+  DevOpt o = default_opt();
+  bool quad = false;
+  std::vector<bwagpu_ext_task_t> t;
+  std::vector<uint8_t> q, tp;
+  ExtendPlan plan;
+  const char* why = nullptr;
+  int run() {
+    Exact<bwagpu_ext_task_t> et(t);
+    Exact<uint8_t> eq(q), ett(tp);
+    Exact<bwagpu_ext_result_t> res(std::vector<bwagpu_ext_result_t>(t.size()));
+    return extend_plan(o, quad, (int32_t)t.size(), et.p, eq.p, (int64_t)q.size(), ett.p, (int64_t)tp.size(), res.p,
+                       &plan, &why);
+  }
+};
+static bwagpu_ext_task_t ext(int64_t qoff, int32_t qlen, int64_t toff, int32_t tlen, int32_t h0 = 0, int32_t w = 100) {
+  return bwagpu_ext_task_t{qoff, toff, qlen, tlen, w, 5, 100, h0};
+}
+static Ext ext_base() {
+  Ext c;
+  c.q.assign(2048, 1);
+  c.tp.assign(4096, 2);
+  c.t = {ext(0, 100, 0, 150), ext(100, 50, 150, 80), ext(0, 300, 0, 400)};
+  return c;
+}
+
+static void test_extend() {
+  ExtendPlan plan;
+  const char* why = nullptr;
+  const DevOpt o = default_opt();
+  bwagpu_ext_result_t r1;
+  bwagpu_ext_task_t t1 = ext(0, 0, 0, 0);
+  uint8_t b1 = 0;
+  {  // n == 0 reads nothing; the argument checks (align2_batch's, with the pools')
+    EXPECT(extend_plan(o, true, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, &plan, &why) == BWAGPU_OK);
+    EXPECT(plan.all.empty() && is(why, ""));
+    EXPECT(extend_plan(o, true, -1, nullptr, nullptr, 0, nullptr, 0, nullptr, &plan, &why) == BWAGPU_E_INVAL);
+    EXPECT(extend_plan(o, true, 1, nullptr, nullptr, 0, nullptr, 0, &r1, &plan, &why) == BWAGPU_E_INVAL);
+    EXPECT(extend_plan(o, true, 1, &t1, nullptr, 0, nullptr, 0, nullptr, &plan, &why) == BWAGPU_E_INVAL);
+    EXPECT(extend_plan(o, true, 0, nullptr, nullptr, -1, nullptr, 0, nullptr, &plan, &why) == BWAGPU_E_INVAL);
+    EXPECT(extend_plan(o, true, 0, nullptr, nullptr, 0, nullptr, -1, nullptr, &plan, &why) == BWAGPU_E_INVAL);
+    EXPECT(extend_plan(o, true, 1, &t1, nullptr, 1, &b1, 1, &r1, &plan, &why) == BWAGPU_E_INVAL);
+    EXPECT(extend_plan(o, true, 1, &t1, &b1, 1, nullptr, 1, &r1, &plan, &why) == BWAGPU_E_INVAL && is(why, ""));
+    EXPECT(extend_plan(o, true, 1, &t1, nullptr, 0, nullptr, 0, &r1, &plan, &why) == BWAGPU_OK);  // empty pools
+    EXPECT(plan.all.size() == 1 && plan.count[0] == 1);
+  }
+  {  // every refusal text
+    Ext c = ext_base();
+    EXPECT(c.run() == BWAGPU_OK);
+    for (int f = 0; f < 7; ++f) {
+      c = ext_base();
+      bwagpu_ext_task_t& t = c.t[1];
+      if (f == 0) t.qlen = -1;
+      if (f == 1) t.tlen = -1;
+      if (f == 2) t.qoff = -1;
+      if (f == 3) t.toff = -1;
+      if (f == 4) t.qoff = 2048 - 49;
+      if (f == 5) t.toff = 4096 - 79;
+      if (f == 6) t.w = -1;
+      EXPECT(c.run() == BWAGPU_E_INVAL && is(c.why, "task outside its pools"));
+    }
+    c = ext_base();
+    c.t[1] = ext(2048 - 50, 50, 4096 - 80, 80);  // up to the last base of both pools
+    EXPECT(c.run() == BWAGPU_OK);
+    c.t[1].qlen = 1024;
+    c.t[1].qoff = 0;
+    EXPECT(c.run() == BWAGPU_E_UNSUPPORTED && is(c.why, "qlen too long"));
+    c = ext_base();
+    c.q[2047] = 5;  // a base no task covers
+    EXPECT(c.run() == BWAGPU_E_INVAL && is(c.why, "query base > 4"));
+    c.tp[4095] = 5;  // the query pool is looked at first
+    EXPECT(c.run() == BWAGPU_E_INVAL && is(c.why, "query base > 4"));
+    c.q[2047] = 4;
+    EXPECT(c.run() == BWAGPU_E_INVAL && is(c.why, "target base > 4"));
+    c = ext_base();
+    c.tp.assign(20000, 2);
+    c.t[0] = ext(0, 100, 0, 20000, 0, 1 << 20);
+    c.t[0].end_bonus = 1 << 20;  // neither the band nor the penalties bound the rows: 20000 of them
+    EXPECT(c.run() == BWAGPU_E_UNSUPPORTED && is(c.why, "task needs too many LDS rows"));
+  }
+  {  // the earlier of two bad tasks wins; a bad task wins over a bad pool base
+    Ext c = ext_base();
+    c.t[1].qlen = 1024, c.t[1].qoff = 0;
+    c.t[2].tlen = 5000;
+    EXPECT(c.run() == BWAGPU_E_UNSUPPORTED && is(c.why, "qlen too long"));
+    c.t[0].tlen = 5000;
+    EXPECT(c.run() == BWAGPU_E_INVAL && is(c.why, "task outside its pools"));
+    c = ext_base();
+    c.q[0] = 9;
+    c.t[2].qlen = 1024;
+    EXPECT(c.run() == BWAGPU_E_UNSUPPORTED && is(c.why, "qlen too long"));
+  }
+  {  // sums that do not fit their type: the task is outside its pool
+    Ext c = ext_base();
+    c.t[1].qoff = I64MAX, c.t[1].qlen = 1;
+    EXPECT(c.run() == BWAGPU_E_INVAL && is(c.why, "task outside its pools"));
+    c = ext_base();
+    c.t[1].toff = I64MAX, c.t[1].tlen = 1;
+    EXPECT(c.run() == BWAGPU_E_INVAL && is(c.why, "task outside its pools"));
+    c = ext_base();
+    c.t[1].qlen = I32MAX;
+    EXPECT(c.run() == BWAGPU_E_INVAL && is(c.why, "task outside its pools"));
+    c.t[1].qoff = 1;
+    EXPECT(c.run() == BWAGPU_E_INVAL && is(c.why, "task outside its pools"));
+  }
+  {  // both sides of every max_len() boundary (qlen + 1 columns): 192, 256, 1024
+    Ext c = ext_base();
+    c.t.clear();
+    const int ql[] = {191, 192, 255, 256, 1023, 0}, want[] = {0, 1, 1, 2, 2, 0};
+    for (int q : ql) c.t.push_back(ext(0, q, 0, 100, 7));
+    EXPECT(c.run() == BWAGPU_OK);
+    EXPECT(!c.plan.t5 && c.plan.count[0] == 2 && c.plan.count[1] == 2 && c.plan.count[2] == 2);
+    for (int v = 0; v < kNumExtVariants; ++v)
+      for (int i = 0; i < c.plan.count[v]; ++i) EXPECT(want[c.plan.all[(size_t)(c.plan.off[v] + i)]] == v);
+    EXPECT((c.plan.all == std::vector<int32_t>{0, 5, 1, 2, 3, 4}));  // task order inside a list
+    // rows = min(tlen, qlen + band + 1) = 100 -> (100 + 2 + 15) & ~15
+    EXPECT(c.plan.tb[0] == 112 && c.plan.tb[1] == 112 && c.plan.tb[2] == 112 && c.plan.tb[3] == 0);
+    // the packed kernel takes h0 > 0, 1 <= qlen <= 255, targets without an N
+    c.quad = true;
+    EXPECT(c.run() == BWAGPU_OK);
+    EXPECT((c.plan.all == std::vector<int32_t>{5, 3, 4, 0, 1, 2}) && c.plan.count[3] == 3 && c.plan.off[3] == 3);
+    c.tp[99] = 4;  // an N in the last target row of every task
+    EXPECT(c.run() == BWAGPU_OK && c.plan.t5 && c.plan.count[3] == 0);
+    EXPECT((c.plan.all == std::vector<int32_t>{0, 5, 1, 2, 3, 4}));
+    c.tp[99] = 2, c.tp[100] = 4;  // an N just past them
+    EXPECT(c.run() == BWAGPU_OK && c.plan.t5 && c.plan.count[3] == 3);
+    c.t[0].h0 = 0;
+    EXPECT(c.run() == BWAGPU_OK && c.plan.count[3] == 2 && c.plan.all[0] == 0);
+  }
+}
+
+static void test_extend_mixed() {  // the plan of a mixed batch
+  Ext c = ext_base();
+  c.quad = true;
+  c.t.clear();
+  std::mt19937 g(5);
+  const int ql[] = {0, 1, 100, 150, 191, 192, 255, 256, 300, 1023};
+  for (int i = 0; i < 200; ++i) {
+    const int q = ql[g() % 10], tl = (int)(g() % 9) * 40;
+    c.t.push_back(ext((int64_t)(g() % (2048 - q + 1)), q, (int64_t)(g() % (4096 - tl + 1)), tl, (int)(g() % 3) * 20));
+  }
+  for (int i = 0; i < 4096; i += 97) c.tp[(size_t)i] = 4;  // some targets hold an N
+  EXPECT(c.run() == BWAGPU_OK);
+  const ExtendPlan& p = c.plan;
+  EXPECT(is_permutation_of_n(p.all, c.t.size()) && p.t5);
+  int32_t off = 0;
+  for (int v = 0; v < kExtLists; ++v) {
+    EXPECT(p.off[v] == off && (p.count[v] == 0) == (p.tb[v] == 0) && p.tb[v] % 16 == 0);
+    for (int32_t i = 0; i < p.count[v]; ++i) {
+      const int32_t k = p.all[(size_t)(off + i)];
+      const bwagpu_ext_task_t& t = c.t[(size_t)k];
+      if (i) EXPECT(p.all[(size_t)(off + i - 1)] < k);  // task order inside a list
+      if (v < kNumExtVariants) {
+        EXPECT(t.qlen + 1 <= kExtVariants[v].max_len() && (v == 0 || t.qlen + 1 > kExtVariants[v - 1].max_len()));
+      } else {
+        EXPECT(t.h0 > 0 && t.qlen >= 1 && t.qlen <= 255);
+        for (int32_t j = 0; j < t.tlen; ++j) EXPECT(c.tp[(size_t)(t.toff + j)] <= 3);
+      }
+      EXPECT(std::min(t.tlen, t.qlen + 1) + 2 <= p.tb[v]);  // its rows fit: at least the band-free ones
+    }
+    off += p.count[v];
+  }
+  EXPECT((size_t)off == c.t.size() && p.count[3] > 0 && p.count[0] > 0 && p.count[2] > 0);
+}
+
+// ---------------------------------------------------------------- align2
+struct A2 {
+  DevOpt o = default_opt();
+  std::vector<bwagpu_align2_task_t> t;
+  std::vector<uint8_t> q, tp;
+  Align2Plan plan;
+  const char* why = nullptr;
+  int run() {
+    Exact<bwagpu_align2_task_t> et(t);
+    Exact<uint8_t> eq(q), ett(tp);
+    Exact<bwagpu_kswr_t> res(std::vector<bwagpu_kswr_t>(t.size()));
+    return align2_plan(o, (int32_t)t.size(), et.p, eq.p, (int64_t)q.size(), ett.p, (int64_t)tp.size(), res.p, &plan,
+                       &why);
+  }
+};
+static bwagpu_align2_task_t a2(int64_t qoff, int32_t qlen, int64_t toff, int32_t tlen, int32_t xtra) {
+  return bwagpu_align2_task_t{qoff, toff, qlen, tlen, xtra, 0};
+}
+static A2 a2_base() {
+  A2 c;
+  c.q.assign(2048, 1);
+  c.tp.assign(4096, 2);
+  c.t = {a2(0, 100, 0, 150, BWAGPU_KSW_XBYTE), a2(100, 50, 150, 80, 0), a2(0, 300, 0, 400, BWAGPU_KSW_XBYTE)};
+  return c;
+}
+
+static void test_align2() {
+  Align2Plan plan;
+  const char* why = nullptr;
+  DevOpt o = default_opt();
+  bwagpu_kswr_t r1;
+  bwagpu_align2_task_t t1 = a2(0, 0, 0, 0, 0);
+  uint8_t b1 = 0;
+  {
+    EXPECT(align2_plan(o, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, &plan, &why) == BWAGPU_OK && plan.bins.empty());
+    EXPECT(align2_plan(o, -1, nullptr, nullptr, 0, nullptr, 0, nullptr, &plan, &why) == BWAGPU_E_INVAL);
+    EXPECT(align2_plan(o, 1, nullptr, nullptr, 0, nullptr, 0, &r1, &plan, &why) == BWAGPU_E_INVAL);
+    EXPECT(align2_plan(o, 1, &t1, nullptr, 0, nullptr, 0, nullptr, &plan, &why) == BWAGPU_E_INVAL);
+    EXPECT(align2_plan(o, 0, nullptr, nullptr, -1, nullptr, 0, nullptr, &plan, &why) == BWAGPU_E_INVAL);
+    EXPECT(align2_plan(o, 0, nullptr, nullptr, 0, nullptr, -1, nullptr, &plan, &why) == BWAGPU_E_INVAL);
+    EXPECT(align2_plan(o, 1, &t1, nullptr, 1, &b1, 1, &r1, &plan, &why) == BWAGPU_E_INVAL);
+    EXPECT(align2_plan(o, 1, &t1, &b1, 1, nullptr, 1, &r1, &plan, &why) == BWAGPU_E_INVAL && is(why, ""));
+    DevOpt bad = o;  // an empty batch is accepted before the options are looked at
+    bad.o_ins = 0;
+    EXPECT(align2_plan(bad, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, &plan, &why) == BWAGPU_OK);
+  }
+  {  // every refusal text
+    A2 c = a2_base();
+    EXPECT(c.run() == BWAGPU_OK);
+    c.o.o_ins = 0;
+    EXPECT(c.run() == BWAGPU_E_UNSUPPORTED && std::strstr(c.why, "ksw_align2 with o_ins == 0") == c.why);
+    c = a2_base();
+    c.o.max_mat = 0;
+    EXPECT(c.run() == BWAGPU_E_UNSUPPORTED && std::strstr(c.why, "ksw_align2 needs a positive match score") == c.why);
+    c = a2_base();
+    c.o.e_del = 65536;
+    EXPECT(c.run() == BWAGPU_E_UNSUPPORTED && is(c.why, "gap penalty > 65535"));
+    for (int f = 0; f < 6; ++f) {
+      c = a2_base();
+      bwagpu_align2_task_t& t = c.t[1];
+      if (f == 0) t.qlen = -1;
+      if (f == 1) t.tlen = -1;
+      if (f == 2) t.qoff = -1;
+      if (f == 3) t.toff = -1;
+      if (f == 4) t.qoff = 2048 - 49;
+      if (f == 5) t.toff = 4096 - 79;
+      EXPECT(c.run() == BWAGPU_E_INVAL && is(c.why, "task outside its pools"));
+    }
+    c = a2_base();
+    c.t[1] = a2(2048 - 50, 50, 4096 - 80, 80, 0);
+    EXPECT(c.run() == BWAGPU_OK);
+    c.t[1] = a2(0, BWAGPU_MAX_READ_LEN, 0, 80, 0);
+    EXPECT(c.run() == BWAGPU_OK);
+    c.t[1].qlen = BWAGPU_MAX_READ_LEN + 1;
+    EXPECT(c.run() == BWAGPU_E_UNSUPPORTED && is(c.why, "qlen > BWAGPU_MAX_READ_LEN"));
+    c = a2_base();
+    c.o.max_mat = 100;
+    c.t[1].qlen = 327;  // 32700
+    EXPECT(c.run() == BWAGPU_OK);
+    c.t[1].qlen = 328;
+    EXPECT(c.run() == BWAGPU_E_UNSUPPORTED && is(c.why, "i16 scores could saturate (qlen * max score > 32767)"));
+    c.t[1].xtra = BWAGPU_KSW_XBYTE;  // the 8-bit kernels saturate like the reference's
+    EXPECT(c.run() == BWAGPU_OK);
+    c = a2_base();
+    c.tp[4095] = 5;
+    EXPECT(c.run() == BWAGPU_E_INVAL && is(c.why, "target base > 4"));
+    c.q[2047] = 5;
+    EXPECT(c.run() == BWAGPU_E_INVAL && is(c.why, "query base > 4"));
+  }
+  {  // order of verdicts
+    A2 c = a2_base();
+    c.t[1].qlen = BWAGPU_MAX_READ_LEN + 1;
+    c.t[2].tlen = 5000;
+    EXPECT(c.run() == BWAGPU_E_UNSUPPORTED && is(c.why, "qlen > BWAGPU_MAX_READ_LEN"));
+    c.t[0].tlen = 5000;
+    EXPECT(c.run() == BWAGPU_E_INVAL && is(c.why, "task outside its pools"));
+    c = a2_base();
+    c.q[0] = 9;
+    c.t[2].qlen = BWAGPU_MAX_READ_LEN + 1;
+    EXPECT(c.run() == BWAGPU_E_UNSUPPORTED && is(c.why, "qlen > BWAGPU_MAX_READ_LEN"));
+  }
+  {  // overflow
+    A2 c = a2_base();
+    c.t[1].qoff = I64MAX, c.t[1].qlen = 1;
+    EXPECT(c.run() == BWAGPU_E_INVAL && is(c.why, "task outside its pools"));
+    c = a2_base();
+    c.t[1].tlen = I32MAX, c.t[1].toff = 1;
+    EXPECT(c.run() == BWAGPU_E_INVAL && is(c.why, "task outside its pools"));
+    c = a2_base();
+    c.t[1].qlen = I32MAX;
+    EXPECT(c.run() == BWAGPU_E_INVAL && is(c.why, "task outside its pools"));
+  }
+  {  // the plan of a mixed batch
+    A2 c = a2_base();
+    c.t.clear();
+    std::mt19937 g(7);
+    const int ql[] = {0, 1, 64, 65, 128, 129, 150, 250, 256, 257, 384, 385, 512, 513, 768, 769, 1023};
+    for (int i = 0; i < 200; ++i) {
+      const int q = ql[g() % 17], tl = (int)(g() % 8) * 50;
+      c.t.push_back(a2((int64_t)(g() % (2048 - q + 1)), q, (int64_t)(g() % (4096 - tl + 1)), tl,
+                       g() % 2 ? BWAGPU_KSW_XBYTE : 0));
+    }
+    EXPECT(c.run() == BWAGPU_OK);
+    const Align2Plan& p = c.plan;
+    const size_t n = c.t.size();
+    EXPECT(is_permutation_of_n(p.all, n) && p.boff.size() == n);
+    int64_t scr = 0;
+    for (size_t k = 0; k < n; ++k) {
+      EXPECT(p.boff[k] == scr);
+      scr += c.t[k].tlen + 1;
+    }
+    EXPECT(p.scratch == scr);
+    int32_t off = 0;
+    std::vector<int64_t> work(kA2Bins, 0);
+    for (int b = 0; b < kA2Bins; ++b) {
+      EXPECT(p.list_off[b] == off && p.counts[kA2Bins + b] == 0);
+      for (int32_t i = 0; i < p.counts[b]; ++i) {
+        const int32_t k = p.all[(size_t)(off + i)];
+        EXPECT(a2_bin_of(c.t[(size_t)k].qlen, (c.t[(size_t)k].xtra & BWAGPU_KSW_XBYTE) != 0) == b);
+        if (i) {  // longest target first, task order among equals
+          const int32_t prev = p.all[(size_t)(off + i - 1)];
+          EXPECT(c.t[(size_t)prev].tlen > c.t[(size_t)k].tlen || (c.t[(size_t)prev].tlen == c.t[(size_t)k].tlen && prev < k));
+        }
+        work[(size_t)b] += (int64_t)c.t[(size_t)k].tlen * kA2CD[b % kA2Buckets];
+      }
+      off += p.counts[b];
+    }
+    EXPECT((size_t)off == n);
+    size_t nonempty = 0;
+    for (int b = 0; b < kA2Bins; ++b) nonempty += p.counts[b] != 0;
+    EXPECT(p.bins.size() == nonempty);
+    for (size_t i = 0; i < p.bins.size(); ++i) {
+      EXPECT(p.counts[p.bins[i]] > 0);
+      if (i) EXPECT(work[(size_t)p.bins[i - 1]] >= work[(size_t)p.bins[i]]);
+    }
+  }
+}
+
+// ---------------------------------------------------------------- stream
+static int run_stream(const std::vector<int32_t>& w, StreamPlan* plan, const char** why) {
+  Exact<int32_t> e(w);
+  return stream_plan(e.p, (int64_t)w.size(), plan, why);
+}
+
+static void test_stream() {
+  StreamPlan plan;
+  const char* why = nullptr;
+  EXPECT(stream_plan(nullptr, 0, &plan, &why) == BWAGPU_OK && plan.starts.empty() && plan.lq_max == 1);
+  EXPECT(stream_plan(nullptr, -1, &plan, &why) == BWAGPU_E_INVAL);
+  EXPECT(stream_plan(nullptr, 3, &plan, &why) == BWAGPU_E_INVAL && is(why, ""));
+  // three records: words [0, 5), [5, 8), [8, 14); word 1 of each is its read length
+  const std::vector<int32_t> good = {5, 150, -7, -7, -7, 8, 0, -7, 14, 250, -7, -7, -7, -7};
+  EXPECT(run_stream(good, &plan, &why) == BWAGPU_OK);
+  EXPECT((plan.starts == std::vector<int64_t>{0, 5, 8}) && plan.lq_max == 250);
+  std::vector<int32_t> w = good;
+  w[8] = 15;  // past the end
+  EXPECT(run_stream(w, &plan, &why) == BWAGPU_E_INVAL && is(why, "stream: a record's end word is out of range"));
+  w[8] = 10;  // a record of two words
+  EXPECT(run_stream(w, &plan, &why) == BWAGPU_E_INVAL && is(why, "stream: a record's end word is out of range"));
+  w[8] = -1;
+  EXPECT(run_stream(w, &plan, &why) == BWAGPU_E_INVAL && is(why, "stream: a record's end word is out of range"));
+  w = good;
+  w.push_back(20);  // a last record of one word: its length word is never read
+  EXPECT(run_stream(w, &plan, &why) == BWAGPU_E_INVAL && is(why, "stream: a record's end word is out of range"));
+  w = good;
+  w[6] = -1;
+  EXPECT(run_stream(w, &plan, &why) == BWAGPU_E_INVAL && is(why, "stream: negative read length"));
+  w[6] = BWAGPU_MAX_READ_LEN;
+  EXPECT(run_stream(w, &plan, &why) == BWAGPU_OK && plan.lq_max == BWAGPU_MAX_READ_LEN);
+  w[6] = BWAGPU_MAX_READ_LEN + 1;
+  EXPECT(run_stream(w, &plan, &why) == BWAGPU_E_UNSUPPORTED && is(why, "stream: read longer than BWAGPU_MAX_READ_LEN"));
+  w[1] = -1;  // the earlier record wins
+  EXPECT(run_stream(w, &plan, &why) == BWAGPU_E_INVAL && is(why, "stream: negative read length"));
+  w[0] = 2;
+  EXPECT(run_stream(w, &plan, &why) == BWAGPU_E_INVAL && is(why, "stream: a record's end word is out of range"));
+}
+
+int main() {
+  test_extend();
+  test_extend_mixed();
+  test_align2();
+  test_stream();
+  if (g_fail) {
+    std::printf("task_host_asan: %d checks failed\n", g_fail);
+    return 1;
+  }
+  std::printf("task_host_asan OK\n");
+  return 0;
+}
