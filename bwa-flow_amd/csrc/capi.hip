@@ -268,6 +268,8 @@ int create_common(int device, const bwagpu_opt_t* opt, const bwagpu_bns_t* bns, 
   ctx->device = device;
   ctx->opt_b = opt->b;
   ctx->ext_form = set_ext_form(-1);
+  ctx->ext_short = ext_short_default();
+  ctx->ext_short_fill = ext_short_fill_default();
   *made = ctx;
   HIPC(hipSetDevice(device), "hipSetDevice");
   HIPC(hipMalloc(&ctx->d_ann_off, sizeof(int64_t) * bns->n_seqs), "hipMalloc(ann_offset)");
@@ -702,6 +704,8 @@ int enqueue_spec(bwagpu_ctx_t* ctx, Slot& s, const DevBatch& db, int lq_max, bwa
   a.lq_bound = lq_max;
   const int tb = tb_bytes_for(ctx->opt, std::max(lq_max, 1));
   ss.form = ctx->ext_form;
+  ss.short_q = ctx->ext_short;
+  ss.short_fill = ctx->ext_short_fill;
   ss.pool = ctx->prof_ev.empty() ? nullptr : ctx->prof_ev.data();
   ss.pool_n = (int)ctx->prof_ev.size();
   ss.pool_used = &ctx->prof_used;
@@ -1196,6 +1200,41 @@ int bwagpu_ctx_ext_form(bwagpu_ctx_t* ctx, int form) {
   const int prev = ctx->ext_form;
   if (form >= 0) ctx->ext_form = form > 2 ? 1 : form;
   return prev;
+}
+
+int bwagpu_ctx_ext_short(bwagpu_ctx_t* ctx, int q) {
+  if (!ctx) return BWAGPU_E_INVAL;
+  const int prev = ctx->ext_short;
+  if (q >= 0) ctx->ext_short = q > 63 ? 63 : q;
+  return prev;
+}
+
+int bwagpu_ctx_ext_short_fill(bwagpu_ctx_t* ctx, int percent) {
+  if (!ctx) return BWAGPU_E_INVAL;
+  const int prev = ctx->ext_short_fill;
+  if (percent >= 0) ctx->ext_short_fill = percent > 100000 ? 100000 : percent;
+  return prev;
+}
+
+int bwagpu_debug_spec_short(bwagpu_ctx_t* ctx, void* stream, int64_t* out) {
+  if (!ctx || !out) return BWAGPU_E_INVAL;
+  hipStream_t st = nullptr;
+  if (int rc = entry_stream(ctx, stream, &st)) return rc;
+  int k = 0;
+  while (k < BWAGPU_NUM_SLOTS && ctx->dev_stream[k] != st) ++k;
+  if (k == BWAGPU_NUM_SLOTS || !ctx->dev_scratch[k].d_ctr.p) return fail(ctx, BWAGPU_E_INVAL, "no device-entry batch on this stream");
+  HIPC(hipStreamSynchronize(st), "hipStreamSynchronize");
+  int32_t c[SPC_WORDS];
+  HIPC(hipMemcpy(c, ctx->dev_scratch[k].d_ctr.p, sizeof c, hipMemcpyDeviceToHost), "hipMemcpy(ctr)");
+  out[0] = c[SPC_SHORT_N];
+  for (int r = 0; r < 2; ++r) {  // rounds A and B, the first length bin's lists
+    const int l = r * kSpecBins;
+    out[1 + 4 * r] = c[SPC_LCNT + l];
+    out[2 + 4 * r] = c[SPC_LLONG + l];
+    out[3 + 4 * r] = c[SPC_RCNT + l];
+    out[4 + 4 * r] = c[SPC_RLONG + l];
+  }
+  return BWAGPU_OK;
 }
 
 int bwagpu_ctx_row_bound(bwagpu_ctx_t* ctx, int on) {

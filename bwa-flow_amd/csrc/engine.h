@@ -138,6 +138,9 @@ enum {
   SPC_LCNT = 64,      // [list] phased extension: tasks with a left side (spec_side4_kernel's left list)
   SPC_RCNT = 73,      // [list] ... with a right side
   SPC_LIGHT_CUR = 82, // the final light pass's cursor over the reads without a round-B task
+  SPC_LLONG = 84,     // [list] phased extension, short phase on: left sides with a query longer than short_q
+  SPC_RLONG = 93,     // [list] ... right sides (the first position of the list's short run)
+  SPC_SHORT_N = 102,  // sides run in the short phase, sixteen per wave (diagnostic)
   SPC_WORDS = 128
 };
 // sharded queue heads of the extension task lists (SpecArgs::qh, zeroed per
@@ -147,7 +150,8 @@ enum {
 // MI355X_MICROARCH.md "dequeue"; measured here: 7.9 -> 6.6 ms per C2 batch
 // when the nine lists' heads moved off the two shared lines)
 constexpr int kQHStride = 32;
-constexpr int kQHWords = 2 * kSpecRounds * kSpecBins * 8 * kQHStride;  // x 2: the phased extension's right lists
+constexpr int kQHShort = 2 * kSpecRounds * kSpecBins * 8 * kQHStride;  // x 2: the phased extension's right lists
+constexpr int kQHWords = 2 * kQHShort;  // x 2: the heads of each side list's short run, laid out alike from kQHShort
 // pair-kernel task order (spec_sort_*): 1024 keys = (left qlen / 8, right qlen / 8)
 constexpr int kSortKeys = 1024;
 // (the phased extension sorts each list twice, by the left and by the right
@@ -222,9 +226,20 @@ struct SpecStreams {
   // the context's extension form (bwagpu_ctx_ext_form): 0 = eight / four seeds
   // per wave where the scores fit (default), 1 = two per wave, 2 = four per wave
   int form = 0;
+  // the context's short-side threshold (bwagpu_ctx_ext_short): the eight-per-
+  // wave phased kernel runs sides with a query of up to short_q bases sixteen
+  // per wave (0: off)
+  int short_q = 0;
+  // ... for a short run of at least short_fill percent of the grid's
+  // sixteen-per-wave slots (bwagpu_ctx_ext_short_fill)
+  int short_fill = 0;
 };
 // the form new contexts start with (bwagpu_debug_ext_form; process-wide default)
 int set_ext_form(int form);
+// the short-side threshold new contexts start with (BWAGPU_EXT_SHORT_Q, else
+// the compiled default)
+int ext_short_default();
+int ext_short_fill_default();
 // the first length bin's extension kernel launch_ext_round picks for `form`
 // and options `o` with target row buffers of tb_bytes: 8 = eight seeds per
 // wave (spec_ext4_kernel<16,10,true>), 4 = four per wave with the 8-bit key

@@ -711,15 +711,29 @@ __device__ __forceinline__ uint32_t neg15(uint32_t a) { return opq(W(S(a) >> (s1
 __device__ __forceinline__ uint32_t sel(uint32_t m, uint32_t a, uint32_t b) { return (m & a) | (~m & b); }
 
 constexpr uint32_t ONE = 0x00010001u;
+// the all-reduce of an 8-lane group (half a DPP row): lane i <-> 7 - i, then
+// the butterflies inside each quad
+constexpr int DPP_ROW_HALF_MIRROR = 0x141, DPP_QUAD_XOR1 = 0xB1 /* [1,0,3,2] */, DPP_QUAD_XOR2 = 0x4E /* [2,3,0,1] */;
 // DPP moves of whole registers (bound_ctrl: a lane without a source reads 0)
 template <int CTRL>
 __device__ __forceinline__ uint32_t mov0(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xF, 0xF, true);
 }
-// inclusive max-scan over each G-lane group (G = 16: a DPP row, 32: a half)
-// of packed values >= 0 (identity 0)
+// inclusive max-scan over each G-lane group (G = 16: a DPP row, 32: a half,
+// 8: half a row) of packed values >= 0 (identity 0)
 template <int G>
 __device__ __forceinline__ uint32_t grp_scan_umax(uint32_t x) {
+  if constexpr (G == 8) {
+    // Two groups share a DPP row, so no row_shr may carry lane 7 into lane 8:
+    // scan each quad (a quad's first lanes read themselves: max(x, x) = x),
+    // then the group's upper quad takes the lower quad's total (row_shr:4
+    // written to banks 1 / 3 only; banks 0 / 2 get the identity)
+    x = umax(x, (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x90 /* quad_perm:[0,0,1,2] */, 0xF, 0xF, false));
+    x = umax(x, (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x44 /* quad_perm:[0,1,0,1] */, 0xF, 0xF, false));
+    const uint32_t q3 = (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0xFF /* quad_perm:[3,3,3,3] */, 0xF, 0xF, false);
+    const uint32_t t = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)q3, DPP_ROW_SHR(4), 0xF, 0xA, false);
+    return umax(x, t);
+  }
   x = umax(x, mov0<DPP_ROW_SHR(1)>(x));
   x = umax(x, mov0<DPP_ROW_SHR(2)>(x));
   x = umax(x, mov0<DPP_ROW_SHR(4)>(x));
@@ -751,11 +765,16 @@ __device__ __forceinline__ void grp_red3(uint32_t& K, uint32_t& L, uint32_t& H) 
     L = umin(L, l);                                                                      \
     H = smax(H, h);                                                                      \
   }
+  if constexpr (G == 8) {  // half a row: mirror it, then the two quad butterflies
+    RED3_STEP(DPP_ROW_HALF_MIRROR)
+    RED3_STEP(DPP_QUAD_XOR1)
+    RED3_STEP(DPP_QUAD_XOR2)
+    return;
+  }
   RED3_STEP(DPP_ROW_ROR(8))
   RED3_STEP(DPP_ROW_ROR(4))
   RED3_STEP(DPP_ROW_ROR(2))
   RED3_STEP(DPP_ROW_ROR(1))
-#undef RED3_STEP
   if constexpr (G == 16) return;  // a DPP row: done
   const auto pk_ = __builtin_amdgcn_permlane16_swap(K, K, false, false);
   const auto pl = __builtin_amdgcn_permlane16_swap(L, L, false, false);
@@ -763,6 +782,7 @@ __device__ __forceinline__ void grp_red3(uint32_t& K, uint32_t& L, uint32_t& H) 
   K = umax((uint32_t)pk_[0], (uint32_t)pk_[1]);
   L = umin((uint32_t)pl[0], (uint32_t)pl[1]);
   H = smax((uint32_t)ph[0], (uint32_t)ph[1]);
+#undef RED3_STEP
 }
 // the group's umax of U and smax of S at once (two independent chains)
 template <int G>
@@ -774,16 +794,22 @@ __device__ __forceinline__ void grp_red2(uint32_t& U, uint32_t& S) {
     U = umax(U, u);                                                                      \
     S = smax(S, s);                                                                      \
   }
+  if constexpr (G == 8) {
+    RED2_STEP(DPP_ROW_HALF_MIRROR)
+    RED2_STEP(DPP_QUAD_XOR1)
+    RED2_STEP(DPP_QUAD_XOR2)
+    return;
+  }
   RED2_STEP(DPP_ROW_ROR(8))
   RED2_STEP(DPP_ROW_ROR(4))
   RED2_STEP(DPP_ROW_ROR(2))
   RED2_STEP(DPP_ROW_ROR(1))
-#undef RED2_STEP
   if constexpr (G == 16) return;
   const auto pu = __builtin_amdgcn_permlane16_swap(U, U, false, false);
   const auto ps = __builtin_amdgcn_permlane16_swap(S, S, false, false);
   U = umax((uint32_t)pu[0], (uint32_t)pu[1]);
   S = smax((uint32_t)ps[0], (uint32_t)ps[1]);
+#undef RED2_STEP
 }
 __device__ __forceinline__ uint32_t half_smax(uint32_t x) {
   x = smax(x, (uint32_t)__builtin_amdgcn_mov_dpp((int)x, DPP_ROW_ROR(8), 0xF, 0xF, false));
@@ -820,17 +846,20 @@ __device__ __forceinline__ QCall quad_idle(const uint8_t* seq, const uint8_t* tb
 
 // K8: the row-max key is H << 8 | j, packed, one reduction for both calls
 // (every H < 256: quad_key8_ok); else H << KS | c widened to H << 10 | j per call.
-// G = the lanes of a group (two calls): 32 (four calls per wave) or 16 (eight
-// calls per wave, K8 only: every scan and reduction stays inside a DPP row).
+// G = the lanes of a group (two calls): 32 (four calls per wave), 16 (eight
+// calls per wave: every scan and reduction stays inside a DPP row) or 8
+// (sixteen calls per wave, K8 only, queries below 64: two groups share a DPP
+// row, so a group's first lane never reads the lane before it).
 // SYM: o_del == o_ins, so E's and F's gap-open terms share one subtraction of
 // the biased M per column.
 template <int G, int CPL, bool K8, bool SYM>
 __device__ __forceinline__ void extend_quad(const DevOpt& o, const QCall& A, const QCall& Bc, ExtOut& xa, ExtOut& xb,
                                             Tally32& ta, Tally32& tbl) {
   using namespace pk16;
-  static_assert(G == 32 || G == 16, "four (G = 32) or eight (G = 16) calls per wave");
+  static_assert(G == 32 || G == 16 || (G == 8 && K8), "four (G = 32), eight (16) or sixteen (8, K8) calls per wave");
   int r;  // the lane index in its group, behind an opaque move (see extend_pair)
-  if constexpr (G == 16) asm volatile("v_and_b32 %0, 15, %1" : "=v"(r) : "v"((int)threadIdx.x));
+  if constexpr (G == 8) asm volatile("v_and_b32 %0, 7, %1" : "=v"(r) : "v"((int)threadIdx.x));
+  else if constexpr (G == 16) asm volatile("v_and_b32 %0, 15, %1" : "=v"(r) : "v"((int)threadIdx.x));
   else asm volatile("v_and_b32 %0, 31, %1" : "=v"(r) : "v"((int)threadIdx.x));
   constexpr int KS = CPL <= 2 ? 1 : (CPL <= 4 ? 2 : (CPL <= 8 ? 3 : 4));  // in-lane column bits of the key
   static_assert(CPL >= 1 && CPL * G <= 256, "columns per call: < 256 (16-bit j, 8-bit key)");
@@ -926,7 +955,10 @@ __device__ __forceinline__ void extend_quad(const DevOpt& o, const QCall& A, con
     }
     const uint32_t sx = grp_scan_umax<G>(add(T, RE2));
     uint32_t EX;
-    if constexpr (G == 16) {
+    if constexpr (G == 8) {
+      EX = mov0<DPP_ROW_SHR(1)>(sx);
+      EX = r == 0 ? 0u : EX;  // a row's lane 8 took lane 7's value: the other group's
+    } else if constexpr (G == 16) {
       EX = mov0<DPP_ROW_SHR(1)>(sx);  // a row's lane 0 reads 0: no column to its left
     } else {
       EX = mov0<DPP_WAVE_SHR1>(sx);
@@ -951,7 +983,10 @@ __device__ __forceinline__ void extend_quad(const DevOpt& o, const QCall& A, con
       H1Q |= hm[c] & qm[c];
     }
     uint32_t hs0;  // H(i, j0 - 1); the group's first lane: the first-column value
-    if constexpr (G == 16) {
+    if constexpr (G == 8) {
+      hs0 = mov0<DPP_ROW_SHR(1)>(hm[CPL - 1]);
+      hs0 = r == 0 ? LEFT0 : hs0;  // lanes 0 and 8 of a row
+    } else if constexpr (G == 16) {
       hs0 = (uint32_t)__builtin_amdgcn_update_dpp((int)LEFT0, (int)hm[CPL - 1], DPP_ROW_SHR(1), 0xF, 0xF, false);
     } else {
       hs0 = mov0<DPP_WAVE_SHR1>(hm[CPL - 1]);

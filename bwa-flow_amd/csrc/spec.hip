@@ -469,13 +469,21 @@ __device__ __forceinline__ SeedExt extend_seed2(const DevOpt& o, const DevRef& r
 
 template <int G = 32>
 __device__ __forceinline__ void store_ext_half(SeedExt* dst, const SeedExt& e) {
-  static_assert(G >= 12, "a SeedExt is 12 words");
+  static_assert(G >= 12 || G == 8, "a SeedExt is 12 words");
   const int d = (int)(threadIdx.x & (G - 1));
   const uint32_t* w = reinterpret_cast<const uint32_t*>(&e);
   uint32_t v = 0;
 #pragma unroll
   for (int k = 0; k < 12; ++k) v = d == k ? w[k] : v;
-  if (d < 12) reinterpret_cast<uint32_t*>(dst)[d] = v;
+  if constexpr (G == 8) {  // eight lanes: words 0-7, then words 8-11 on the first four
+    reinterpret_cast<uint32_t*>(dst)[d] = v;
+    uint32_t u = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) u = d == k ? w[8 + k] : u;
+    if (d < 4) reinterpret_cast<uint32_t*>(dst)[8 + d] = u;
+  } else {
+    if (d < 12) reinterpret_cast<uint32_t*>(dst)[d] = v;
+  }
 }
 
 // Extension tasks of one list, two per wave: a wave claims two consecutive
@@ -1145,8 +1153,12 @@ __global__ void __launch_bounds__(256) spec_sort2_count(DevBatch b, SpecArgs a, 
 }
 
 // exclusive scan of the 256 keys of each (side, bin) histogram: one block each
-// (bins bin0 .. bin0 + nbins - 1)
-__global__ void __launch_bounds__(256) spec_sort2_scan(SpecArgs a, int round, int bin0, int nbins) {
+// (bins bin0 .. bin0 + nbins - 1).  short_q > 0: the first bin's lists get a
+// short run, the sides with a query of up to short_q bases; its first position
+// (= the sides with a longer query: the list is in descending length order)
+// goes to the list's SPC_LLONG / SPC_RLONG word here, before the scatter turns
+// the key positions into cursors.
+__global__ void __launch_bounds__(256) spec_sort2_scan(SpecArgs a, int round, int bin0, int nbins, int short_q) {
   sel_prio();
   __shared__ int part[256];
   const int bin = bin0 + (int)blockIdx.x % nbins, side = (int)blockIdx.x / nbins;
@@ -1162,6 +1174,8 @@ __global__ void __launch_bounds__(256) spec_sort2_scan(SpecArgs a, int round, in
     __syncthreads();
   }
   gh[t] = part[t] - v;  // the key's first position (a cursor from here on)
+  if (short_q > 0 && bin == 0 && t == side_key(short_q))
+    a.ctr[(side ? SPC_RLONG : SPC_LLONG) + round * kSpecBins + bin] = part[t] - v;
 }
 
 __global__ void __launch_bounds__(256) spec_sort2_scatter(DevOpt o, DevBatch b, SpecArgs a, int round, int bin0) {
@@ -1414,34 +1428,34 @@ __device__ __forceinline__ void side_query(const DevBatch& b, const FatTask& f, 
   for (int j = r; j < qlen; j += G) qd[j] = q[RIGHT ? j : -j];
 }
 
-// The phased extension's kernel: one side (RIGHT = false: left calls, true:
-// right calls) of the tasks of one list, eight calls per wave (G = 16) or four
-// (G = 32) in the packed 16-bit DP (extend_quad), claimed in the list's
-// order (the side's query length, longest first).
+// The phased extension's loop over one run of a side list: 128 / G calls per
+// wave (G = 16: eight, 32: four, 8: sixteen) in the
+// packed 16-bit DP (extend_quad), claimed in the list's order (the side's
+// query length, longest first) from the run's own sharded heads.  wlds = the
+// wave's own LDS slice, cut per group: A's and B's target rows (tb_bytes
+// each), their states, their query bytes.  Returns the sides it started.
 template <int G, int PMAX, bool K8, bool RIGHT>
-__global__ void __launch_bounds__(kBlock) spec_side4_kernel(DevOpt o, DevRef ref, DevBatch b, SpecArgs a, int list,
-                                                            int tb_bytes) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-  constexpr uint64_t kLead = G == 16 ? 0x0001000100010001ull : 0x0000000100000001ull;
+__device__ __forceinline__ int side_loop(const DevOpt& o, const DevRef& ref, const DevBatch& b, const SpecArgs& a,
+                                         const FatTask* fl, int n, int32_t* heads, uint8_t* wlds, int tb_bytes,
+                                         long long& spec_cells
+#ifdef BWAGPU_OCC_DIAG
+                                         , unsigned long long* tw, unsigned long long* occ
+#endif
+) {
+  constexpr uint64_t kLead =
+      G == 8 ? 0x0101010101010101ull : (G == 16 ? 0x0001000100010001ull : 0x0000000100000001ull);
   const uint64_t below = kLead & ((1ull << ((int)threadIdx.x & (64 - G))) - 1);
-  // per group: A's and B's target rows, their states, their query bytes
   constexpr int QB = PMAX * G;
-  uint8_t* const ta_ = lds + (size_t)(threadIdx.x / G) * (2 * (size_t)tb_bytes + 2 * kSideLds + 2 * QB);
+  uint8_t* const ta_ = wlds + (size_t)((threadIdx.x & 63) / G) * (2 * (size_t)tb_bytes + 2 * kSideLds + 2 * QB);
   uint8_t* const tb_ = ta_ + tb_bytes;
   LdsS* const sa = (LdsS*)(tb_ + tb_bytes);
   LdsS* const sb = (LdsS*)(tb_ + tb_bytes + kSideLds);
   uint8_t* const qa_ = tb_ + tb_bytes + 2 * kSideLds;
   uint8_t* const qb_ = qa_ + QB;
-  const int n = uni(__hip_atomic_load(&a.ctr[(RIGHT ? SPC_RCNT : SPC_LCNT) + list], __ATOMIC_RELAXED,
-                                      __HIP_MEMORY_SCOPE_AGENT));
-  const FatTask* fl = (RIGHT ? a.ftaskR : a.ftask) + spec_list_off(list, b.n_chains, b.n_seeds);
   ShardQ qq;
-  qq.init(a.qh + 8 * kQHStride * (RIGHT ? kSpecRounds * kSpecBins + list : list) , n);
+  qq.init(heads, n);
   bool ha = false, hb = false, more = n > 0;
-  long long spec_cells = 0;
-#ifdef BWAGPU_OCC_DIAG
-  unsigned long long tw[6] = {0, 0, 0, 0, 0, 0}, occ[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
+  int started = 0;
   for (;;) {
 #ifdef BWAGPU_OCC_DIAG
     const unsigned long long c0 = __builtin_amdgcn_s_memtime();
@@ -1460,6 +1474,7 @@ __global__ void __launch_bounds__(kBlock) spec_side4_kernel(DevOpt o, DevRef ref
             side_start<G, RIGHT>(t, o, ref, a, f, ta_);
             spark(sa, t);
             ha = true;
+            ++started;
           }
           if (!hb && ib < cap) {
             SideTask t;
@@ -1468,6 +1483,7 @@ __global__ void __launch_bounds__(kBlock) spec_side4_kernel(DevOpt o, DevRef ref
             side_start<G, RIGHT>(t, o, ref, a, f, tb_);
             spark(sb, t);
             hb = true;
+            ++started;
           }
         } else {
           more = false;
@@ -1521,6 +1537,76 @@ __global__ void __launch_bounds__(kBlock) spec_side4_kernel(DevOpt o, DevRef ref
     tw[3] += __builtin_amdgcn_s_memtime() - c3;
 #endif
   }
+  return started;
+}
+
+// the short phase's groups and columns: eight lanes, queries up to 63
+constexpr int kShortG = 8, kShortPmax = 8, kShortQMax = kShortG * kShortPmax - 1;
+
+// LDS of one wave of the side kernel: 64 / g groups of two target row buffers,
+// two states and two query buffers
+static size_t side4_wave_lds(int tb_bytes, int g, int pmax) {
+  return (size_t)(64 / g) * (2 * (size_t)tb_bytes + 2 * kSideLds + 2 * (size_t)pmax * g);
+}
+
+// The phased extension's kernel: one side (RIGHT = false: left calls, true:
+// right calls) of the tasks of one list.  The list is sorted by the side's
+// query length, longest first: entries [0, n_long) have a query longer than
+// short_q and run eight per wave (G = 16) or four (G = 32); the eight-per-wave
+// form then runs the rest, [n_long, n), sixteen per wave in groups of eight
+// lanes (short_q > 0; spec_sort2_scan left n_long in the list's counter word).
+// A wave goes from the first run to the second on its own, when the first
+// run's heads are dry: no launch and no barrier between them.  LDS is cut per
+// wave (wave_lds bytes each, the larger of the two runs' needs), so a wave in
+// the second run never touches a sibling's buffers of the first.
+template <int G, int PMAX, bool K8, bool RIGHT>
+__global__ void __launch_bounds__(kBlock) spec_side4_kernel(DevOpt o, DevRef ref, DevBatch b, SpecArgs a, int list,
+                                                            int tb_bytes, int wave_lds, int short_q, int tb_short,
+                                                            int short_fill) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+  uint8_t* const wlds = lds + (size_t)(threadIdx.x >> 6) * (size_t)wave_lds;
+  const int n = uni(__hip_atomic_load(&a.ctr[(RIGHT ? SPC_RCNT : SPC_LCNT) + list], __ATOMIC_RELAXED,
+                                      __HIP_MEMORY_SCOPE_AGENT));
+  const FatTask* fl = (RIGHT ? a.ftaskR : a.ftask) + spec_list_off(list, b.n_chains, b.n_seeds);
+  constexpr bool kShort = G == 16 && K8;  // the form with a short phase
+  int n_long = n;
+  if constexpr (kShort) {
+    if (short_q > 0) {
+      n_long = min(n, uni(__hip_atomic_load(&a.ctr[(RIGHT ? SPC_RLONG : SPC_LLONG) + list], __ATOMIC_RELAXED,
+                                            __HIP_MEMORY_SCOPE_AGENT)));
+      // a short run that does not fill the grid's sixteen-per-wave slots
+      // short_fill / 100 times over runs eight per wave as before (every wave
+      // decides alike): see launch_side_pair
+      const long long slots = (long long)gridDim.x * (kBlock / 64) * (128 / kShortG);
+      if ((long long)(n - n_long) * 100 < slots * short_fill) n_long = n;
+    }
+  }
+  const int hl = RIGHT ? kSpecRounds * kSpecBins + list : list;
+  long long spec_cells = 0;
+#ifdef BWAGPU_OCC_DIAG
+  unsigned long long tw[6] = {0, 0, 0, 0, 0, 0}, occ[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  (void)side_loop<G, PMAX, K8, RIGHT>(o, ref, b, a, fl, n_long, a.qh + 8 * kQHStride * hl, wlds, tb_bytes, spec_cells,
+                                      tw, occ);
+#else
+  (void)side_loop<G, PMAX, K8, RIGHT>(o, ref, b, a, fl, n_long, a.qh + 8 * kQHStride * hl, wlds, tb_bytes, spec_cells);
+#endif
+  if constexpr (kShort) {
+    if (n_long < n) {
+      int32_t* const hs = a.qh + kQHShort + 8 * kQHStride * hl;
+      long long cells_s = 0;  // group-uniform over eight lanes, not sixteen: added on its own
+#ifdef BWAGPU_OCC_DIAG
+      const int ns = side_loop<kShortG, kShortPmax, true, RIGHT>(o, ref, b, a, fl + n_long, n - n_long, hs, wlds,
+                                                                 tb_short, cells_s, tw, occ);
+#else
+      const int ns = side_loop<kShortG, kShortPmax, true, RIGHT>(o, ref, b, a, fl + n_long, n - n_long, hs, wlds,
+                                                                 tb_short, cells_s);
+#endif
+      if ((threadIdx.x & (kShortG - 1)) == 0 && ns) {
+        atomicAdd(&a.ctr[SPC_SHORT_N], ns);
+        atomicAdd(reinterpret_cast<unsigned long long*>(a.ctr + SPC_SPEC64), (unsigned long long)cells_s);
+      }
+    }
+  }
 #ifdef BWAGPU_OCC_DIAG
   if ((threadIdx.x & 63) == 0) {
     for (int k = 0; k < 8; ++k) atomicAdd(reinterpret_cast<unsigned long long*>(a.ctr + 32) + k, occ[k]);
@@ -1529,10 +1615,6 @@ __global__ void __launch_bounds__(kBlock) spec_side4_kernel(DevOpt o, DevRef ref
 #endif
   if ((threadIdx.x & (G - 1)) == 0 && spec_cells)
     atomicAdd(reinterpret_cast<unsigned long long*>(a.ctr + SPC_SPEC64), (unsigned long long)spec_cells);
-}
-
-static size_t side4_lds(int tb_bytes, int g, int pmax) {
-  return (size_t)(kBlock / g) * (2 * (size_t)tb_bytes + 2 * kSideLds + 2 * (size_t)pmax * g);
 }
 
 // ------------------------------------ the side kernel with a producer wave
@@ -2937,17 +3019,71 @@ int set_ext_form(int form) {  // the default of contexts made later; -> the prev
   return prev;
 }
 
+// The short-side threshold (bwagpu_ctx_ext_short): sides
+// with a query of up to this many bases run sixteen per wave in the eight-
+// per-wave phased kernel.  BWAGPU_EXT_SHORT_Q sets the process default (0: off).
+#ifndef BWAGPU_EXT_SHORT_Q_DEFAULT
+#define BWAGPU_EXT_SHORT_Q_DEFAULT 63
+#endif
+int ext_short_default() {
+  static const int q = [] {
+    const char* e = getenv("BWAGPU_EXT_SHORT_Q");
+    const int v = e && e[0] ? atoi(e) : BWAGPU_EXT_SHORT_Q_DEFAULT;
+    return std::min(std::max(v, 0), kShortQMax);
+  }();
+  return q;
+}
+// The short phase trades latency for throughput: a generation of sixteen
+// calls of up to 63 columns takes about 1.5 times as long as one of eight (442
+// against 296 VALU per row at the longest), and pays only while every wave
+// has a next generation to run.  On C2, round A's short runs (36-40 k sides,
+// 2.2-2.5 times the grid's 16 384 slots) gained 7-8 % per launch; round B's
+// (10-12 k sides, 0.6-0.8 times) lost 9 %.  So a
+// short run smaller than short_fill percent of the grid's sixteen-per-wave
+// slots runs eight per wave as before.  BWAGPU_EXT_SHORT_FILL sets the process
+// default.
+#ifndef BWAGPU_EXT_SHORT_FILL_DEFAULT
+#define BWAGPU_EXT_SHORT_FILL_DEFAULT 150
+#endif
+int ext_short_fill_default() {
+  static const int f = [] {
+    const char* e = getenv("BWAGPU_EXT_SHORT_FILL");
+    return std::min(std::max(e && e[0] ? atoi(e) : BWAGPU_EXT_SHORT_FILL_DEFAULT, 0), 100000);
+  }();
+  return f;
+}
+// the threshold a launch runs with: 0 where the short run's buffers (rows for
+// queries up to short_q, as tb_bytes_for sizes them) would not fit the block's
+// LDS; -> the LDS bytes of one wave, the larger of the two runs' needs
+static int side_short_plan(const DevOpt& o, int tb_bytes, int g, int pmax, int short_q, int* tb_short, size_t* wave_lds) {
+  const size_t w1 = side4_wave_lds(tb_bytes, g, pmax);
+  *tb_short = 0;
+  *wave_lds = w1;
+  short_q = std::min(std::max(short_q, 0), kShortQMax);
+  if (short_q == 0) return 0;
+  const int tbs = tb_bytes_for(o, short_q);
+  const size_t w2 = (side4_wave_lds(tbs, kShortG, kShortPmax) + 15) & ~(size_t)15;
+  if ((size_t)(kBlock / 64) * std::max(w1, w2) > 64 * 1024) return 0;
+  *tb_short = tbs;
+  *wave_lds = std::max(w1, w2);
+  return short_q;
+}
+
 // one side launch of the phased extension for list l: G calls per group
 template <int G, int PMAX, bool K8>
 static void launch_side_pair(const DevOpt& o, const DevRef& ref, const DevBatch& b, const SpecArgs& a, int l,
-                             int tb_bytes, hipStream_t st, int grid_cap, int round) {
-  const size_t lds = side4_lds(tb_bytes, G, PMAX);
+                             int tb_bytes, hipStream_t st, int grid_cap, int round, int short_q = 0,
+                             int short_fill = 0) {
+  int tb_short = 0;
+  size_t wave_lds = 0;
+  short_q = side_short_plan(o, tb_bytes, G, PMAX, G == 16 && K8 ? short_q : 0, &tb_short, &wave_lds);
+  const size_t lds = (size_t)(kBlock / 64) * wave_lds;
   const int nb = resident_blocks(spec_side4_kernel<G, PMAX, K8, false>, lds);
   const int gr = round == 2 ? std::min(nb, 64) : std::min(nb, grid_cap);
   hipLaunchKernelGGL((spec_side4_kernel<G, PMAX, K8, false>), dim3(gr), dim3(kBlock), lds, st, o, ref, b, a, l,
-                     tb_bytes);
+                     tb_bytes, (int)wave_lds, short_q, tb_short, short_fill);
   hipLaunchKernelGGL((spec_side4_kernel<G, PMAX, K8, true>), dim3(gr), dim3(kBlock), lds, st, o, ref, b, a, l,
-                     tb_bytes);
+                     tb_bytes, (int)wave_lds, short_q, tb_short, short_fill);
 }
 
 template <int G, int PMAX, bool K8>
@@ -2974,10 +3110,10 @@ static bool launch_sidep_pair(const DevOpt& o, const DevRef& ref, const DevBatch
 // (spec_sort_*) for the task state machine, one list per side in its query
 // length order (spec_sort2_*) for the phased launches
 static void launch_sort(const DevOpt& o, const DevBatch& b, const SpecArgs& a, int round, bool phased, int bin0,
-                        int nbins, hipStream_t st) {
+                        int nbins, hipStream_t st, int short_q = 0) {
   if (phased) {
     hipLaunchKernelGGL(spec_sort2_count, dim3(256, nbins), dim3(256), 0, st, b, a, round, bin0);
-    hipLaunchKernelGGL(spec_sort2_scan, dim3(2 * nbins), dim3(256), 0, st, a, round, bin0, nbins);
+    hipLaunchKernelGGL(spec_sort2_scan, dim3(2 * nbins), dim3(256), 0, st, a, round, bin0, nbins, short_q);
     hipLaunchKernelGGL(spec_sort2_scatter, dim3(256, nbins), dim3(256), 0, st, o, b, a, round, bin0);
   } else {
     hipLaunchKernelGGL(spec_sort_count, dim3(256, nbins), dim3(256), 0, st, b, a, round, bin0);
@@ -3003,10 +3139,17 @@ static void launch_ext_round(const DevOpt& o, const DevRef& ref, const DevBatch&
   const size_t lds2 = quad ? ext4_lds(tb_bytes, 32) : ext2_lds(tb_bytes);
   const int pm = quad ? ext_phased_mask() : 0;
   const bool p0 = pm & 1, p1 = (pm >> 1) & 1;
+  // the first bin's short run: only where its eight-per-wave side kernel runs
+  int short_q = 0;
+  if (p0 && oct) {
+    int tbs;
+    size_t wl;
+    short_q = side_short_plan(o, tb_bytes, 16, kSpecBinLen[0] / 16, ss.short_q, &tbs, &wl);
+  }
   if (!bin1 || p0 == p1) {
-    launch_sort(o, b, a, round, p0, 0, bin1 ? 2 : 1, st);
+    launch_sort(o, b, a, round, p0, 0, bin1 ? 2 : 1, st, short_q);
   } else {
-    launch_sort(o, b, a, round, p0, 0, 1, st);
+    launch_sort(o, b, a, round, p0, 0, 1, st, short_q);
     launch_sort(o, b, a, round, p1, 1, 1, st);
   }
   const int cap = ext2_grid(1 << 30, true);
@@ -3015,7 +3158,8 @@ static void launch_ext_round(const DevOpt& o, const DevRef& ref, const DevBatch&
   if (p0) {
     if (oct) {
       if (!launch_sidep_pair<16, kSpecBinLen[0] / 16, true>(o, ref, b, a, l + 0, tb_bytes, st, cap, round))
-        launch_side_pair<16, kSpecBinLen[0] / 16, true>(o, ref, b, a, l + 0, tb_bytes, st, cap, round);
+        launch_side_pair<16, kSpecBinLen[0] / 16, true>(o, ref, b, a, l + 0, tb_bytes, st, cap, round, short_q,
+                                                        ss.short_fill);
     } else if (key8) launch_side_pair<32, kSpecBinLen[0] / 32, true>(o, ref, b, a, l + 0, tb_bytes, st, cap, round);
     else launch_side_pair<32, kSpecBinLen[1] / 32, false>(o, ref, b, a, l + 0, tb_bytes, st, cap, round);
   } else if (oct) {

@@ -309,6 +309,18 @@ class Engine:
         """this context's extension form (bwagpu_ctx_ext_form); -> the previous one"""
         return self.lib.bwagpu_ctx_ext_form(self.ctx, int(form))
 
+    def ext_short(self, q: int = -1) -> int:
+        """this context's short-side threshold (bwagpu_ctx_ext_short): sides with
+        a query of 1 .. q bases run sixteen per wave in the eight-per-wave
+        phased extension; 0 = off, -1 = query; -> the previous value"""
+        return self.lib.bwagpu_ctx_ext_short(self.ctx, int(q))
+
+    def ext_short_fill(self, percent: int = -1) -> int:
+        """the smallest short run that takes the short phase, in percent of the
+        launch's sixteen-per-wave call slots (bwagpu_ctx_ext_short_fill; 0 =
+        every short run); -> the previous value"""
+        return self.lib.bwagpu_ctx_ext_short_fill(self.ctx, int(percent))
+
     def row_bound(self, on: int = -1) -> int:
         """this context's row bound in the packed extension kernels
         (bwagpu_ctx_row_bound, default on); -> the previous setting"""

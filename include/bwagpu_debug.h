@@ -85,6 +85,30 @@ int bwagpu_prof_read(bwagpu_ctx_t *ctx, double *total_ms, int32_t *launches);
    Both return the previous form; form < 0 only queries. */
 int bwagpu_debug_ext_form(int form);
 int bwagpu_ctx_ext_form(bwagpu_ctx_t *ctx, int form);
+/* the short-side threshold of the eight-per-wave phased extension (form 0,
+   first length bin): a task side whose query has 1 .. q bases runs in groups
+   of eight lanes, sixteen calls per wave, after the longer sides of its launch
+   (the same kernel; no further launch).  q = 0: off, every side eight per
+   wave; 1 .. 63 otherwise (a larger q counts as 63); q < 0 only queries.
+   Returns the previous value.  A context starts with BWAGPU_EXT_SHORT_Q if
+   set, else the compiled default.  A launch whose short buffers would not fit
+   the workgroup's LDS runs with 0.  Results do not depend on it. */
+int bwagpu_ctx_ext_short(bwagpu_ctx_t *ctx, int q);
+/* ... and the smallest short run that takes the short phase, in percent of the
+   launch's sixteen-per-wave call slots (16 x the grid's waves): a smaller run
+   leaves fewer waves busy for longer generations than eight per wave would, so
+   it runs eight per wave as before.  0: every short run takes the short phase
+   (tests of small batches).  percent < 0 only queries; returns the previous
+   value.  A context starts with BWAGPU_EXT_SHORT_FILL if set, else the compiled
+   default. */
+int bwagpu_ctx_ext_short_fill(bwagpu_ctx_t *ctx, int percent);
+/* diagnostics of the last device-entry batch on `stream` (waits for it), out: 9
+   entries.  out[0] = the task sides run in the short phase, all rounds
+   (bwagpu_debug_spec_counters' eight words are a fixed layout its callers size
+   their buffers by, so this counter has an entry of its own); out[1..4] = round
+   A's first-bin side lists: left sides, of them longer than the threshold (0
+   with the short phase off), right sides, of them longer; out[5..8] = round B's */
+int bwagpu_debug_spec_short(bwagpu_ctx_t *ctx, void *stream, int64_t *out);
 /* the packed extension kernels' row bound (default on): a ksw_extend2 call
    ends once no later target row can change its score, qle, tle, gtle, gscore
    or max_off (every later cell is bounded by a stored value plus max(mat) per
