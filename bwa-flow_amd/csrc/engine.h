@@ -7,6 +7,7 @@
 #include "bwagpu.h"
 #include "bwagpu_debug.h"
 #include "pure.h"
+#include "spec_plan.h"
 
 namespace bwagpu {
 
@@ -114,10 +115,7 @@ struct SeedExt {
                                      // calls = ksw_extend2 calls + 1, so 0 = not computed
 };  // 48 B; the per-batch memset 0 marks every slot "not computed"
 
-// extension task lists: 3 length classes (kernel columns per lane) x 3 rounds
-constexpr int kSpecBins = 3;                           // lq <= 160 / <= 256 / <= 1023
-// (160: the pair kernel's first bin needs CPL <= 5 = 160 / 32; 2x150 reads all fall in it)
-constexpr int kSpecBinLen[kSpecBins] = {160, 256, 1023};
+// extension task lists: kSpecBins length classes (spec_plan.h) x 3 rounds
 constexpr int kSpecRounds = 3;                         // A, B, C
 constexpr int kOrderLane = 8;                          // chains up to this many seeds are ordered by their spec_chain lane
 constexpr int kSelLight = 64;                          // reads with more seeds go first
@@ -241,10 +239,8 @@ int set_ext_form(int form);
 int ext_short_default();
 int ext_short_fill_default();
 // the first length bin's extension kernel launch_ext_round picks for `form`
-// and options `o` with target row buffers of tb_bytes: 8 = eight seeds per
-// wave (spec_ext4_kernel<16,10,true>), 4 = four per wave with the 8-bit key
-// (<32,5,true>), 5 = four per wave (<32,8,false>), 2 = two per wave
-// (spec_ext2_kernel<5>)
+// and options `o` with target row buffers of tb_bytes: ext_plan's code
+// (spec_plan.h lists the codes)
 int ext_kernel_for(const DevOpt& o, int form, int tb_bytes);
 hipError_t launch_spec_clear(const SpecArgs& a, int n_reads, int n_seeds, hipStream_t st);
 hipError_t launch_spec_chain2aln(const DevOpt& o, const DevRef& ref, const DevBatch& b, const SpecArgs& a,

@@ -2,15 +2,12 @@
 // bwagpu_chain2aln): extension task rounds on persistent grids
 // (one, two or four ksw_extend2 calls per wave, ksw_dev.h) and the selection
 // passes that replay bwa's sequential seed logic (bwamem.c:641-795) exactly
-// over the precomputed extensions.
-#include "ksw_dev.h"
+// over the precomputed extensions.  The phased extension (the first bin's
+// side kernels and their lists' sort) is a translation unit of its own,
+// spec_side.hip; spec_dev.h has what the two share.
+#include "spec_dev.h"
 
 namespace bwagpu {
-
-// The selection and bookkeeping kernels are latency-bound chains that share
-// CUs with the other caller stream's persistent extension kernel; at wave
-// priority 3 their instructions issue ahead of its (priority 0) waves.
-__device__ __forceinline__ void sel_prio() { __builtin_amdgcn_s_setprio(3); }
 
 // per-read selection trace (bwagpu_debug_set_trace; this file's copy)
 __device__ uint32_t* g_trace = nullptr;
@@ -105,14 +102,6 @@ __global__ void __launch_bounds__(256) spec_chain_kernel(DevOpt o, DevRef ref, D
   }
   const int p = wave_append(&a.ctr[SPC_LONG_N], longc);
   if (p >= 0) a.longc[p] = c;
-}
-
-// rows are triangular: row k holds words w < ceil(k / 64) (only seeds j < k
-// count); tri_off(k) = sum over i < k of ceil(i / 64)
-__host__ __device__ inline int64_t tri_off(int k) {
-  if (k <= 1) return 0;
-  const int64_t q = (k - 1) >> 6;
-  return 32 * q * (q + 1) + (int64_t)(k - 1 - 64 * q) * (q + 1);
 }
 
 // lane per read: length check, and the list of heavy reads (selected first)
@@ -260,112 +249,6 @@ __global__ void __launch_bounds__(kBlock) spec_ext_kernel(DevOpt o, DevRef ref, 
 // Everything below is per lane and uniform over a half; the halves diverge
 // only through EXEC (a half without a left side, a retry or a task waits for
 // the other).
-//
-// Both target windows of the half's seed into its LDS rows (fill_two on 32
-// lanes: 4 loads per side per lane in flight, 128 rows per side per pass).
-template <int G = 32>
-__device__ __forceinline__ void fill_two_half(uint8_t* tbl, int64_t x0l, int nl, uint8_t* tbr, int64_t x0r, int nr,
-                                              const DevRef& ref) {
-  const int r = (int)(threadIdx.x & (G - 1));
-  const int64_t two1 = (ref.l_pac << 1) - 1;
-  const int n = max(nl, nr);
-  for (int base = 0; base < n; base += 4 * G) {
-    uint32_t raw[8];
-    int sh[8], kk[8];
-    bool rev[8];
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-      const bool left = m < 4;
-      const int nn = left ? nl : nr;
-      const int k = min(base + (m & 3) * G + r, max(nn - 1, 0));
-      kk[m] = k;
-      const int64_t x = left ? x0l - k : x0r + k;
-      rev[m] = x >= ref.l_pac;
-      int64_t f = rev[m] ? two1 - x : x;
-      f = f < 0 ? 0 : (f >= ref.l_pac ? ref.l_pac - 1 : f);  // only for an empty side (nn == 0)
-      raw[m] = ref.pac[f >> 2];
-      sh[m] = (int)((~f & 3) << 1);
-    }
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-      const int bse = (raw[m] >> sh[m]) & 3;
-      const uint8_t v = (uint8_t)(rev[m] ? 3 - bse : bse);
-      if (m < 4) {
-        if (nl > 0) tbl[kk[m]] = v;
-      } else {
-        if (nr > 0) tbr[kk[m]] = v;
-      }
-    }
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// The same gather in ONE memory round trip (the packed kernels' task starts):
-// lane r of the group takes rows [r R, r R + R) of each side, R = ceil(n / G)
-// <= 32, i.e. a run of <= 32 consecutive bases of one strand, and loads the
-// three aligned words of the pac that hold them (<= 9 bytes from a word
-// boundary); each row's base is a 2-bit field of those words.  fill_two_half
-// takes 4 rows per side per lane per pass, one dependent round trip per pass
-// (5-6 for a 150 bp read's windows).  A run that leaves the pac's last 12
-// bytes, or would straddle the two strands (a chain window never does), takes
-// the per-row loads of fill_two_half's kind.
-template <int G>
-__device__ __forceinline__ void fill_side_run(uint8_t* tb, int64_t x0, int dir, int k0, int k1, const DevRef& ref,
-                                              int64_t pac_bytes) {
-  if (k1 <= k0) return;
-  const int64_t two1 = (ref.l_pac << 1) - 1;
-  const int64_t xa = x0 + (int64_t)dir * k0, xb = x0 + (int64_t)dir * (k1 - 1);
-  const bool rev = xa >= ref.l_pac;
-  const int64_t fa = rev ? two1 - xa : xa, fb = rev ? two1 - xb : xb;
-  const int64_t fmin = fa < fb ? fa : fb;
-  const int64_t w0 = (fmin >> 2) & ~(int64_t)3;  // first byte of the aligned words
-  const bool fast = (xb >= ref.l_pac) == rev && fmin >= 0 && (fa > fb ? fa : fb) < ref.l_pac && w0 + 12 <= pac_bytes;
-  const int df = (dir > 0) == !rev ? 1 : -1;  // f along the run
-  if (fast) {
-    const uint32_t* pw = reinterpret_cast<const uint32_t*>(ref.pac + w0);
-    const uint32_t d0 = pw[0], d1 = pw[1], d2 = pw[2];
-    const int o0 = (int)(fa - (w0 << 2));  // the first row's base offset in the 48 loaded bases
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-      if (k0 + j >= k1) break;
-      const int o = o0 + df * j;
-      const uint32_t w = o < 16 ? d0 : (o < 32 ? d1 : d2);
-      const int bit = ((o >> 2) & 3) * 8 + 6 - 2 * (o & 3);
-      const uint32_t bse = (w >> bit) & 3u;
-      tb[k0 + j] = (uint8_t)(rev ? 3u - bse : bse);
-    }
-  } else {
-    for (int k = k0; k < k1; ++k) {
-      const int64_t x = x0 + (int64_t)dir * k;
-      const bool rv = x >= ref.l_pac;
-      int64_t f = rv ? two1 - x : x;
-      f = f < 0 ? 0 : (f >= ref.l_pac ? ref.l_pac - 1 : f);
-      const int bse = (ref.pac[f >> 2] >> ((~f & 3) << 1)) & 3;
-      tb[k] = (uint8_t)(rv ? 3 - bse : bse);
-    }
-  }
-}
-
-template <int G>
-__device__ __forceinline__ void fill_two_fast(uint8_t* tbl, int64_t x0l, int nl, uint8_t* tbr, int64_t x0r, int nr,
-                                              const DevRef& ref) {
-  const int n = max(nl, nr);
-  const int R = (n + G - 1) / G;
-  if (R > 32) {  // options with bands wider than the packed kernels' defaults
-    fill_two_half<G>(tbl, x0l, nl, tbr, x0r, nr, ref);
-    return;
-  }
-  const int r = (int)(threadIdx.x & (G - 1));
-  const int64_t pac_bytes = (ref.l_pac >> 2) + 1;  // bwa.c:281-282
-  const int k0 = r * R;
-  fill_side_run<G>(tbl, x0l, -1, k0, min(k0 + R, nl), ref, pac_bytes);
-  fill_side_run<G>(tbr, x0r, 1, k0, min(k0 + R, nr), ref, pac_bytes);
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // One half's task and the state of its extension, in LDS for the whole task:
 // re-read (volatile, LDS address space) around every call, so that none of it
@@ -467,25 +350,6 @@ __device__ __forceinline__ SeedExt extend_seed2(const DevOpt& o, const DevRef& r
   return e;
 }
 
-template <int G = 32>
-__device__ __forceinline__ void store_ext_half(SeedExt* dst, const SeedExt& e) {
-  static_assert(G >= 12 || G == 8, "a SeedExt is 12 words");
-  const int d = (int)(threadIdx.x & (G - 1));
-  const uint32_t* w = reinterpret_cast<const uint32_t*>(&e);
-  uint32_t v = 0;
-#pragma unroll
-  for (int k = 0; k < 12; ++k) v = d == k ? w[k] : v;
-  if constexpr (G == 8) {  // eight lanes: words 0-7, then words 8-11 on the first four
-    reinterpret_cast<uint32_t*>(dst)[d] = v;
-    uint32_t u = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) u = d == k ? w[8 + k] : u;
-    if (d < 4) reinterpret_cast<uint32_t*>(dst)[8 + d] = u;
-  } else {
-    if (d < 12) reinterpret_cast<uint32_t*>(dst)[d] = v;
-  }
-}
-
 // Extension tasks of one list, two per wave: a wave claims two consecutive
 // entries of a shard (one atomic), lanes 0-31 take the first, 32-63 the second.
 // PMAX = the bin's largest CPL: ceil(read length / 32) (qlen + 1 <= read length)
@@ -583,43 +447,6 @@ __device__ __forceinline__ void qtask_start(QTask& t, const DevOpt& o, const Dev
   t.re = t.rbeg + t.len;
   t.cells = t.rows = t.calls = 0;
 }
-
-#ifdef BWAGPU_OCC_DIAG
-// Occupancy of one extend_quad generation (a diagnostic build's counters,
-// bwagpu_debug_occupancy): the wave runs rows until its longest call ends and
-// CPL x G columns per call for its longest query; of those call-slot cells,
-// the ones of calls that already ended, the ones beyond a live call's query,
-// outside ksw's band, and the cells computed.  int64 counters at ctr words
-// 32..47: generations, rows run, call-slot rows, live call rows, slot cells,
-// live slot cells, query cells, computed cells.
-template <int G>
-__device__ __forceinline__ void occ_diag(unsigned long long* acc, const QCall& ca, const QCall& cb, const Tally32& ta,
-                                         const Tally32& tb) {
-  int qm = 0, rm = 0;
-  long long lr = 0, lq = 0, cc = 0;
-#pragma unroll
-  for (int g = 0; g < 64; g += G) {
-    const int qa = __builtin_amdgcn_readlane(ca.qlen, g), qb = __builtin_amdgcn_readlane(cb.qlen, g);
-    const int ra = __builtin_amdgcn_readlane(ta.rows, g), rb = __builtin_amdgcn_readlane(tb.rows, g);
-    qm = max(qm, max(qa, qb));
-    rm = max(rm, max(ra, rb));
-    lr += ra + rb;
-    lq += (long long)ra * (qa + 1) + (long long)rb * (qb + 1);
-    cc += __builtin_amdgcn_readlane(ta.cells, g) + __builtin_amdgcn_readlane(tb.cells, g);
-  }
-  const int cpl = (qm + G) / G;
-  // summed per wave in registers, added to ctr words 32.. once at the kernel's end
-  // (atomics here would put their round trips on the next generation start)
-  acc[0] += 1ull;
-  acc[1] += (unsigned long long)rm;
-  acc[2] += (unsigned long long)rm * (2 * 64 / G);
-  acc[3] += (unsigned long long)lr;
-  acc[4] += (unsigned long long)rm * 128ull * cpl;
-  acc[5] += (unsigned long long)lr * G * cpl;
-  acc[6] += (unsigned long long)lq;
-  acc[7] += (unsigned long long)cc;
-}
-#endif
 
 // the same from the task's FatTask record (spec_sort_scatter)
 template <int G>
@@ -994,22 +821,6 @@ __device__ __forceinline__ int pair_key(const DevBatch& b, const SpecArgs& a, in
   return (kSortKeys - 1) - ((hi >> 3) << 5 | (lo >> 3));
 }
 
-// the task's FatTask record (engine.h): its seed, its chain's window, its read
-__device__ __forceinline__ FatTask fat_task(const DevBatch& b, const SpecArgs& a, int2 tk) {
-  const bwagpu_seed_t sd = a.prog[tk.x];
-  const ChainWin cw = a.win[tk.y];
-  const int rd = a.chain_read[tk.y];
-  FatTask f;
-  f.rbeg = sd.rbeg;
-  f.qoff = b.seq_off[rd];
-  f.pos = tk.x;
-  f.dlo = (int32_t)(sd.rbeg - cw.lo);
-  f.dhi = (int32_t)(cw.hi - sd.rbeg);
-  const int lq = (int)(b.seq_off[rd + 1] - f.qoff);
-  f.qls = (uint32_t)sd.qbeg | (uint32_t)sd.len << 10 | (uint32_t)lq << 20;
-  return f;
-}
-
 __global__ void __launch_bounds__(256) spec_sort_count(DevBatch b, SpecArgs a, int round, int bin0) {
   sel_prio();
   __shared__ int hist[kSortKeys];
@@ -1103,784 +914,41 @@ __global__ void __launch_bounds__(256) spec_sort_scatter(DevBatch b, SpecArgs a,
   }
 }
 
-// ---------------------------------------------- phased extension (round 6)
-// The extension tasks of the first two length bins run as two launches per
-// round: every task's LEFT call(s) (ksw_extend2 with the band retry,
-// bwamem.c:717-751), then every task's RIGHT call(s) (752-792, h0 = the left
-// score).  Each launch takes calls in the order of their own query length
-// (longest first), so the eight calls of a wave have about the same length:
-// with a task's left and right calls in one wave generation after another
-// (spec_ext4_kernel), a wave ran until its longest call ended while shorter
-// ones had ended (25 % of its call-slot cells) and set its columns by its
-// longest query (10 %), tools_dev/occ_diag.py.  Lists: the tasks with a left
-// side (FatTask, key = left query length) and those with a right side; a
-// whole-read seed (neither side) is written by the scatter itself.
-__device__ __forceinline__ int side_key(int qlen) { return 255 - min(qlen, 255); }  // descending
 
-__global__ void __launch_bounds__(256) spec_sort2_count(DevBatch b, SpecArgs a, int round, int bin0) {
-  sel_prio();
-  __shared__ int hist[2][256];
-  __shared__ int tot[2];
-  const int bin = bin0 + (int)blockIdx.y;
-  const int list = round * kSpecBins + bin;
-  int32_t* ghL = a.sorth + (round * 2 + bin) * kSortKeys;
-  int32_t* ghR = ghL + kSortWordsR;
-  for (int k = threadIdx.x; k < 2 * 256; k += 256) hist[k >> 8][k & 255] = 0;
-  if (threadIdx.x < 2) tot[threadIdx.x] = 0;
-  __syncthreads();
-  const int n = __hip_atomic_load(&a.ctr[SPC_CNT + list], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const int2* tl = a.tasks + spec_list_off(list, b.n_chains, b.n_seeds);
-  const int chunk = (n + (int)gridDim.x - 1) / (int)gridDim.x;
-  const int i0 = (int)blockIdx.x * chunk, i1 = min(n, i0 + chunk);
-  for (int i = i0 + (int)threadIdx.x; i < i1; i += 256) {
-    const FatTask f = fat_task(b, a, tl[i]);
-    const int qb = (int)(f.qls & 1023u), ln = (int)((f.qls >> 10) & 1023u), lq = (int)(f.qls >> 20);
-    const int qr = lq - qb - ln;
-    if (qb > 0) atomicAdd(&hist[0][side_key(qb)], 1);
-    if (qr > 0) atomicAdd(&hist[1][side_key(qr)], 1);
-  }
-  __syncthreads();
-  for (int k = threadIdx.x; k < 2 * 256; k += 256) {
-    const int c = hist[k >> 8][k & 255];
-    if (c) {
-      atomicAdd((k >> 8) ? &ghR[k & 255] : &ghL[k & 255], c);
-      atomicAdd(&tot[k >> 8], c);
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < 2 && tot[threadIdx.x])
-    atomicAdd(&a.ctr[(threadIdx.x ? SPC_RCNT : SPC_LCNT) + list], tot[threadIdx.x]);
+// a bin's list in pair order (the task kernels EXT2 / EXT4)
+static void launch_task_sort(const ExtRound& r, int bin0, int nbins) {
+  hipLaunchKernelGGL(spec_sort_count, dim3(256, nbins), dim3(256), 0, r.st, r.b, r.a, r.round, bin0);
+  hipLaunchKernelGGL(spec_sort_scan, dim3(nbins), dim3(256), 0, r.st, r.a, r.round, bin0);
+  hipLaunchKernelGGL(spec_sort_scatter, dim3(256, nbins), dim3(256), 0, r.st, r.b, r.a, r.round, bin0);
 }
 
-// exclusive scan of the 256 keys of each (side, bin) histogram: one block each
-// (bins bin0 .. bin0 + nbins - 1).  short_q > 0: the first bin's lists get a
-// short run, the sides with a query of up to short_q bases; its first position
-// (= the sides with a longer query: the list is in descending length order)
-// goes to the list's SPC_LLONG / SPC_RLONG word here, before the scatter turns
-// the key positions into cursors.
-__global__ void __launch_bounds__(256) spec_sort2_scan(SpecArgs a, int round, int bin0, int nbins, int short_q) {
-  sel_prio();
-  __shared__ int part[256];
-  const int bin = bin0 + (int)blockIdx.x % nbins, side = (int)blockIdx.x / nbins;
-  int32_t* gh = a.sorth + (round * 2 + bin) * kSortKeys + side * kSortWordsR;
-  const int t = (int)threadIdx.x;
-  const int v = gh[t];
-  part[t] = v;
-  __syncthreads();
-  for (int o = 1; o < 256; o <<= 1) {
-    const int x = t >= o ? part[t - o] : 0;
-    __syncthreads();
-    part[t] += x;
-    __syncthreads();
-  }
-  gh[t] = part[t] - v;  // the key's first position (a cursor from here on)
-  if (short_q > 0 && bin == 0 && t == side_key(short_q))
-    a.ctr[(side ? SPC_RLONG : SPC_LLONG) + round * kSpecBins + bin] = part[t] - v;
+// one launch of a task kernel (EXT2 / EXT4) for one list
+template <class K>
+static void launch_task(K kernel, size_t lds, const ExtRound& r, int list, bool quad) {
+  const int nb = resident_blocks(kernel, lds);
+  const int gr = r.round == 2 ? std::min(nb, 64) : ext2_grid(nb, quad);
+  hipLaunchKernelGGL(kernel, dim3(gr), dim3(kBlock), lds, r.st, r.o, r.ref, r.b, r.a, list, r.tb_bytes);
 }
 
-__global__ void __launch_bounds__(256) spec_sort2_scatter(DevOpt o, DevBatch b, SpecArgs a, int round, int bin0) {
-  sel_prio();
-  __shared__ int cnt[2][256];
-  const int bin = bin0 + (int)blockIdx.y;
-  const int list = round * kSpecBins + bin;
-  int32_t* ghL = a.sorth + (round * 2 + bin) * kSortKeys;
-  int32_t* ghR = ghL + kSortWordsR;
-  for (int k = threadIdx.x; k < 2 * 256; k += 256) cnt[k >> 8][k & 255] = 0;
-  __syncthreads();
-  const int n = __hip_atomic_load(&a.ctr[SPC_CNT + list], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const size_t off = spec_list_off(list, b.n_chains, b.n_seeds);
-  const int2* tl = a.tasks + off;
-  FatTask* foL = a.ftask + off;
-  FatTask* foR = a.ftaskR + off;
-  const int chunk = (n + (int)gridDim.x - 1) / (int)gridDim.x;
-  const int i0 = (int)blockIdx.x * chunk, i1 = min(n, i0 + chunk);
-  constexpr int kPer = 8;  // entries per thread held across the barrier
-  int kl[kPer], kr[kPer], rl[kPer], rr[kPer];
-  FatTask ft[kPer];
-  for (int base = i0; base < i1; base += 256 * kPer) {
-#pragma unroll
-    for (int m = 0; m < kPer; ++m) {
-      const int i = base + m * 256 + (int)threadIdx.x;
-      kl[m] = kr[m] = -1;
-      if (i < i1) {
-        ft[m] = fat_task(b, a, tl[i]);
-        const int qb = (int)(ft[m].qls & 1023u), ln = (int)((ft[m].qls >> 10) & 1023u), lq = (int)(ft[m].qls >> 20);
-        const int qr = lq - qb - ln;
-        if (qb > 0) {
-          kl[m] = side_key(qb);
-          rl[m] = atomicAdd(&cnt[0][kl[m]], 1);
-        }
-        if (qr > 0) {
-          kr[m] = side_key(qr);
-          rr[m] = atomicAdd(&cnt[1][kr[m]], 1);
-        }
-        if (qb == 0 && qr == 0) {  // a whole-read seed (bwamem.c:753, 781): no ksw_extend2 call
-          SeedExt e;
-          e.rb = ft[m].rbeg;
-          e.re = ft[m].rbeg + ln;
-          e.qb = 0;
-          e.qe = lq;
-          e.score = e.truesc = ln * o.a;
-          e.w = o.w;
-          e.cells = e.rows = 0;
-          e.calls = 1;
-          a.ext[ft[m].pos] = e;
-        }
-      }
-    }
-    __syncthreads();
-    for (int k = threadIdx.x; k < 2 * 256; k += 256) {
-      const int c = cnt[k >> 8][k & 255];
-      cnt[k >> 8][k & 255] = c ? atomicAdd((k >> 8) ? &ghR[k & 255] : &ghL[k & 255], c) : 0;  // this pass's range
-    }
-    __syncthreads();
-#pragma unroll
-    for (int m = 0; m < kPer; ++m) {
-      if (kl[m] >= 0) foL[cnt[0][kl[m]] + rl[m]] = ft[m];
-      if (kr[m] >= 0) foR[cnt[1][kr[m]] + rr[m]] = ft[m];
-    }
-    __syncthreads();
-    for (int k = threadIdx.x; k < 2 * 256; k += 256) cnt[k >> 8][k & 255] = 0;
-    __syncthreads();
+// the task kernels compiled are exactly these cases
+static void launch_task_bin(const ExtBin& k, const ExtRound& r, int list, bool quad) {
+  const int tb = r.tb_bytes;
+  switch (ext_key(k.family, k.G, k.PMAX, k.K8)) {
+    // eight per wave, the row-max key widened per call (H may reach 256 and more)
+    case ext_key(EXT4, 16, 16, false): return launch_task(spec_ext4_kernel<16, 16, false>, ext4_lds(tb, 16), r, list, quad);
+    case ext_key(EXT4, 32, 8, false): return launch_task(spec_ext4_kernel<32, 8, false>, ext4_lds(tb, 32), r, list, quad);
+    case ext_key(EXT2, 32, 5, false): return launch_task(spec_ext2_kernel<5>, ext2_lds(tb), r, list, quad);
+    case ext_key(EXT2, 32, 8, false): return launch_task(spec_ext2_kernel<8>, ext2_lds(tb), r, list, quad);
+    default: abort();  // ext_plan names no other task kernel (tests/cpp/ext_plan_asan.cpp)
   }
 }
 
-// One side of a task in flight (LDS, per sub-slot, between its calls).
-struct SideTask {
-  int64_t rbeg, qoff, rb;
-  int32_t pos, dlo, dhi, qbeg, len, lq;
-  int32_t tt, score, h0, truesc, qb, aw0, cells, rows, calls, pad_;
-};
-static_assert(sizeof(SideTask) <= 96, "SideTask layout");
-constexpr int kSideLds = 96;
-typedef __attribute__((address_space(3))) SideTask LdsS;
-#define SIDE_FIELDS(X) X(rbeg) X(qoff) X(rb) X(pos) X(dlo) X(dhi) X(qbeg) X(len) X(lq) X(tt) X(score) X(h0) \
-  X(truesc) X(qb) X(aw0) X(cells) X(rows) X(calls)
-__device__ __forceinline__ void spark(LdsS* p, const SideTask& t) {
-#define X(f) p->f = t.f;
-  SIDE_FIELDS(X)
-#undef X
-  asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ SideTask sload(LdsS* p) {
-  asm volatile("" ::: "memory");
-  SideTask t;
-#define X(f) t.f = p->f;
-  SIDE_FIELDS(X)
-#undef X
-  return t;
-}
-#undef SIDE_FIELDS
-
-// a sub-slot's start: the side's target rows into its LDS buffer, the state
-// of the side's first call (a right side reads what the left launch left in
-// the seed's SeedExt slot)
-template <int G, bool RIGHT>
-__device__ __forceinline__ void side_start(SideTask& t, const DevOpt& o, const DevRef& ref, const SpecArgs& a,
-                                           const FatTask& f, uint8_t* tb) {
-  t.rbeg = f.rbeg;
-  t.qoff = f.qoff;
-  t.pos = f.pos;
-  t.dlo = f.dlo;
-  t.dhi = f.dhi;
-  t.qbeg = (int)(f.qls & 1023u);
-  t.len = (int)((f.qls >> 10) & 1023u);
-  t.lq = (int)(f.qls >> 20);
-  t.tt = 0;
-  const int64_t pac_bytes = (ref.l_pac >> 2) + 1;
-  const int r = (int)(threadIdx.x & (G - 1));
-  if constexpr (!RIGHT) {
-    const int n = rows_needed(o, t.qbeg, t.dlo, o.w << 1, o.pen_clip5);
-    const int R = (n + G - 1) / G;
-    if (R <= 32) fill_side_run<G>(tb, t.rbeg - 1, -1, r * R, min(r * R + R, n), ref, pac_bytes);
-    else fill_two_half<G>(tb, t.rbeg - 1, n, tb, 0, 0, ref);
-    t.score = -1;  // bwamem.c:753 (a left side: the retry test compares with -1)
-    t.h0 = t.len * o.a;
-    t.truesc = -1;
-    t.qb = 0;
-    t.rb = t.rbeg;
-    t.aw0 = o.w;
-    t.cells = t.rows = t.calls = 0;
-  } else {
-    const int64_t x0 = t.rbeg + t.len;
-    const int qr = t.lq - t.qbeg - t.len;
-    const int n = rows_needed(o, qr, (int)(t.rbeg + t.dhi - x0), o.w << 1, o.pen_clip3);
-    const int R = (n + G - 1) / G;
-    if (R <= 32) fill_side_run<G>(tb, x0, 1, r * R, min(r * R + R, n), ref, pac_bytes);
-    else fill_two_half<G>(tb, 0, 0, tb, x0, n, ref);
-    if (t.qbeg > 0) {  // the left launch's result (the same wave wrote... another wave did: SeedExt slot)
-      const SeedExt e = a.ext[t.pos];
-      t.score = e.score;
-      t.truesc = e.truesc;
-      t.qb = e.qb;
-      t.rb = e.rb;
-      t.aw0 = e.w;
-      t.cells = e.cells;
-      t.rows = e.rows;
-      t.calls = e.calls;
-    } else {
-      t.score = t.truesc = t.len * o.a;  // bwamem.c:753
-      t.qb = 0;
-      t.rb = t.rbeg;
-      t.aw0 = o.w;
-      t.cells = t.rows = t.calls = 0;
-    }
-    t.h0 = t.score;  // sc0 (bwamem.c:761)
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-template <bool RIGHT>
-__device__ __forceinline__ QCall side_call(const SideTask& t, const DevOpt& o, const uint8_t* seq, const uint8_t* tb) {
-  QCall q;
-  if constexpr (!RIGHT) {
-    q.qlen = t.qbeg;
-    q.tlen = t.dlo;
-    q.qa = t.qbeg - 1;
-    q.qd = -1;
-    q.eb = o.pen_clip5;
-  } else {
-    const int64_t x0 = t.rbeg + t.len;
-    q.qlen = t.lq - t.qbeg - t.len;
-    q.tlen = (int)(t.rbeg + t.dhi - x0);
-    q.qa = t.qbeg + t.len;
-    q.qd = 1;
-    q.eb = o.pen_clip3;
-  }
-  q.h0 = t.h0;
-  q.w = o.w << t.tt;
-  q.zdrop = o.zdrop;
-  q.q = seq + t.qoff;
-  q.tb = tb;
-  q.tlen = rows_needed(o, q.qlen, q.tlen, q.w, q.eb);  // as qtask_call
-  return q;
-}
-
-// the call's result (bwamem.c:737-751 / 770-792); true = the side is done,
-// its result written to the seed's SeedExt slot (partial after a left side
-// with a right side to come, else final)
-template <int G, bool RIGHT>
-__device__ __forceinline__ bool side_advance(SideTask& t, const DevOpt& o, const SpecArgs& a, const ExtOut& x,
-                                             const Tally32& tl, long long& spec_cells) {
-  t.cells += tl.cells;
-  t.rows += tl.rows;
-  t.calls += tl.calls;
-  const int prev = t.score;
-  t.score = x.score;
-  const int aw = o.w << t.tt;
-  if (t.tt == 0 && !(x.score == prev || x.max_off < (aw >> 1) + (aw >> 2))) {  // the band retry (MAX_BAND_TRY)
-    t.tt = 1;
-    return false;
-  }
-  const int eb = RIGHT ? o.pen_clip3 : o.pen_clip5;
-  const bool local = x.gscore <= 0 || x.gscore <= x.score - eb;
-  SeedExt e;
-  if constexpr (!RIGHT) {
-    const int qr = t.lq - t.qbeg - t.len;
-    e.rb = t.rbeg - (local ? x.tle : x.gtle);
-    e.qb = local ? t.qbeg - x.qle : 0;
-    e.score = t.score;
-    e.truesc = local ? x.score : x.gscore;
-    if (qr != 0) {  // partial: the right launch goes on from here
-      e.re = 0;
-      e.qe = 0;
-      e.w = aw;
-      e.cells = t.cells;
-      e.rows = t.rows;
-      e.calls = t.calls;
-    } else {
-      e.re = t.rbeg + t.len;
-      e.qe = t.lq;
-      e.w = max(aw, o.w);
-      e.cells = t.cells;
-      e.rows = t.rows;
-      e.calls = t.calls + 1;  // + 1: a computed slot is never all-zero
-      spec_cells += t.cells;
-    }
-  } else {
-    e.rb = t.rb;
-    e.qb = t.qb;
-    e.qe = local ? t.qbeg + t.len + x.qle : t.lq;
-    e.re = t.rbeg + t.len + (local ? x.tle : x.gtle);
-    e.score = t.score;
-    e.truesc = t.truesc + (local ? x.score : x.gscore) - t.h0;
-    e.w = max(t.aw0, aw);
-    e.cells = t.cells;
-    e.rows = t.rows;
-    e.calls = t.calls + 1;
-    spec_cells += t.cells;
-  }
-  store_ext_half<G>(a.ext + t.pos, e);
-  return true;
-}
-
-// a side's query bytes into LDS in column order (qd[j] = column j), so the DP
-// has no global load (its prologue read them from HBM: a dependent round trip
-// per generation)
-template <int G, bool RIGHT>
-__device__ __forceinline__ void side_query(const DevBatch& b, const FatTask& f, uint8_t* qd, int qb) {
-  const int r = (int)(threadIdx.x & (G - 1));
-  const int qbeg = (int)(f.qls & 1023u), len = (int)((f.qls >> 10) & 1023u), lq = (int)(f.qls >> 20);
-  const int qlen = min(RIGHT ? lq - qbeg - len : qbeg, qb);
-  const uint8_t* q = b.seq + f.qoff + (RIGHT ? qbeg + len : qbeg - 1);
-  for (int j = r; j < qlen; j += G) qd[j] = q[RIGHT ? j : -j];
-}
-
-// The phased extension's loop over one run of a side list: 128 / G calls per
-// wave (G = 16: eight, 32: four, 8: sixteen) in the
-// packed 16-bit DP (extend_quad), claimed in the list's order (the side's
-// query length, longest first) from the run's own sharded heads.  wlds = the
-// wave's own LDS slice, cut per group: A's and B's target rows (tb_bytes
-// each), their states, their query bytes.  Returns the sides it started.
-template <int G, int PMAX, bool K8, bool RIGHT>
-__device__ __forceinline__ int side_loop(const DevOpt& o, const DevRef& ref, const DevBatch& b, const SpecArgs& a,
-                                         const FatTask* fl, int n, int32_t* heads, uint8_t* wlds, int tb_bytes,
-                                         long long& spec_cells
-#ifdef BWAGPU_OCC_DIAG
-                                         , unsigned long long* tw, unsigned long long* occ
-#endif
-) {
-  constexpr uint64_t kLead =
-      G == 8 ? 0x0101010101010101ull : (G == 16 ? 0x0001000100010001ull : 0x0000000100000001ull);
-  const uint64_t below = kLead & ((1ull << ((int)threadIdx.x & (64 - G))) - 1);
-  constexpr int QB = PMAX * G;
-  uint8_t* const ta_ = wlds + (size_t)((threadIdx.x & 63) / G) * (2 * (size_t)tb_bytes + 2 * kSideLds + 2 * QB);
-  uint8_t* const tb_ = ta_ + tb_bytes;
-  LdsS* const sa = (LdsS*)(tb_ + tb_bytes);
-  LdsS* const sb = (LdsS*)(tb_ + tb_bytes + kSideLds);
-  uint8_t* const qa_ = tb_ + tb_bytes + 2 * kSideLds;
-  uint8_t* const qb_ = qa_ + QB;
-  ShardQ qq;
-  qq.init(heads, n);
-  bool ha = false, hb = false, more = n > 0;
-  int started = 0;
-  for (;;) {
-#ifdef BWAGPU_OCC_DIAG
-    const unsigned long long c0 = __builtin_amdgcn_s_memtime();
-#endif
-    if (more) {  // every sub-slot without a call takes the next entry: one claim for the wave
-      const uint64_t na = __builtin_amdgcn_ballot_w64(!ha) & kLead, nb = __builtin_amdgcn_ballot_w64(!hb) & kLead;
-      const int nn = __popcll(na) + __popcll(nb);
-      if (nn > 0) {
-        int m0, cap;
-        if (qq.claim(nn, m0, cap)) {
-          const int ia = m0 + __popcll(na & below) + __popcll(nb & below), ib = ia + (ha ? 0 : 1);
-          if (!ha && ia < cap) {
-            SideTask t;
-            const FatTask f = fl[qq.shard + 8 * ia];
-            side_query<G, RIGHT>(b, f, qa_, QB);
-            side_start<G, RIGHT>(t, o, ref, a, f, ta_);
-            spark(sa, t);
-            ha = true;
-            ++started;
-          }
-          if (!hb && ib < cap) {
-            SideTask t;
-            const FatTask f = fl[qq.shard + 8 * ib];
-            side_query<G, RIGHT>(b, f, qb_, QB);
-            side_start<G, RIGHT>(t, o, ref, a, f, tb_);
-            spark(sb, t);
-            hb = true;
-            ++started;
-          }
-        } else {
-          more = false;
-        }
-      }
-    }
-#ifdef BWAGPU_OCC_DIAG
-    const unsigned long long c1 = __builtin_amdgcn_s_memtime();
-    tw[0] += c1 - c0;
-#endif
-    if (!__builtin_amdgcn_ballot_w64(ha || hb)) {
-      if (!more) break;
-      continue;
-    }
-    QCall ca = quad_idle(qa_, ta_), cb = quad_idle(qb_, tb_);  // every query pointer in LDS
-    if (ha) {
-      ca = side_call<RIGHT>(sload(sa), o, b.seq, ta_);
-      ca.q = qa_;
-      ca.qa = 0;
-      ca.qd = 1;
-    }
-    if (hb) {
-      cb = side_call<RIGHT>(sload(sb), o, b.seq, tb_);
-      cb.q = qb_;
-      cb.qa = 0;
-      cb.qd = 1;
-    }
-    ExtOut xa, xb;
-    Tally32 tla{0, 0, 0}, tlb{0, 0, 0};
-#ifdef BWAGPU_OCC_DIAG
-    const unsigned long long c2 = __builtin_amdgcn_s_memtime();
-    tw[1] += c2 - c1;
-#endif
-    extend_quad_dispatch<G, PMAX, K8>(o, ca, cb, xa, xb, tla, tlb);
-#ifdef BWAGPU_OCC_DIAG
-    const unsigned long long c3 = __builtin_amdgcn_s_memtime();
-    tw[2] += c3 - c2;
-    occ_diag<G>(occ, ca, cb, tla, tlb);
-#endif
-    if (ha) {
-      SideTask t = sload(sa);
-      if (side_advance<G, RIGHT>(t, o, a, xa, tla, spec_cells)) ha = false;
-      else spark(sa, t);
-    }
-    if (hb) {
-      SideTask t = sload(sb);
-      if (side_advance<G, RIGHT>(t, o, a, xb, tlb, spec_cells)) hb = false;
-      else spark(sb, t);
-    }
-#ifdef BWAGPU_OCC_DIAG
-    tw[3] += __builtin_amdgcn_s_memtime() - c3;
-#endif
-  }
-  return started;
-}
-
-// the short phase's groups and columns: eight lanes, queries up to 63
-constexpr int kShortG = 8, kShortPmax = 8, kShortQMax = kShortG * kShortPmax - 1;
-
-// LDS of one wave of the side kernel: 64 / g groups of two target row buffers,
-// two states and two query buffers
-static size_t side4_wave_lds(int tb_bytes, int g, int pmax) {
-  return (size_t)(64 / g) * (2 * (size_t)tb_bytes + 2 * kSideLds + 2 * (size_t)pmax * g);
-}
-
-// The phased extension's kernel: one side (RIGHT = false: left calls, true:
-// right calls) of the tasks of one list.  The list is sorted by the side's
-// query length, longest first: entries [0, n_long) have a query longer than
-// short_q and run eight per wave (G = 16) or four (G = 32); the eight-per-wave
-// form then runs the rest, [n_long, n), sixteen per wave in groups of eight
-// lanes (short_q > 0; spec_sort2_scan left n_long in the list's counter word).
-// A wave goes from the first run to the second on its own, when the first
-// run's heads are dry: no launch and no barrier between them.  LDS is cut per
-// wave (wave_lds bytes each, the larger of the two runs' needs), so a wave in
-// the second run never touches a sibling's buffers of the first.
-template <int G, int PMAX, bool K8, bool RIGHT>
-__global__ void __launch_bounds__(kBlock) spec_side4_kernel(DevOpt o, DevRef ref, DevBatch b, SpecArgs a, int list,
-                                                            int tb_bytes, int wave_lds, int short_q, int tb_short,
-                                                            int short_fill) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-  uint8_t* const wlds = lds + (size_t)(threadIdx.x >> 6) * (size_t)wave_lds;
-  const int n = uni(__hip_atomic_load(&a.ctr[(RIGHT ? SPC_RCNT : SPC_LCNT) + list], __ATOMIC_RELAXED,
-                                      __HIP_MEMORY_SCOPE_AGENT));
-  const FatTask* fl = (RIGHT ? a.ftaskR : a.ftask) + spec_list_off(list, b.n_chains, b.n_seeds);
-  constexpr bool kShort = G == 16 && K8;  // the form with a short phase
-  int n_long = n;
-  if constexpr (kShort) {
-    if (short_q > 0) {
-      n_long = min(n, uni(__hip_atomic_load(&a.ctr[(RIGHT ? SPC_RLONG : SPC_LLONG) + list], __ATOMIC_RELAXED,
-                                            __HIP_MEMORY_SCOPE_AGENT)));
-      // a short run that does not fill the grid's sixteen-per-wave slots
-      // short_fill / 100 times over runs eight per wave as before (every wave
-      // decides alike): see launch_side_pair
-      const long long slots = (long long)gridDim.x * (kBlock / 64) * (128 / kShortG);
-      if ((long long)(n - n_long) * 100 < slots * short_fill) n_long = n;
-    }
-  }
-  const int hl = RIGHT ? kSpecRounds * kSpecBins + list : list;
-  long long spec_cells = 0;
-#ifdef BWAGPU_OCC_DIAG
-  unsigned long long tw[6] = {0, 0, 0, 0, 0, 0}, occ[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  (void)side_loop<G, PMAX, K8, RIGHT>(o, ref, b, a, fl, n_long, a.qh + 8 * kQHStride * hl, wlds, tb_bytes, spec_cells,
-                                      tw, occ);
-#else
-  (void)side_loop<G, PMAX, K8, RIGHT>(o, ref, b, a, fl, n_long, a.qh + 8 * kQHStride * hl, wlds, tb_bytes, spec_cells);
-#endif
-  if constexpr (kShort) {
-    if (n_long < n) {
-      int32_t* const hs = a.qh + kQHShort + 8 * kQHStride * hl;
-      long long cells_s = 0;  // group-uniform over eight lanes, not sixteen: added on its own
-#ifdef BWAGPU_OCC_DIAG
-      const int ns = side_loop<kShortG, kShortPmax, true, RIGHT>(o, ref, b, a, fl + n_long, n - n_long, hs, wlds,
-                                                                 tb_short, cells_s, tw, occ);
-#else
-      const int ns = side_loop<kShortG, kShortPmax, true, RIGHT>(o, ref, b, a, fl + n_long, n - n_long, hs, wlds,
-                                                                 tb_short, cells_s);
-#endif
-      if ((threadIdx.x & (kShortG - 1)) == 0 && ns) {
-        atomicAdd(&a.ctr[SPC_SHORT_N], ns);
-        atomicAdd(reinterpret_cast<unsigned long long*>(a.ctr + SPC_SPEC64), (unsigned long long)cells_s);
-      }
-    }
-  }
-#ifdef BWAGPU_OCC_DIAG
-  if ((threadIdx.x & 63) == 0) {
-    for (int k = 0; k < 8; ++k) atomicAdd(reinterpret_cast<unsigned long long*>(a.ctr + 32) + k, occ[k]);
-    for (int k = 0; k < 4; ++k) atomicAdd(reinterpret_cast<unsigned long long*>(a.ctr + 48) + k, tw[k]);
-  }
-#endif
-  if ((threadIdx.x & (G - 1)) == 0 && spec_cells)
-    atomicAdd(reinterpret_cast<unsigned long long*>(a.ctr + SPC_SPEC64), (unsigned long long)spec_cells);
-}
-
-// ------------------------------------ the side kernel with a producer wave
-// spec_side4_kernel's waves spent 17.5 % of their cycles at call starts: the
-// claim, then the FatTask, then the target rows, three dependent round trips
-// with nothing to hide them at one wave per SIMD (tools_dev/occ_diag.py,
-// r06h).  spec_sidep_kernel pairs every DP wave with a producer wave that
-// does only that: every call slot has a second buffer (the side's state, its
-// target rows and its query bytes, all in LDS), and the producer keeps those
-// filled, so a DP wave's next call starts from LDS.  A DP wave claims and
-// fills its own first calls (as spec_side4_kernel) while its producer fills
-// the second buffers.  Buffer b = k * 32 + group * 2 + half (k: which of the
-// slot's two): kBufBusy = the DP wave's, kBufEmpty = the producer's to fill,
-// kBufReady = filled.  A producer raises its `ex` once it leaves (the queue's
-// tail: BWAGPU_SIDEP_RETIRE), after its last kBufReady; the DP wave then
-// claims for itself.
-constexpr int kBufEmpty = 0, kBufReady = 1, kBufBusy = 2;
-__host__ __device__ constexpr int sidep_buf_bytes(int tb_bytes, int qb) { return (tb_bytes + qb + kSideLds + 15) & ~15; }
-
-__device__ __forceinline__ int lds_ld(int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-// a buffer state after every LDS access of this wave before it (the DP's reads
-// of the rows; the producer's writes of them): lgkmcnt only, so that the
-// wave's outstanding global stores (SeedExt) are not waited for
-__device__ __forceinline__ void lds_publish(int* p, int v) {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// a call slot's buffer: target rows (tb_bytes) | query bytes in column order (qb) | SideTask
-template <int G, bool RIGHT>
-__device__ __forceinline__ void side_prep(const DevOpt& o, const DevRef& ref, const DevBatch& b, const SpecArgs& a,
-                                          const FatTask& f, uint8_t* buf, int tb_bytes, int qb) {
-  uint8_t* const qd = buf + tb_bytes;
-  side_query<G, RIGHT>(b, f, qd, qb);
-  SideTask t;
-  side_start<G, RIGHT>(t, o, ref, a, f, buf);
-  spark((LdsS*)(qd + qb), t);
-}
-
-__device__ __forceinline__ FatTask shfl_fat(const FatTask& f, int src) {
-  FatTask g;
-  g.rbeg = (int64_t)((uint64_t)(uint32_t)__shfl((int)(f.rbeg >> 32), src, 64) << 32 | (uint32_t)__shfl((int)f.rbeg, src, 64));
-  g.qoff = (int64_t)((uint64_t)(uint32_t)__shfl((int)(f.qoff >> 32), src, 64) << 32 | (uint32_t)__shfl((int)f.qoff, src, 64));
-  g.pos = __shfl(f.pos, src, 64);
-  g.dlo = __shfl(f.dlo, src, 64);
-  g.dhi = __shfl(f.dhi, src, 64);
-  g.qls = (uint32_t)__shfl((int)f.qls, src, 64);
-  return g;
-}
-
-template <int G, int PMAX>
-static size_t sidep_lds(int tb_bytes) {
-  constexpr int nbuf = 4 * (kBlock / G);
-  return (size_t)nbuf * sidep_buf_bytes(tb_bytes, PMAX * G) + 4 * (size_t)(nbuf + 4);
-}
-
-template <int G, int PMAX, bool K8, bool RIGHT>
-__global__ void __launch_bounds__(2 * kBlock) spec_sidep_kernel(DevOpt o, DevRef ref, DevBatch b, SpecArgs a, int list,
-                                                                int tb_bytes, int retire) {
-  static_assert(G == 16, "a producer wave per DP wave: 2 buffers x 2 halves x 4 groups = 16 buffers");
-  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-  constexpr int QB = PMAX * G;            // query bytes per buffer (the widest call's columns)
-  constexpr int NBUF = 4 * (kBlock / G);  // 64
-  const int SB = sidep_buf_bytes(tb_bytes, QB);
-  int* const st = reinterpret_cast<int*>(lds + (size_t)NBUF * SB);
-  int* const ex = st + NBUF;  // per DP wave: its producer has left
-  for (int k = threadIdx.x; k < NBUF + 4; k += 2 * kBlock) st[k] = k < NBUF / 2 ? kBufBusy : kBufEmpty;
-  __syncthreads();
-  const int n = uni(__hip_atomic_load(&a.ctr[(RIGHT ? SPC_RCNT : SPC_LCNT) + list], __ATOMIC_RELAXED,
-                                      __HIP_MEMORY_SCOPE_AGENT));
-  const FatTask* fl = (RIGHT ? a.ftaskR : a.ftask) + spec_list_off(list, b.n_chains, b.n_seeds);
-  int32_t* const heads = a.qh + 8 * kQHStride * (RIGHT ? kSpecRounds * kSpecBins + list : list);
-  ShardQ qq;
-  qq.init(heads, n);
-#ifdef BWAGPU_OCC_DIAG
-  unsigned long long tw[6] = {0, 0, 0, 0, 0, 0}, occ[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-  const int lane = (int)(threadIdx.x & 63);
-  if (threadIdx.x >= kBlock) {  // ---- a producer wave: DP wave pw's 16 buffers, lane l < 16 = buffer bmap(l)
-    // above the DP wave it shares a SIMD with: the arbiter prefers the older
-    // of two ready waves, and a DP wave is nearly always ready
-    __builtin_amdgcn_s_setprio(2);
-    const int pw = (int)(threadIdx.x - kBlock) >> 6;
-    const auto bmap = [pw](int l) { return (l >> 3) << 5 | (4 * pw + ((l >> 1) & 3)) << 1 | (l & 1); };
-    const uint64_t below = (1ull << lane) - 1;
-    bool more = n > 0;
-    while (more) {
-#ifdef BWAGPU_OCC_DIAG
-      const unsigned long long p0 = __builtin_amdgcn_s_memtime();
-#endif
-      const uint64_t em = __builtin_amdgcn_ballot_w64(lane < 16 && lds_ld(st + bmap(lane & 15)) == kBufEmpty);
-      if (!em) {
-        __builtin_amdgcn_s_sleep(2);
-#ifdef BWAGPU_OCC_DIAG
-        tw[5] += __builtin_amdgcn_s_memtime() - p0;
-#endif
-        continue;
-      }
-      int m0, cap;
-      if (!qq.claim(__popcll(em), m0, cap)) break;
-      const int idx = m0 + __popcll(em & below);
-      const bool mine = ((em >> lane) & 1) && idx < cap;
-      uint64_t v = __builtin_amdgcn_ballot_w64(mine);
-      FatTask f{};
-      if (mine) f = fl[qq.shard + 8 * idx];
-      while (v) {  // four buffers at a time, a group of G lanes each
-        int bsel = -1;
-#pragma unroll
-        for (int g = 0; g < 64 / G; ++g) {
-          const int bq = v ? __builtin_ctzll(v) : -1;
-          v &= v - 1;
-          bsel = lane / G == g ? bq : bsel;
-        }
-        const FatTask g = shfl_fat(f, max(bsel, 0));
-        const int bb = bmap(max(bsel, 0));
-        if (bsel >= 0) side_prep<G, RIGHT>(o, ref, b, a, g, lds + (size_t)bb * SB, tb_bytes, QB);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the buffers' rows, query and state first
-        if (bsel >= 0) __hip_atomic_store(st + bb, kBufReady, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      }
-#ifdef BWAGPU_OCC_DIAG
-      tw[4] += __builtin_amdgcn_s_memtime() - p0;
-#endif
-      // the queue's tail goes to the DP waves' own claims: a call claimed ahead
-      // waits behind its slot's current one while other slots run dry
-      if (cap - m0 - __popcll(em) < retire) break;
-    }
-    lds_publish(ex + pw, 1);
-  } else {  // ---- a DP wave: eight call slots, half A / B of four groups
-    const int gi = (int)threadIdx.x / G, gw = lane / G;
-    const auto bidx = [gi](int h, int k) { return (k << 5) | (gi << 1) | h; };
-    const auto bufp = [&](int h, int k) { return lds + (size_t)bidx(h, k) * SB; };
-    constexpr uint64_t kLead = 0x0001000100010001ull;  // each group's first lane
-    const uint64_t below = kLead & ((1ull << (lane & (64 - G))) - 1);
-    bool ha = false, hb = false, fa = false, fb = false, dry = false;
-    int ka = 0, kb = 0;  // the buffer of the slot's call (or its last one)
-    long long spec_cells = 0;
-    {  // the first calls: this wave's own claim (the producer fills the second buffers meanwhile)
-      int m0, cap;
-      if (n > 0 && qq.claim(2 * (64 / G), m0, cap)) {
-        const int ia = m0 + 2 * gw, ib = ia + 1;
-        if (ia < cap) {
-          side_prep<G, RIGHT>(o, ref, b, a, fl[qq.shard + 8 * ia], bufp(0, 0), tb_bytes, QB);
-          ha = true;
-        }
-        if (ib < cap) {
-          side_prep<G, RIGHT>(o, ref, b, a, fl[qq.shard + 8 * ib], bufp(1, 0), tb_bytes, QB);
-          hb = true;
-        }
-      }
-      lds_publish(st + bidx(0, 0), ha ? kBufBusy : kBufEmpty);  // a slot without a first call: the producer's
-      lds_publish(st + bidx(1, 0), hb ? kBufBusy : kBufEmpty);
-    }
-    for (;;) {
-#ifdef BWAGPU_OCC_DIAG
-      const unsigned long long c0 = __builtin_amdgcn_s_memtime();
-#endif
-      // a slot without a call takes a filled buffer: its other one (filled
-      // while this call ran), else the one it just gave back (the producer may
-      // have refilled that first).  Once the producer has left (`ex`, after
-      // its last kBufReady) and neither is filled, the wave claims for the slot
-      // itself (the queue's tail), into the slot's free buffer.
-      const auto take = [&](int h, int& k, bool& has, bool& own, bool last) {
-        own = false;
-        if (has) return;
-        const int so = lds_ld(st + bidx(h, k ^ 1)), sk = lds_ld(st + bidx(h, k));
-        if (so == kBufReady) {
-          has = true;
-          k ^= 1;
-        } else if (sk == kBufReady) {
-          has = true;
-        } else {
-          own = last;
-        }
-      };
-      for (;;) {
-        const bool last = __hip_atomic_load(ex + (threadIdx.x >> 6), __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != 0;  // before the states
-        bool oa, ob;
-        take(0, ka, ha, oa, last && !fa);
-        take(1, kb, hb, ob, last && !fb);
-        const uint64_t na = __builtin_amdgcn_ballot_w64(oa) & kLead, nb = __builtin_amdgcn_ballot_w64(ob) & kLead;
-        if (na | nb) {
-          int m0, cap;
-          if (!dry && qq.claim(__popcll(na) + __popcll(nb), m0, cap)) {
-            const int ia = m0 + __popcll(na & below) + __popcll(nb & below), ib = ia + (oa ? 1 : 0);
-            if (oa && ia < cap) {
-              side_prep<G, RIGHT>(o, ref, b, a, fl[qq.shard + 8 * ia], bufp(0, ka), tb_bytes, QB);
-              ha = true;
-            }
-            if (ob && ib < cap) {
-              side_prep<G, RIGHT>(o, ref, b, a, fl[qq.shard + 8 * ib], bufp(1, kb), tb_bytes, QB);
-              hb = true;
-            }
-          } else {
-            dry = true;
-            fa = fa || oa;
-            fb = fb || ob;
-          }
-        }
-        if (!__builtin_amdgcn_ballot_w64((!ha && !fa) || (!hb && !fb))) break;
-        if (!(na | nb)) __builtin_amdgcn_s_sleep(1);
-      }
-      if (!__builtin_amdgcn_ballot_w64(ha || hb)) break;
-#ifdef BWAGPU_OCC_DIAG
-      const unsigned long long c1 = __builtin_amdgcn_s_memtime();
-      tw[0] += c1 - c0;
-#endif
-      uint8_t* const pa = bufp(0, ka);
-      uint8_t* const pb = bufp(1, kb);
-      LdsS* const sa = (LdsS*)(pa + tb_bytes + QB);
-      LdsS* const sb = (LdsS*)(pb + tb_bytes + QB);
-      QCall ca = quad_idle(pa + tb_bytes, pa), cb = quad_idle(pb + tb_bytes, pb);  // every query pointer in LDS
-      if (ha) {
-        ca = side_call<RIGHT>(sload(sa), o, b.seq, pa);
-        ca.q = pa + tb_bytes;
-        ca.qa = 0;
-        ca.qd = 1;
-      }
-      if (hb) {
-        cb = side_call<RIGHT>(sload(sb), o, b.seq, pb);
-        cb.q = pb + tb_bytes;
-        cb.qa = 0;
-        cb.qd = 1;
-      }
-      ExtOut xa, xb;
-      Tally32 tla{0, 0, 0}, tlb{0, 0, 0};
-#ifdef BWAGPU_OCC_DIAG
-      const unsigned long long c2 = __builtin_amdgcn_s_memtime();
-      tw[1] += c2 - c1;
-#endif
-      extend_quad_dispatch<G, PMAX, K8>(o, ca, cb, xa, xb, tla, tlb);
-#ifdef BWAGPU_OCC_DIAG
-      const unsigned long long c3 = __builtin_amdgcn_s_memtime();
-      tw[2] += c3 - c2;
-      occ_diag<G>(occ, ca, cb, tla, tlb);
-#endif
-      if (ha) {
-        SideTask t = sload(sa);
-        if (side_advance<G, RIGHT>(t, o, a, xa, tla, spec_cells)) {
-          ha = false;
-          lds_publish(st + bidx(0, ka), kBufEmpty);
-        } else {
-          spark(sa, t);
-        }
-      }
-      if (hb) {
-        SideTask t = sload(sb);
-        if (side_advance<G, RIGHT>(t, o, a, xb, tlb, spec_cells)) {
-          hb = false;
-          lds_publish(st + bidx(1, kb), kBufEmpty);
-        } else {
-          spark(sb, t);
-        }
-      }
-#ifdef BWAGPU_OCC_DIAG
-      tw[3] += __builtin_amdgcn_s_memtime() - c3;
-#endif
-    }
-    if ((threadIdx.x & (G - 1)) == 0 && spec_cells)
-      atomicAdd(reinterpret_cast<unsigned long long*>(a.ctr + SPC_SPEC64), (unsigned long long)spec_cells);
-  }
-#ifdef BWAGPU_OCC_DIAG
-  if (lane == 0) {
-    for (int k = 0; k < 8; ++k) atomicAdd(reinterpret_cast<unsigned long long*>(a.ctr + 32) + k, occ[k]);
-    for (int k = 0; k < 6; ++k) atomicAdd(reinterpret_cast<unsigned long long*>(a.ctr + 48) + k, tw[k]);
-  }
-#endif
+// the third bin: spec_ext_kernel<16>
+static void launch_task_long(const ExtRound& r, int list) {
+  const size_t lds = (size_t)(kBlock / 64) * 2 * r.tb_bytes;
+  const int nb = resident_blocks(spec_ext_kernel<16>, lds);
+  hipLaunchKernelGGL(spec_ext_kernel<16>, dim3(r.round == 2 ? std::min(nb, 64) : nb), dim3(kBlock), lds, r.st, r.o, r.ref,
+                     r.b, r.a, list, r.tb_bytes);
 }
 
 // The pair kernel's grid: its waves pull tasks from the queue, so the grid
@@ -1893,7 +961,7 @@ __global__ void __launch_bounds__(2 * kBlock) spec_sidep_kernel(DevOpt o, DevRef
 // waves per SIMD at 2/CU) run at 1 workgroup per CU: 37.97-38.04 against
 // 36.99-37.17 Mreads/s on C2, C3 0.66 against 0.78-0.79 ms per batch (same
 // box).  BWAGPU_EXT2_BLOCKS_PER_CU overrides both.
-static int ext2_grid(int nb, bool packed) {
+int ext2_grid(int nb, bool packed) {
   static const int env_cu = [] {
     const char* e = getenv("BWAGPU_EXT2_BLOCKS_PER_CU");
     const int v = e ? atoi(e) : 0;
@@ -2975,44 +2043,10 @@ static void launch_select(const DevOpt& o, const DevRef& ref, const DevBatch& b,
   }
 }
 
-// The first two length bins' extension kernel: eight seeds per wave for the
-// first bin and four for the second (spec_ext4_kernel, packed 16-bit DP) when
-// every score of the bin fits the packed ranges, else two per wave
-// (spec_ext2_kernel, 32-bit).  Form 1 (bwagpu_ctx_ext_form, per context)
-// forces two per wave, 2 four per wave in the first bin too (tests, A/B).
-// the phased extension (spec_side4_kernel) per length bin: BWAGPU_EXT_PHASED
-// is a mask (bit 0: the first bin, bit 1: the second); unset = 1.  The second
-// bin (161-256 bp) stays on the task state machine of spec_ext4_kernel by
-// default: its calls run ~250 rows, so the tail of each side launch (one long
-// call on a nearly empty chip) cost more than the phasing saved (C5: 3.42 ms
-// per batch with both bins phased, 2.81 with neither, r06h).
-static int ext_phased_mask() {
-  static const int m = [] {
-    const char* e = getenv("BWAGPU_EXT_PHASED");
-    return e && e[0] ? atoi(e) & 3 : 1;
-  }();
-  return m;
-}
-
-// the phased pair with producer waves (spec_sidep_kernel; the first bin's
-// eight-per-wave form only): BWAGPU_EXT_PRODUCER=1.  Off by default: it lost
-// on every A/B (C2 43.6-47.4 vs 50.9-54.5 Mreads/s)
-static bool ext_producer() {
-  static const bool on = [] {
-    const char* e = getenv("BWAGPU_EXT_PRODUCER");
-    return e && e[0] == '1';
-  }();
-  return on;
-}
+// The extension form (bwagpu_ctx_ext_form, per context; tests, A/B): which
+// kernels a form runs is ext_plan's table (spec_plan.h).
 static std::atomic<int> g_ext_form{0};
-int ext_kernel_for(const DevOpt& o, int form, int tb_bytes) {  // launch_ext_round's choice, first bin
-  const bool quad = form != 1 && quad_scores_ok(o, kSpecBinLen[1]) && quad_rows_ok(o, tb_bytes);
-  const bool key8 = quad && quad_key8_ok(o, kSpecBinLen[0]);
-  const int k = key8 ? (form == 0 ? 8 : 4) : (quad ? 5 : 2);
-  if (!quad || !(ext_phased_mask() & 1)) return k;
-  // the phased pair: 28 with the producer wave (spec_sidep_kernel), 1x spec_side4_kernel
-  return k == 8 && ext_producer() && sidep_lds<16, kSpecBinLen[0] / 16>(tb_bytes) <= 64 * 1024 ? 28 : 10 + k;
-}
+int ext_kernel_for(const DevOpt& o, int form, int tb_bytes) { return ext_plan(o, form, tb_bytes, 0).bin[0].code; }
 int set_ext_form(int form) {  // the default of contexts made later; -> the previous one (form < 0: query only)
   const int prev = g_ext_form.load(std::memory_order_relaxed);
   if (form >= 0) g_ext_form.store(form > 2 ? 1 : form, std::memory_order_relaxed);
@@ -3052,76 +2086,19 @@ int ext_short_fill_default() {
   }();
   return f;
 }
-// the threshold a launch runs with: 0 where the short run's buffers (rows for
-// queries up to short_q, as tb_bytes_for sizes them) would not fit the block's
-// LDS; -> the LDS bytes of one wave, the larger of the two runs' needs
-static int side_short_plan(const DevOpt& o, int tb_bytes, int g, int pmax, int short_q, int* tb_short, size_t* wave_lds) {
-  const size_t w1 = side4_wave_lds(tb_bytes, g, pmax);
-  *tb_short = 0;
-  *wave_lds = w1;
-  short_q = std::min(std::max(short_q, 0), kShortQMax);
-  if (short_q == 0) return 0;
-  const int tbs = tb_bytes_for(o, short_q);
-  const size_t w2 = (side4_wave_lds(tbs, kShortG, kShortPmax) + 15) & ~(size_t)15;
-  if ((size_t)(kBlock / 64) * std::max(w1, w2) > 64 * 1024) return 0;
-  *tb_short = tbs;
-  *wave_lds = std::max(w1, w2);
-  return short_q;
+
+
+// a bin's list sorted as its kernel takes it, and its launch
+static void launch_sort(const ExtBin& k, const ExtRound& r, int bin0, int nbins, int short_q) {
+  if (k.phased) launch_side_sort(r, bin0, nbins, short_q);
+  else launch_task_sort(r, bin0, nbins);
+}
+static void launch_ext_bin(const ExtBin& k, const ExtRound& r, int list, const ExtPlan& p, int short_fill) {
+  if (k.family == SIDE4) launch_side_bin(k, r, list, p, short_fill);
+  else launch_task_bin(k, r, list, p.quad);
 }
 
-// one side launch of the phased extension for list l: G calls per group
-template <int G, int PMAX, bool K8>
-static void launch_side_pair(const DevOpt& o, const DevRef& ref, const DevBatch& b, const SpecArgs& a, int l,
-                             int tb_bytes, hipStream_t st, int grid_cap, int round, int short_q = 0,
-                             int short_fill = 0) {
-  int tb_short = 0;
-  size_t wave_lds = 0;
-  short_q = side_short_plan(o, tb_bytes, G, PMAX, G == 16 && K8 ? short_q : 0, &tb_short, &wave_lds);
-  const size_t lds = (size_t)(kBlock / 64) * wave_lds;
-  const int nb = resident_blocks(spec_side4_kernel<G, PMAX, K8, false>, lds);
-  const int gr = round == 2 ? std::min(nb, 64) : std::min(nb, grid_cap);
-  hipLaunchKernelGGL((spec_side4_kernel<G, PMAX, K8, false>), dim3(gr), dim3(kBlock), lds, st, o, ref, b, a, l,
-                     tb_bytes, (int)wave_lds, short_q, tb_short, short_fill);
-  hipLaunchKernelGGL((spec_side4_kernel<G, PMAX, K8, true>), dim3(gr), dim3(kBlock), lds, st, o, ref, b, a, l,
-                     tb_bytes, (int)wave_lds, short_q, tb_short, short_fill);
-}
-
-template <int G, int PMAX, bool K8>
-static bool launch_sidep_pair(const DevOpt& o, const DevRef& ref, const DevBatch& b, const SpecArgs& a, int l,
-                              int tb_bytes, hipStream_t st, int grid_cap, int round) {
-  const size_t lds = sidep_lds<G, PMAX>(tb_bytes);
-  if (!ext_producer() || lds > 64 * 1024) return false;
-  // the producer leaves its shard's last `retire` entries to the DP waves'
-  // own claims (BWAGPU_SIDEP_RETIRE; 1 024 = one call per call slot of an XCD)
-  static const int retire = [] {
-    const char* e = getenv("BWAGPU_SIDEP_RETIRE");
-    return e && e[0] ? std::max(atoi(e), 0) : 1024;
-  }();
-  const int nb = resident_blocks(spec_sidep_kernel<G, PMAX, K8, false>, lds, 2 * kBlock);
-  const int gr = round == 2 ? std::min(nb, 64) : std::min(nb, grid_cap);
-  hipLaunchKernelGGL((spec_sidep_kernel<G, PMAX, K8, false>), dim3(gr), dim3(2 * kBlock), lds, st, o, ref, b, a, l,
-                     tb_bytes, retire);
-  hipLaunchKernelGGL((spec_sidep_kernel<G, PMAX, K8, true>), dim3(gr), dim3(2 * kBlock), lds, st, o, ref, b, a, l,
-                     tb_bytes, retire);
-  return true;
-}
-
-// the length bins' lists in the order their kernels take them: pair order
-// (spec_sort_*) for the task state machine, one list per side in its query
-// length order (spec_sort2_*) for the phased launches
-static void launch_sort(const DevOpt& o, const DevBatch& b, const SpecArgs& a, int round, bool phased, int bin0,
-                        int nbins, hipStream_t st, int short_q = 0) {
-  if (phased) {
-    hipLaunchKernelGGL(spec_sort2_count, dim3(256, nbins), dim3(256), 0, st, b, a, round, bin0);
-    hipLaunchKernelGGL(spec_sort2_scan, dim3(2 * nbins), dim3(256), 0, st, a, round, bin0, nbins, short_q);
-    hipLaunchKernelGGL(spec_sort2_scatter, dim3(256, nbins), dim3(256), 0, st, o, b, a, round, bin0);
-  } else {
-    hipLaunchKernelGGL(spec_sort_count, dim3(256, nbins), dim3(256), 0, st, b, a, round, bin0);
-    hipLaunchKernelGGL(spec_sort_scan, dim3(nbins), dim3(256), 0, st, a, round, bin0);
-    hipLaunchKernelGGL(spec_sort_scatter, dim3(256, nbins), dim3(256), 0, st, b, a, round, bin0);
-  }
-}
-
+// One round's extension launches, as ext_plan (spec_plan.h) names them.
 // Only the bins the batch's longest read reaches are launched: a persistent
 // grid over an empty list still waits for CU slots that the other caller
 // stream's extension kernel holds, and its stream waits with it.  Round C
@@ -3129,83 +2106,26 @@ static void launch_sort(const DevOpt& o, const DevBatch& b, const SpecArgs& a, i
 // reason.
 static void launch_ext_round(const DevOpt& o, const DevRef& ref, const DevBatch& b, const SpecArgs& a, int round,
                              int tb_bytes, int lq_max, hipStream_t st, const SpecStreams& ss) {
-  const size_t lds = (size_t)(kBlock / 64) * 2 * tb_bytes;
   const int l = round * kSpecBins;
   const bool bin1 = lq_max > kSpecBinLen[0], bin2 = lq_max > kSpecBinLen[1];
-  const int form = ss.form;
-  const bool quad = form != 1 && quad_scores_ok(o, kSpecBinLen[1]) && quad_rows_ok(o, tb_bytes);
-  const auto grid = [round, quad](int nb) { return round == 2 ? std::min(nb, 64) : ext2_grid(nb, quad); };
-  const bool key8 = quad && quad_key8_ok(o, kSpecBinLen[0]), oct = key8 && form == 0;
-  const size_t lds2 = quad ? ext4_lds(tb_bytes, 32) : ext2_lds(tb_bytes);
-  const int pm = quad ? ext_phased_mask() : 0;
-  const bool p0 = pm & 1, p1 = (pm >> 1) & 1;
-  // the first bin's short run: only where its eight-per-wave side kernel runs
-  int short_q = 0;
-  if (p0 && oct) {
-    int tbs;
-    size_t wl;
-    short_q = side_short_plan(o, tb_bytes, 16, kSpecBinLen[0] / 16, ss.short_q, &tbs, &wl);
-  }
-  if (!bin1 || p0 == p1) {
-    launch_sort(o, b, a, round, p0, 0, bin1 ? 2 : 1, st, short_q);
+  const ExtPlan plan = ext_plan(o, ss.form, tb_bytes, ss.short_q);
+  const ExtRound r{o, ref, b, a, round, tb_bytes, st};
+  if (!bin1 || plan.bin[0].phased == plan.bin[1].phased) {
+    launch_sort(plan.bin[0], r, 0, bin1 ? 2 : 1, plan.short_q);
   } else {
-    launch_sort(o, b, a, round, p0, 0, 1, st, short_q);
-    launch_sort(o, b, a, round, p1, 1, 1, st);
+    launch_sort(plan.bin[0], r, 0, 1, plan.short_q);
+    launch_sort(plan.bin[1], r, 1, 1, 0);
   }
-  const int cap = ext2_grid(1 << 30, true);
   const bool prof = ss.pool && *ss.pool_used + 2 <= ss.pool_n;
   if (prof) (void)hipEventRecord(ss.pool[*ss.pool_used], st);
-  if (p0) {
-    if (oct) {
-      if (!launch_sidep_pair<16, kSpecBinLen[0] / 16, true>(o, ref, b, a, l + 0, tb_bytes, st, cap, round))
-        launch_side_pair<16, kSpecBinLen[0] / 16, true>(o, ref, b, a, l + 0, tb_bytes, st, cap, round, short_q,
-                                                        ss.short_fill);
-    } else if (key8) launch_side_pair<32, kSpecBinLen[0] / 32, true>(o, ref, b, a, l + 0, tb_bytes, st, cap, round);
-    else launch_side_pair<32, kSpecBinLen[1] / 32, false>(o, ref, b, a, l + 0, tb_bytes, st, cap, round);
-  } else if (oct) {
-    const size_t lds8 = ext4_lds(tb_bytes, 16);
-    const int nb = resident_blocks(spec_ext4_kernel<16, kSpecBinLen[0] / 16, true>, lds8);
-    hipLaunchKernelGGL((spec_ext4_kernel<16, kSpecBinLen[0] / 16, true>), dim3(grid(nb)), dim3(kBlock), lds8, st, o,
-                       ref, b, a, l + 0, tb_bytes);
-  } else if (key8) {
-    const int nb = resident_blocks(spec_ext4_kernel<32, kSpecBinLen[0] / 32, true>, lds2);
-    hipLaunchKernelGGL((spec_ext4_kernel<32, kSpecBinLen[0] / 32, true>), dim3(grid(nb)), dim3(kBlock), lds2, st, o,
-                       ref, b, a, l + 0, tb_bytes);
-  } else if (quad) {
-    const int nb = resident_blocks(spec_ext4_kernel<32, kSpecBinLen[1] / 32, false>, lds2);
-    hipLaunchKernelGGL((spec_ext4_kernel<32, kSpecBinLen[1] / 32, false>), dim3(grid(nb)), dim3(kBlock), lds2, st, o,
-                       ref, b, a, l + 0, tb_bytes);
-  } else {
-    const int nb = resident_blocks(spec_ext2_kernel<kSpecBinLen[0] / 32>, lds2);
-    hipLaunchKernelGGL(spec_ext2_kernel<kSpecBinLen[0] / 32>, dim3(grid(nb)), dim3(kBlock), lds2, st, o, ref, b, a,
-                       l + 0, tb_bytes);
-  }
+  launch_ext_bin(plan.bin[0], r, l + 0, plan, ss.short_fill);
   if (prof) {
     (void)hipEventRecord(ss.pool[*ss.pool_used + 1], st);
     *ss.pool_used += 2;
   }
   if (!bin1) return;
-  if (p1) {
-    if (form == 0) launch_side_pair<16, kSpecBinLen[1] / 16, false>(o, ref, b, a, l + 1, tb_bytes, st, cap, round);
-    else launch_side_pair<32, kSpecBinLen[1] / 32, false>(o, ref, b, a, l + 1, tb_bytes, st, cap, round);
-  } else if (quad && form == 0) {  // eight per wave, the row-max key widened per call (H may reach 256 and more)
-    const size_t lds8 = ext4_lds(tb_bytes, 16);
-    const int nb = resident_blocks(spec_ext4_kernel<16, kSpecBinLen[1] / 16, false>, lds8);
-    hipLaunchKernelGGL((spec_ext4_kernel<16, kSpecBinLen[1] / 16, false>), dim3(grid(nb)), dim3(kBlock), lds8, st, o,
-                       ref, b, a, l + 1, tb_bytes);
-  } else if (quad) {
-    const int nb = resident_blocks(spec_ext4_kernel<32, kSpecBinLen[1] / 32, false>, lds2);
-    hipLaunchKernelGGL((spec_ext4_kernel<32, kSpecBinLen[1] / 32, false>), dim3(grid(nb)), dim3(kBlock), lds2, st, o,
-                       ref, b, a, l + 1, tb_bytes);
-  } else {
-    const int nb = resident_blocks(spec_ext2_kernel<kSpecBinLen[1] / 32>, lds2);
-    hipLaunchKernelGGL(spec_ext2_kernel<kSpecBinLen[1] / 32>, dim3(grid(nb)), dim3(kBlock), lds2, st, o, ref, b, a,
-                       l + 1, tb_bytes);
-  }
-  if (!bin2) return;
-  const int nb = resident_blocks(spec_ext_kernel<16>, lds);
-  hipLaunchKernelGGL(spec_ext_kernel<16>, dim3(round == 2 ? std::min(nb, 64) : nb), dim3(kBlock), lds, st, o, ref, b, a,
-                     l + 2, tb_bytes);
+  launch_ext_bin(plan.bin[1], r, l + 1, plan, ss.short_fill);
+  if (bin2) launch_task_long(r, l + 2);
 }
 
 // prep -> round A -> emulate -> round B -> final -> [round C] -> redo, one

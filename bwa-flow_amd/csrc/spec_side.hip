@@ -1,0 +1,543 @@
+// spec_side.hip — the phased extension of the speculative mem_chain2aln
+// (spec.hip has the design): its side lists' sort and spec_side4_kernel.
+#include "spec_dev.h"
+
+namespace bwagpu {
+
+// ---------------------------------------------- phased extension (round 6)
+// The extension tasks of the first two length bins run as two launches per
+// round: every task's LEFT call(s) (ksw_extend2 with the band retry,
+// bwamem.c:717-751), then every task's RIGHT call(s) (752-792, h0 = the left
+// score).  Each launch takes calls in the order of their own query length
+// (longest first), so the eight calls of a wave have about the same length:
+// with a task's left and right calls in one wave generation after another
+// (spec_ext4_kernel), a wave ran until its longest call ended while shorter
+// ones had ended (25 % of its call-slot cells) and set its columns by its
+// longest query (10 %), tools_dev/occ_diag.py.  Lists: the tasks with a left
+// side (FatTask, key = left query length) and those with a right side; a
+// whole-read seed (neither side) is written by the scatter itself.
+__device__ __forceinline__ int side_key(int qlen) { return 255 - min(qlen, 255); }  // descending
+
+__global__ void __launch_bounds__(256) spec_sort2_count(DevBatch b, SpecArgs a, int round, int bin0) {
+  sel_prio();
+  __shared__ int hist[2][256];
+  __shared__ int tot[2];
+  const int bin = bin0 + (int)blockIdx.y;
+  const int list = round * kSpecBins + bin;
+  int32_t* ghL = a.sorth + (round * 2 + bin) * kSortKeys;
+  int32_t* ghR = ghL + kSortWordsR;
+  for (int k = threadIdx.x; k < 2 * 256; k += 256) hist[k >> 8][k & 255] = 0;
+  if (threadIdx.x < 2) tot[threadIdx.x] = 0;
+  __syncthreads();
+  const int n = __hip_atomic_load(&a.ctr[SPC_CNT + list], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int2* tl = a.tasks + spec_list_off(list, b.n_chains, b.n_seeds);
+  const int chunk = (n + (int)gridDim.x - 1) / (int)gridDim.x;
+  const int i0 = (int)blockIdx.x * chunk, i1 = min(n, i0 + chunk);
+  for (int i = i0 + (int)threadIdx.x; i < i1; i += 256) {
+    const FatTask f = fat_task(b, a, tl[i]);
+    const int qb = (int)(f.qls & 1023u), ln = (int)((f.qls >> 10) & 1023u), lq = (int)(f.qls >> 20);
+    const int qr = lq - qb - ln;
+    if (qb > 0) atomicAdd(&hist[0][side_key(qb)], 1);
+    if (qr > 0) atomicAdd(&hist[1][side_key(qr)], 1);
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < 2 * 256; k += 256) {
+    const int c = hist[k >> 8][k & 255];
+    if (c) {
+      atomicAdd((k >> 8) ? &ghR[k & 255] : &ghL[k & 255], c);
+      atomicAdd(&tot[k >> 8], c);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 2 && tot[threadIdx.x])
+    atomicAdd(&a.ctr[(threadIdx.x ? SPC_RCNT : SPC_LCNT) + list], tot[threadIdx.x]);
+}
+
+// exclusive scan of the 256 keys of each (side, bin) histogram: one block each
+// (bins bin0 .. bin0 + nbins - 1).  short_q > 0: the first bin's lists get a
+// short run, the sides with a query of up to short_q bases; its first position
+// (= the sides with a longer query: the list is in descending length order)
+// goes to the list's SPC_LLONG / SPC_RLONG word here, before the scatter turns
+// the key positions into cursors.
+__global__ void __launch_bounds__(256) spec_sort2_scan(SpecArgs a, int round, int bin0, int nbins, int short_q) {
+  sel_prio();
+  __shared__ int part[256];
+  const int bin = bin0 + (int)blockIdx.x % nbins, side = (int)blockIdx.x / nbins;
+  int32_t* gh = a.sorth + (round * 2 + bin) * kSortKeys + side * kSortWordsR;
+  const int t = (int)threadIdx.x;
+  const int v = gh[t];
+  part[t] = v;
+  __syncthreads();
+  for (int o = 1; o < 256; o <<= 1) {
+    const int x = t >= o ? part[t - o] : 0;
+    __syncthreads();
+    part[t] += x;
+    __syncthreads();
+  }
+  gh[t] = part[t] - v;  // the key's first position (a cursor from here on)
+  if (short_q > 0 && bin == 0 && t == side_key(short_q))
+    a.ctr[(side ? SPC_RLONG : SPC_LLONG) + round * kSpecBins + bin] = part[t] - v;
+}
+
+__global__ void __launch_bounds__(256) spec_sort2_scatter(DevOpt o, DevBatch b, SpecArgs a, int round, int bin0) {
+  sel_prio();
+  __shared__ int cnt[2][256];
+  const int bin = bin0 + (int)blockIdx.y;
+  const int list = round * kSpecBins + bin;
+  int32_t* ghL = a.sorth + (round * 2 + bin) * kSortKeys;
+  int32_t* ghR = ghL + kSortWordsR;
+  for (int k = threadIdx.x; k < 2 * 256; k += 256) cnt[k >> 8][k & 255] = 0;
+  __syncthreads();
+  const int n = __hip_atomic_load(&a.ctr[SPC_CNT + list], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const size_t off = spec_list_off(list, b.n_chains, b.n_seeds);
+  const int2* tl = a.tasks + off;
+  FatTask* foL = a.ftask + off;
+  FatTask* foR = a.ftaskR + off;
+  const int chunk = (n + (int)gridDim.x - 1) / (int)gridDim.x;
+  const int i0 = (int)blockIdx.x * chunk, i1 = min(n, i0 + chunk);
+  constexpr int kPer = 8;  // entries per thread held across the barrier
+  int kl[kPer], kr[kPer], rl[kPer], rr[kPer];
+  FatTask ft[kPer];
+  for (int base = i0; base < i1; base += 256 * kPer) {
+#pragma unroll
+    for (int m = 0; m < kPer; ++m) {
+      const int i = base + m * 256 + (int)threadIdx.x;
+      kl[m] = kr[m] = -1;
+      if (i < i1) {
+        ft[m] = fat_task(b, a, tl[i]);
+        const int qb = (int)(ft[m].qls & 1023u), ln = (int)((ft[m].qls >> 10) & 1023u), lq = (int)(ft[m].qls >> 20);
+        const int qr = lq - qb - ln;
+        if (qb > 0) {
+          kl[m] = side_key(qb);
+          rl[m] = atomicAdd(&cnt[0][kl[m]], 1);
+        }
+        if (qr > 0) {
+          kr[m] = side_key(qr);
+          rr[m] = atomicAdd(&cnt[1][kr[m]], 1);
+        }
+        if (qb == 0 && qr == 0) {  // a whole-read seed (bwamem.c:753, 781): no ksw_extend2 call
+          SeedExt e;
+          e.rb = ft[m].rbeg;
+          e.re = ft[m].rbeg + ln;
+          e.qb = 0;
+          e.qe = lq;
+          e.score = e.truesc = ln * o.a;
+          e.w = o.w;
+          e.cells = e.rows = 0;
+          e.calls = 1;
+          a.ext[ft[m].pos] = e;
+        }
+      }
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < 2 * 256; k += 256) {
+      const int c = cnt[k >> 8][k & 255];
+      cnt[k >> 8][k & 255] = c ? atomicAdd((k >> 8) ? &ghR[k & 255] : &ghL[k & 255], c) : 0;  // this pass's range
+    }
+    __syncthreads();
+#pragma unroll
+    for (int m = 0; m < kPer; ++m) {
+      if (kl[m] >= 0) foL[cnt[0][kl[m]] + rl[m]] = ft[m];
+      if (kr[m] >= 0) foR[cnt[1][kr[m]] + rr[m]] = ft[m];
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < 2 * 256; k += 256) cnt[k >> 8][k & 255] = 0;
+    __syncthreads();
+  }
+}
+
+// One side of a task in flight (LDS, per sub-slot, between its calls).
+struct SideTask {
+  int64_t rbeg, qoff, rb;
+  int32_t pos, dlo, dhi, qbeg, len, lq;
+  int32_t tt, score, h0, truesc, qb, aw0, cells, rows, calls, pad_;
+};
+static_assert(sizeof(SideTask) <= 96, "SideTask layout");
+typedef __attribute__((address_space(3))) SideTask LdsS;
+#define SIDE_FIELDS(X) X(rbeg) X(qoff) X(rb) X(pos) X(dlo) X(dhi) X(qbeg) X(len) X(lq) X(tt) X(score) X(h0) \
+  X(truesc) X(qb) X(aw0) X(cells) X(rows) X(calls)
+__device__ __forceinline__ void spark(LdsS* p, const SideTask& t) {
+#define X(f) p->f = t.f;
+  SIDE_FIELDS(X)
+#undef X
+  asm volatile("" ::: "memory");
+}
+__device__ __forceinline__ SideTask sload(LdsS* p) {
+  asm volatile("" ::: "memory");
+  SideTask t;
+#define X(f) t.f = p->f;
+  SIDE_FIELDS(X)
+#undef X
+  return t;
+}
+#undef SIDE_FIELDS
+
+// a sub-slot's start: the side's target rows into its LDS buffer, the state
+// of the side's first call (a right side reads what the left launch left in
+// the seed's SeedExt slot)
+template <int G, bool RIGHT>
+__device__ __forceinline__ void side_start(SideTask& t, const DevOpt& o, const DevRef& ref, const SpecArgs& a,
+                                           const FatTask& f, uint8_t* tb) {
+  t.rbeg = f.rbeg;
+  t.qoff = f.qoff;
+  t.pos = f.pos;
+  t.dlo = f.dlo;
+  t.dhi = f.dhi;
+  t.qbeg = (int)(f.qls & 1023u);
+  t.len = (int)((f.qls >> 10) & 1023u);
+  t.lq = (int)(f.qls >> 20);
+  t.tt = 0;
+  const int64_t pac_bytes = (ref.l_pac >> 2) + 1;
+  const int r = (int)(threadIdx.x & (G - 1));
+  if constexpr (!RIGHT) {
+    const int n = rows_needed(o, t.qbeg, t.dlo, o.w << 1, o.pen_clip5);
+    const int R = (n + G - 1) / G;
+    if (R <= 32) fill_side_run<G>(tb, t.rbeg - 1, -1, r * R, min(r * R + R, n), ref, pac_bytes);
+    else fill_two_half<G>(tb, t.rbeg - 1, n, tb, 0, 0, ref);
+    t.score = -1;  // bwamem.c:753 (a left side: the retry test compares with -1)
+    t.h0 = t.len * o.a;
+    t.truesc = -1;
+    t.qb = 0;
+    t.rb = t.rbeg;
+    t.aw0 = o.w;
+    t.cells = t.rows = t.calls = 0;
+  } else {
+    const int64_t x0 = t.rbeg + t.len;
+    const int qr = t.lq - t.qbeg - t.len;
+    const int n = rows_needed(o, qr, (int)(t.rbeg + t.dhi - x0), o.w << 1, o.pen_clip3);
+    const int R = (n + G - 1) / G;
+    if (R <= 32) fill_side_run<G>(tb, x0, 1, r * R, min(r * R + R, n), ref, pac_bytes);
+    else fill_two_half<G>(tb, 0, 0, tb, x0, n, ref);
+    if (t.qbeg > 0) {  // the left launch's result (the same wave wrote... another wave did: SeedExt slot)
+      const SeedExt e = a.ext[t.pos];
+      t.score = e.score;
+      t.truesc = e.truesc;
+      t.qb = e.qb;
+      t.rb = e.rb;
+      t.aw0 = e.w;
+      t.cells = e.cells;
+      t.rows = e.rows;
+      t.calls = e.calls;
+    } else {
+      t.score = t.truesc = t.len * o.a;  // bwamem.c:753
+      t.qb = 0;
+      t.rb = t.rbeg;
+      t.aw0 = o.w;
+      t.cells = t.rows = t.calls = 0;
+    }
+    t.h0 = t.score;  // sc0 (bwamem.c:761)
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <bool RIGHT>
+__device__ __forceinline__ QCall side_call(const SideTask& t, const DevOpt& o, const uint8_t* seq, const uint8_t* tb) {
+  QCall q;
+  if constexpr (!RIGHT) {
+    q.qlen = t.qbeg;
+    q.tlen = t.dlo;
+    q.qa = t.qbeg - 1;
+    q.qd = -1;
+    q.eb = o.pen_clip5;
+  } else {
+    const int64_t x0 = t.rbeg + t.len;
+    q.qlen = t.lq - t.qbeg - t.len;
+    q.tlen = (int)(t.rbeg + t.dhi - x0);
+    q.qa = t.qbeg + t.len;
+    q.qd = 1;
+    q.eb = o.pen_clip3;
+  }
+  q.h0 = t.h0;
+  q.w = o.w << t.tt;
+  q.zdrop = o.zdrop;
+  q.q = seq + t.qoff;
+  q.tb = tb;
+  q.tlen = rows_needed(o, q.qlen, q.tlen, q.w, q.eb);  // as qtask_call
+  return q;
+}
+
+// the call's result (bwamem.c:737-751 / 770-792); true = the side is done,
+// its result written to the seed's SeedExt slot (partial after a left side
+// with a right side to come, else final)
+template <int G, bool RIGHT>
+__device__ __forceinline__ bool side_advance(SideTask& t, const DevOpt& o, const SpecArgs& a, const ExtOut& x,
+                                             const Tally32& tl, long long& spec_cells) {
+  t.cells += tl.cells;
+  t.rows += tl.rows;
+  t.calls += tl.calls;
+  const int prev = t.score;
+  t.score = x.score;
+  const int aw = o.w << t.tt;
+  if (t.tt == 0 && !(x.score == prev || x.max_off < (aw >> 1) + (aw >> 2))) {  // the band retry (MAX_BAND_TRY)
+    t.tt = 1;
+    return false;
+  }
+  const int eb = RIGHT ? o.pen_clip3 : o.pen_clip5;
+  const bool local = x.gscore <= 0 || x.gscore <= x.score - eb;
+  SeedExt e;
+  if constexpr (!RIGHT) {
+    const int qr = t.lq - t.qbeg - t.len;
+    e.rb = t.rbeg - (local ? x.tle : x.gtle);
+    e.qb = local ? t.qbeg - x.qle : 0;
+    e.score = t.score;
+    e.truesc = local ? x.score : x.gscore;
+    if (qr != 0) {  // partial: the right launch goes on from here
+      e.re = 0;
+      e.qe = 0;
+      e.w = aw;
+      e.cells = t.cells;
+      e.rows = t.rows;
+      e.calls = t.calls;
+    } else {
+      e.re = t.rbeg + t.len;
+      e.qe = t.lq;
+      e.w = max(aw, o.w);
+      e.cells = t.cells;
+      e.rows = t.rows;
+      e.calls = t.calls + 1;  // + 1: a computed slot is never all-zero
+      spec_cells += t.cells;
+    }
+  } else {
+    e.rb = t.rb;
+    e.qb = t.qb;
+    e.qe = local ? t.qbeg + t.len + x.qle : t.lq;
+    e.re = t.rbeg + t.len + (local ? x.tle : x.gtle);
+    e.score = t.score;
+    e.truesc = t.truesc + (local ? x.score : x.gscore) - t.h0;
+    e.w = max(t.aw0, aw);
+    e.cells = t.cells;
+    e.rows = t.rows;
+    e.calls = t.calls + 1;
+    spec_cells += t.cells;
+  }
+  store_ext_half<G>(a.ext + t.pos, e);
+  return true;
+}
+
+// a side's query bytes into LDS in column order (qd[j] = column j), so the DP
+// has no global load (its prologue read them from HBM: a dependent round trip
+// per generation)
+template <int G, bool RIGHT>
+__device__ __forceinline__ void side_query(const DevBatch& b, const FatTask& f, uint8_t* qd, int qb) {
+  const int r = (int)(threadIdx.x & (G - 1));
+  const int qbeg = (int)(f.qls & 1023u), len = (int)((f.qls >> 10) & 1023u), lq = (int)(f.qls >> 20);
+  const int qlen = min(RIGHT ? lq - qbeg - len : qbeg, qb);
+  const uint8_t* q = b.seq + f.qoff + (RIGHT ? qbeg + len : qbeg - 1);
+  for (int j = r; j < qlen; j += G) qd[j] = q[RIGHT ? j : -j];
+}
+
+// The phased extension's loop over one run of a side list: 128 / G calls per
+// wave (G = 16: eight, 32: four, 8: sixteen) in the
+// packed 16-bit DP (extend_quad), claimed in the list's order (the side's
+// query length, longest first) from the run's own sharded heads.  wlds = the
+// wave's own LDS slice, cut per group: A's and B's target rows (tb_bytes
+// each), their states, their query bytes.  Returns the sides it started.
+template <int G, int PMAX, bool K8, bool RIGHT>
+__device__ __forceinline__ int side_loop(const DevOpt& o, const DevRef& ref, const DevBatch& b, const SpecArgs& a,
+                                         const FatTask* fl, int n, int32_t* heads, uint8_t* wlds, int tb_bytes,
+                                         long long& spec_cells
+#ifdef BWAGPU_OCC_DIAG
+                                         , unsigned long long* tw, unsigned long long* occ
+#endif
+) {
+  constexpr uint64_t kLead =
+      G == 8 ? 0x0101010101010101ull : (G == 16 ? 0x0001000100010001ull : 0x0000000100000001ull);
+  const uint64_t below = kLead & ((1ull << ((int)threadIdx.x & (64 - G))) - 1);
+  constexpr int QB = PMAX * G;
+  uint8_t* const ta_ = wlds + (size_t)((threadIdx.x & 63) / G) * (2 * (size_t)tb_bytes + 2 * kSideLds + 2 * QB);
+  uint8_t* const tb_ = ta_ + tb_bytes;
+  LdsS* const sa = (LdsS*)(tb_ + tb_bytes);
+  LdsS* const sb = (LdsS*)(tb_ + tb_bytes + kSideLds);
+  uint8_t* const qa_ = tb_ + tb_bytes + 2 * kSideLds;
+  uint8_t* const qb_ = qa_ + QB;
+  ShardQ qq;
+  qq.init(heads, n);
+  bool ha = false, hb = false, more = n > 0;
+  int started = 0;
+  for (;;) {
+#ifdef BWAGPU_OCC_DIAG
+    const unsigned long long c0 = __builtin_amdgcn_s_memtime();
+#endif
+    if (more) {  // every sub-slot without a call takes the next entry: one claim for the wave
+      const uint64_t na = __builtin_amdgcn_ballot_w64(!ha) & kLead, nb = __builtin_amdgcn_ballot_w64(!hb) & kLead;
+      const int nn = __popcll(na) + __popcll(nb);
+      if (nn > 0) {
+        int m0, cap;
+        if (qq.claim(nn, m0, cap)) {
+          const int ia = m0 + __popcll(na & below) + __popcll(nb & below), ib = ia + (ha ? 0 : 1);
+          if (!ha && ia < cap) {
+            SideTask t;
+            const FatTask f = fl[qq.shard + 8 * ia];
+            side_query<G, RIGHT>(b, f, qa_, QB);
+            side_start<G, RIGHT>(t, o, ref, a, f, ta_);
+            spark(sa, t);
+            ha = true;
+            ++started;
+          }
+          if (!hb && ib < cap) {
+            SideTask t;
+            const FatTask f = fl[qq.shard + 8 * ib];
+            side_query<G, RIGHT>(b, f, qb_, QB);
+            side_start<G, RIGHT>(t, o, ref, a, f, tb_);
+            spark(sb, t);
+            hb = true;
+            ++started;
+          }
+        } else {
+          more = false;
+        }
+      }
+    }
+#ifdef BWAGPU_OCC_DIAG
+    const unsigned long long c1 = __builtin_amdgcn_s_memtime();
+    tw[0] += c1 - c0;
+#endif
+    if (!__builtin_amdgcn_ballot_w64(ha || hb)) {
+      if (!more) break;
+      continue;
+    }
+    QCall ca = quad_idle(qa_, ta_), cb = quad_idle(qb_, tb_);  // every query pointer in LDS
+    if (ha) {
+      ca = side_call<RIGHT>(sload(sa), o, b.seq, ta_);
+      ca.q = qa_;
+      ca.qa = 0;
+      ca.qd = 1;
+    }
+    if (hb) {
+      cb = side_call<RIGHT>(sload(sb), o, b.seq, tb_);
+      cb.q = qb_;
+      cb.qa = 0;
+      cb.qd = 1;
+    }
+    ExtOut xa, xb;
+    Tally32 tla{0, 0, 0}, tlb{0, 0, 0};
+#ifdef BWAGPU_OCC_DIAG
+    const unsigned long long c2 = __builtin_amdgcn_s_memtime();
+    tw[1] += c2 - c1;
+#endif
+    extend_quad_dispatch<G, PMAX, K8>(o, ca, cb, xa, xb, tla, tlb);
+#ifdef BWAGPU_OCC_DIAG
+    const unsigned long long c3 = __builtin_amdgcn_s_memtime();
+    tw[2] += c3 - c2;
+    occ_diag<G>(occ, ca, cb, tla, tlb);
+#endif
+    if (ha) {
+      SideTask t = sload(sa);
+      if (side_advance<G, RIGHT>(t, o, a, xa, tla, spec_cells)) ha = false;
+      else spark(sa, t);
+    }
+    if (hb) {
+      SideTask t = sload(sb);
+      if (side_advance<G, RIGHT>(t, o, a, xb, tlb, spec_cells)) hb = false;
+      else spark(sb, t);
+    }
+#ifdef BWAGPU_OCC_DIAG
+    tw[3] += __builtin_amdgcn_s_memtime() - c3;
+#endif
+  }
+  return started;
+}
+
+// The phased extension's kernel: one side (RIGHT = false: left calls, true:
+// right calls) of the tasks of one list.  The list is sorted by the side's
+// query length, longest first: entries [0, n_long) have a query longer than
+// short_q and run eight per wave (G = 16) or four (G = 32); the eight-per-wave
+// form then runs the rest, [n_long, n), sixteen per wave in groups of eight
+// lanes (short_q > 0; spec_sort2_scan left n_long in the list's counter word).
+// A wave goes from the first run to the second on its own, when the first
+// run's heads are dry: no launch and no barrier between them.  LDS is cut per
+// wave (wave_lds bytes each, the larger of the two runs' needs), so a wave in
+// the second run never touches a sibling's buffers of the first.
+template <int G, int PMAX, bool K8, bool RIGHT>
+__global__ void __launch_bounds__(kBlock) spec_side4_kernel(DevOpt o, DevRef ref, DevBatch b, SpecArgs a, int list,
+                                                            int tb_bytes, int wave_lds, int short_q, int tb_short,
+                                                            int short_fill) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+  uint8_t* const wlds = lds + (size_t)(threadIdx.x >> 6) * (size_t)wave_lds;
+  const int n = uni(__hip_atomic_load(&a.ctr[(RIGHT ? SPC_RCNT : SPC_LCNT) + list], __ATOMIC_RELAXED,
+                                      __HIP_MEMORY_SCOPE_AGENT));
+  const FatTask* fl = (RIGHT ? a.ftaskR : a.ftask) + spec_list_off(list, b.n_chains, b.n_seeds);
+  constexpr bool kShort = G == 16 && K8;  // the form with a short phase
+  int n_long = n;
+  if constexpr (kShort) {
+    if (short_q > 0) {
+      n_long = min(n, uni(__hip_atomic_load(&a.ctr[(RIGHT ? SPC_RLONG : SPC_LLONG) + list], __ATOMIC_RELAXED,
+                                            __HIP_MEMORY_SCOPE_AGENT)));
+      // a short run that does not fill the grid's sixteen-per-wave slots
+      // short_fill / 100 times over runs eight per wave as before (every wave
+      // decides alike): see launch_side_pair
+      const long long slots = (long long)gridDim.x * (kBlock / 64) * (128 / kShortG);
+      if ((long long)(n - n_long) * 100 < slots * short_fill) n_long = n;
+    }
+  }
+  const int hl = RIGHT ? kSpecRounds * kSpecBins + list : list;
+  long long spec_cells = 0;
+#ifdef BWAGPU_OCC_DIAG
+  unsigned long long tw[6] = {0, 0, 0, 0, 0, 0}, occ[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  (void)side_loop<G, PMAX, K8, RIGHT>(o, ref, b, a, fl, n_long, a.qh + 8 * kQHStride * hl, wlds, tb_bytes, spec_cells,
+                                      tw, occ);
+#else
+  (void)side_loop<G, PMAX, K8, RIGHT>(o, ref, b, a, fl, n_long, a.qh + 8 * kQHStride * hl, wlds, tb_bytes, spec_cells);
+#endif
+  if constexpr (kShort) {
+    if (n_long < n) {
+      int32_t* const hs = a.qh + kQHShort + 8 * kQHStride * hl;
+      long long cells_s = 0;  // group-uniform over eight lanes, not sixteen: added on its own
+#ifdef BWAGPU_OCC_DIAG
+      const int ns = side_loop<kShortG, kShortPmax, true, RIGHT>(o, ref, b, a, fl + n_long, n - n_long, hs, wlds,
+                                                                 tb_short, cells_s, tw, occ);
+#else
+      const int ns = side_loop<kShortG, kShortPmax, true, RIGHT>(o, ref, b, a, fl + n_long, n - n_long, hs, wlds,
+                                                                 tb_short, cells_s);
+#endif
+      if ((threadIdx.x & (kShortG - 1)) == 0 && ns) {
+        atomicAdd(&a.ctr[SPC_SHORT_N], ns);
+        atomicAdd(reinterpret_cast<unsigned long long*>(a.ctr + SPC_SPEC64), (unsigned long long)cells_s);
+      }
+    }
+  }
+#ifdef BWAGPU_OCC_DIAG
+  if ((threadIdx.x & 63) == 0) {
+    for (int k = 0; k < 8; ++k) atomicAdd(reinterpret_cast<unsigned long long*>(a.ctr + 32) + k, occ[k]);
+    for (int k = 0; k < 4; ++k) atomicAdd(reinterpret_cast<unsigned long long*>(a.ctr + 48) + k, tw[k]);
+  }
+#endif
+  if ((threadIdx.x & (G - 1)) == 0 && spec_cells)
+    atomicAdd(reinterpret_cast<unsigned long long*>(a.ctr + SPC_SPEC64), (unsigned long long)spec_cells);
+}
+
+
+void launch_side_sort(const ExtRound& r, int bin0, int nbins, int short_q) {
+  hipLaunchKernelGGL(spec_sort2_count, dim3(256, nbins), dim3(256), 0, r.st, r.b, r.a, r.round, bin0);
+  hipLaunchKernelGGL(spec_sort2_scan, dim3(2 * nbins), dim3(256), 0, r.st, r.a, r.round, bin0, nbins, short_q);
+  hipLaunchKernelGGL(spec_sort2_scatter, dim3(256, nbins), dim3(256), 0, r.st, r.o, r.b, r.a, r.round, bin0);
+}
+
+// the two side launches of the phased extension for one list: every left
+// call, then every right call, G lanes per call.  The short phase's settings
+// are the plan's (only the eight-per-wave form has one).
+template <int G, int PMAX, bool K8>
+static void launch_side_pair(const ExtRound& r, int list, const ExtPlan& p, int short_fill) {
+  const size_t lds = (size_t)(kBlock / 64) * p.wave_lds;
+  const int nb = resident_blocks(spec_side4_kernel<G, PMAX, K8, false>, lds);
+  const int gr = r.round == 2 ? std::min(nb, 64) : std::min(nb, ext2_grid(1 << 30, true));
+  if (!(G == 16 && K8)) short_fill = 0;
+  hipLaunchKernelGGL((spec_side4_kernel<G, PMAX, K8, false>), dim3(gr), dim3(kBlock), lds, r.st, r.o, r.ref, r.b, r.a,
+                     list, r.tb_bytes, (int)p.wave_lds, p.short_q, p.tb_short, short_fill);
+  hipLaunchKernelGGL((spec_side4_kernel<G, PMAX, K8, true>), dim3(gr), dim3(kBlock), lds, r.st, r.o, r.ref, r.b, r.a,
+                     list, r.tb_bytes, (int)p.wave_lds, p.short_q, p.tb_short, short_fill);
+}
+
+// the side kernels compiled are exactly these cases
+void launch_side_bin(const ExtBin& k, const ExtRound& r, int list, const ExtPlan& p, int short_fill) {
+  switch (ext_key(k.family, k.G, k.PMAX, k.K8)) {
+    case ext_key(SIDE4, 16, 10, true): return launch_side_pair<16, 10, true>(r, list, p, short_fill);
+    case ext_key(SIDE4, 32, 5, true): return launch_side_pair<32, 5, true>(r, list, p, short_fill);
+    case ext_key(SIDE4, 32, 8, false): return launch_side_pair<32, 8, false>(r, list, p, short_fill);
+    default: abort();  // ext_plan names no other side kernel (tests/cpp/ext_plan_asan.cpp)
+  }
+}
+
+}  // namespace bwagpu

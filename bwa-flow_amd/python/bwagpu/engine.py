@@ -289,17 +289,16 @@ class Engine:
                                               C.byref(n)), "sw_stream")
         return out[:n.value]
 
-    # bwagpu_debug_ext_kernel codes -> the first bin's extension kernel
-    EXT_KERNELS = {8: "spec_ext4_kernel<16, 10, true>", 4: "spec_ext4_kernel<32, 5, true>",
-                   5: "spec_ext4_kernel<32, 8, false>", 2: "spec_ext2_kernel<5>",
+    # bwagpu_debug_ext_kernel codes (ext_plan, csrc/spec_plan.h) -> the first bin's extension kernel
+    EXT_KERNELS = {2: "spec_ext2_kernel<5>",
                    # the phased pair: one "launch" = its left and right side launches
                    18: "spec_side4_kernel<16, 10, true>", 14: "spec_side4_kernel<32, 5, true>",
-                   15: "spec_side4_kernel<32, 8, false>", 28: "spec_sidep_kernel<16, 10, true>"}
+                   15: "spec_side4_kernel<32, 8, false>"}
 
     def ext_kernel(self, lq_max: int = 256) -> str:
         """the first length bin's extension kernel this context launches for
-        reads of up to lq_max bases (the C side's own decision, spec.hip
-        ext_kernel_for)"""
+        reads of up to lq_max bases (the C side's own decision: ext_plan,
+        csrc/spec_plan.h)"""
         k = self.lib.bwagpu_debug_ext_kernel(self.ctx, int(lq_max))
         if k not in self.EXT_KERNELS:
             raise BwaGpuError(k, "debug_ext_kernel")

@@ -9,8 +9,6 @@ cells beyond a live call's query, outside ksw's band, and computed
   beyond_q   columns past a live call's own query (columns set by the longest)
   out_band   inside the query but outside ksw's band
   computed   cells computed (the row bound's live rows only)
-With spec_sidep_kernel (the producer wave) start_claim is a DP wave's wait for
-its next buffer, and claim / taskrec are the producer wave's busy / idle cycles.
     BWAGPU_LIB=bwa-flow_amd/lib/diag/libbwagpu.so python tools_dev/occ_diag.py [row_bound 0|1]"""
 import ctypes as C
 import json
