@@ -270,6 +270,7 @@ int create_common(int device, const bwagpu_opt_t* opt, const bwagpu_bns_t* bns, 
   ctx->ext_form = set_ext_form(-1);
   ctx->ext_short = ext_short_default();
   ctx->ext_short_fill = ext_short_fill_default();
+  ctx->light_pack = light_pack_default();
   *made = ctx;
   HIPC(hipSetDevice(device), "hipSetDevice");
   HIPC(hipMalloc(&ctx->d_ann_off, sizeof(int64_t) * bns->n_seqs), "hipMalloc(ann_offset)");
@@ -696,6 +697,7 @@ int enqueue_spec(bwagpu_ctx_t* ctx, Slot& s, const DevBatch& db, int lq_max, bwa
     return !(e && e[0] == '0');
   }();
   a.emu_strict = emu_strict;
+  a.light_pack = ctx->light_pack;
   a.out = d_out;
   a.out_n = d_n;
   a.stats = d_stats;
@@ -1213,6 +1215,13 @@ int bwagpu_ctx_ext_short_fill(bwagpu_ctx_t* ctx, int percent) {
   if (!ctx) return BWAGPU_E_INVAL;
   const int prev = ctx->ext_short_fill;
   if (percent >= 0) ctx->ext_short_fill = percent > 100000 ? 100000 : percent;
+  return prev;
+}
+
+int bwagpu_ctx_light_pack(bwagpu_ctx_t* ctx, int on) {
+  if (!ctx) return BWAGPU_E_INVAL;
+  const int prev = ctx->light_pack;
+  if (on >= 0) ctx->light_pack = on != 0;
   return prev;
 }
 

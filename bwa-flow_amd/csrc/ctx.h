@@ -147,6 +147,7 @@ struct bwagpu_ctx {
   int watchdog_ms = 10000;
   int ext_form = 0;  // bwagpu_ctx_ext_form (the process default when made)
   int ext_short = 0; // bwagpu_ctx_ext_short (BWAGPU_EXT_SHORT_Q or the compiled default when made)
+  int light_pack = 0;  // bwagpu_ctx_light_pack (BWAGPU_LIGHT_PACK or the compiled default when made)
   int ext_short_fill = 0;  // bwagpu_ctx_ext_short_fill (BWAGPU_EXT_SHORT_FILL or the compiled default when made)
   Slot slot[BWAGPU_NUM_SLOTS];
   // bwagpu_chain2aln_device: the caller's streams, one per slot's scratch (a

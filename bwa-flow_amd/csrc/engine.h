@@ -206,6 +206,7 @@ struct SpecArgs {
   FatTask* ftaskR;            // the phased extension: the tasks with a right side, by its length
   int risky_first;            // spec_select_light<SEL_FINAL>: reads with a round-B task first (BWAGPU_LIGHT_RISKY_FIRST)
   int emu_strict;             // spec_select_light<SEL_EMULATE>: round-B tasks for uncertain skips too (BWAGPU_EMU_STRICT)
+  int light_pack;             // spec_select_light: narrow reads eight per wave (bwagpu_ctx_light_pack)
   int ext_prefetch;           // spec_ext4_kernel: claim next tasks a generation ahead while more than
                               // ext_prefetch x 8 x (waves per XCD) remain (0: on demand)
   bwagpu_alnreg_t* out;
@@ -238,6 +239,9 @@ int set_ext_form(int form);
 // the compiled default)
 int ext_short_default();
 int ext_short_fill_default();
+// the packed light selection new contexts start with (BWAGPU_LIGHT_PACK, else
+// the compiled default)
+int light_pack_default();
 // the first length bin's extension kernel launch_ext_round picks for `form`
 // and options `o` with target row buffers of tb_bytes: ext_plan's code
 // (spec_plan.h lists the codes)

@@ -1315,77 +1315,15 @@ __global__ void __launch_bounds__(64) spec_select_kernel(DevOpt o, DevRef ref, D
 #ifndef BWAGPU_LIGHT_INLINE
 #define BWAGPU_LIGHT_INLINE 1
 #endif
+// One light read (1 <= ns <= kSelLight) by the whole wave; d is wave-uniform.
 template <int MODE>
-__global__ void __launch_bounds__(kBlock) spec_select_light(DevOpt o, DevRef ref, DevBatch b, SpecArgs a,
-                                                            int tb_bytes) {
-  sel_prio();
+__device__ __forceinline__ void light_read(const DevOpt& o, const DevRef& ref, const DevBatch& b, const SpecArgs& a,
+                                           const int32_t* MG, uint8_t* tbl, uint8_t* tbr, int rd, const ReadDesc& d,
+                                           Tally& tl) {
   constexpr bool WRITE = MODE != SEL_EMULATE;
-  __shared__ int32_t MG[kMglN];
-  extern __shared__ __attribute__((aligned(16))) uint8_t lrows[];  // per wave: target rows of an inline extension
-  uint8_t* const tbl = lrows + (threadIdx.x >> 6) * 2 * tb_bytes;
-  uint8_t* const tbr = tbl + tb_bytes;
-  for (int x = threadIdx.x; x < kMglN; x += kBlock) MG[x] = max_gap_len(o, x);
-  __syncthreads();
   const int r = (int)(threadIdx.x & 63);
   const uint64_t lt_mask = r ? (~0ull >> (64 - r)) : 0ull;  // lanes below r
-  Tally tl{0, 0, 0};
-  // static deal: wave w takes reads w, w + NW, ... (light reads cost about the
-  // same; no queue atomics), the next read's descriptor in flight meanwhile.
-  // The final pass first takes, in its static share, only the reads the
-  // emulate pass left a round-B task in (rbits): only those can miss, and a
-  // miss is extended inline (one wave, ~0.1 ms per extension, cascades of
-  // several in a read) — so they start first, and every other read is claimed
-  // afterwards in chunks of kLightChunk by whichever wave is free, instead of
-  // waiting behind a wave's misses in its static share.
-  const int NW = (int)gridDim.x * (kBlock / 64);
-  const int w0 = (int)blockIdx.x * (kBlock / 64) + uni((int)(threadIdx.x >> 6));
-  constexpr int kLightChunk = 16;
-  int ph = 0, cb = 0, ce = 0, pbase = w0 - 64 * NW;
-  uint64_t pm = 0;
-  const auto risky = [&](int x) { return ((a.rbits[x >> 5] >> (x & 31)) & 1u) != 0; };
-  const auto next_read = [&]() -> int {
-    if (ph == 0) {  // this wave's static share, the reads with a round-B task, 64 at a time
-      for (;;) {
-        if (pm) {
-          const int i = __builtin_ctzll(pm);
-          pm &= pm - 1;
-          return pbase + i * NW;
-        }
-        pbase += 64 * NW;
-        if (pbase >= b.n_reads) break;
-        const int x = pbase + r * NW;
-        pm = __builtin_amdgcn_ballot_w64(x < b.n_reads && risky(x));
-      }
-      ph = 1;
-    }
-    for (;;) {  // the rest, claimed
-      if (cb >= ce) {
-        int c = 0;
-        if (r == 0) c = atomicAdd(&a.ctr[SPC_LIGHT_CUR], kLightChunk);
-        c = __builtin_amdgcn_readfirstlane(__shfl(c, 0, 64));
-        if (c >= b.n_reads) return b.n_reads;
-        cb = c;
-        ce = min(c + kLightChunk, b.n_reads);
-      }
-      const int y = cb++;
-      if (!risky(y)) return y;
-    }
-  };
-  const bool dyn = MODE == SEL_FINAL && a.risky_first;
-  int rd = dyn ? next_read() : w0;
-  ReadDesc dn{};
-  if (rd < b.n_reads) dn = a.rdesc[rd];
-  for (int nx; rd < b.n_reads; rd = nx) {
-    const uint64_t t_start = g_trace ? __builtin_amdgcn_s_memrealtime() : 0;
-    const ReadDesc d = uniform_desc(dn);
-    nx = dyn ? next_read() : rd + NW;
-    if (nx < b.n_reads) dn = a.rdesc[nx];
-    if (d.ns > kSelLight || d.nch > kSelLight) continue;  // the heavy kernel's read
-    if (d.lq > a.lq_bound) continue;                      // flagged by spec_reads_kernel
-    if (d.ns == 0) {
-      if (WRITE) a.out_n[rd] = 0;
-      continue;
-    }
+  const uint64_t t_start = g_trace ? __builtin_amdgcn_s_memrealtime() : 0;
     // a miss of the final pass is computed inline and the read starts over
     // with it (a region changes only later decisions; light reads are cheap)
     for (;;) {
@@ -1579,6 +1517,300 @@ __global__ void __launch_bounds__(kBlock) spec_select_light(DevOpt o, DevRef ref
     trace_read(MODE, b.n_reads, rd, t_start, d.ns, (int)__popcll(ext), 1);
     break;
     }  // the read's attempts
+}
+
+// NARROW light reads (<= kPackW seeds and chains: nine in ten C2 reads), eight
+// per wave: group g = lane >> 3 is the read, lane i = lane & 7 its seed i (in
+// prog[] order) and its chain i.  The three steps of light_read, with every
+// set an 8-bit one held alike by the group's lanes:
+//   1. pairs: pass k gives seed k to its group; the group's byte of the two
+//      ballots is C[k] / O[k], kept as byte k of a 64-bit word; seedcov of k
+//      is summed over the group into lane k;
+//   2. scan: light_read's statements in their order, as selects on the sets,
+//      eight steps for the eight reads at once;
+//   3. output: every extended seed's record at its rank within the group.
+// d, rd and nar (this lane's read is a narrow one of this wave) are the same
+// in a group's lanes.  -> the lanes whose read the final pass missed a result
+// for; nothing of such a read is written here, light_read takes it.
+constexpr int kPackW = 8;
+template <int MODE>
+__device__ __forceinline__ uint64_t light_packed(const DevBatch& b, const SpecArgs& a, const int32_t* MG, int rd,
+                                                 const ReadDesc& d, bool nar, Tally& tl) {
+  constexpr bool WRITE = MODE != SEL_EMULATE;
+  const uint64_t t_start = g_trace ? __builtin_amdgcn_s_memrealtime() : 0;
+  int r = (int)(threadIdx.x & 63);
+  asm volatile("" : "+v"(r));  // per octet: what derives from it is not held in registers over light_read
+  const int i = r & 7, g0 = r & ~7;
+  const auto grp = [&](int v, int l) { return __builtin_amdgcn_ds_bpermute((g0 + l) << 2, v); };  // lane l of the group
+  const auto grp64 = [&](int64_t v, int l) {
+    return (int64_t)((uint64_t)(uint32_t)grp((int)(v >> 32), l) << 32 | (uint32_t)grp((int)v, l));
+  };
+  const auto byte_of = [&](uint64_t m) { return (uint32_t)(m >> g0) & 0xFFu; };  // the group's lanes of a ballot
+  // everything of the eight reads, one round trip
+  const bool has_c = nar && i < d.nch, has_s = nar && i < d.ns;
+  int ce_l = 15, rid_l = 0;
+  float fr_l = 0.f;
+  bool ok_l = false;
+  if (has_c) {
+    ce_l = b.chain_seed_off[d.c0 + i + 1] - d.s0;
+    const ChainWin cw = a.win[d.c0 + i];
+    ok_l = cw.hi >= cw.lo;  // a chain with a flagged window is never processed
+    rid_l = b.chain_rid[d.c0 + i];
+    fr_l = b.chain_frac_rep[d.c0 + i];
+  }
+  bwagpu_seed_t sd{};
+  SeedExt x{};
+  if (has_s) {
+    sd = a.prog[d.s0 + i];
+    x = a.ext[d.s0 + i];
+  }
+  // seed i's chain: the chains' seed ranges follow each other from 0, so it is
+  // the number of chains that end at or before i (ends as nibbles, or-ed over
+  // the group; 15 for no chain)
+  uint32_t ends = (uint32_t)ce_l << (4 * i);
+  ends |= (uint32_t)dpp<0xB1>(0, (int)ends);   // quad_perm:[1,0,3,2]
+  ends |= (uint32_t)dpp<0x4E>(0, (int)ends);   // quad_perm:[2,3,0,1]
+  ends |= (uint32_t)dpp<0x141>(0, (int)ends);  // row_half_mirror
+  int cid = 0;
+#pragma unroll
+  for (int c = 0; c < kPackW - 1; ++c) cid += (int)((ends >> (4 * c)) & 15u) <= i;
+  const bool vchain = grp(ok_l ? 1 : 0, cid) != 0;
+  const int rid = grp(rid_l, cid);
+  const float frac = __int_as_float(grp(__float_as_int(fr_l), cid));
+  const bool present = has_s && vchain;
+  const bool computed = present && x.calls != 0;
+  const bool j_pad = has_s && sd.pad_ != 0;
+  const uint32_t present_m = byte_of(__builtin_amdgcn_ballot_w64(present));
+  const uint32_t computed_m = byte_of(__builtin_amdgcn_ballot_w64(computed));
+  const uint32_t pad_m = byte_of(__builtin_amdgcn_ballot_w64(j_pad));
+  const int rep_lim = (int)floor(.1 * d.lq) + 1;  // s->len - p->seedlen0 > .1 * l_query, bwamem.c:685
+  // ---- 1. pair masks: pass k, lane j = i; no pass depends on another
+  RegRec pj;  // this lane's region
+  pj.rb = x.rb;
+  pj.re = x.re;
+  pj.qb = x.qb;
+  pj.qe = x.qe;
+  pj.w = x.w;
+  pj.seedlen0 = sd.len;
+  uint64_t C = 0, O = 0;
+  int cov = 0;
+#pragma unroll 1  // (unrolled, the eight source lanes' addresses are held over the whole kernel)
+  for (int k = 0; k < kPackW && __builtin_amdgcn_ballot_w64(nar && k < d.ns) != 0; ++k) {
+    bwagpu_seed_t sk;
+    sk.rbeg = grp64(sd.rbeg, k);
+    sk.qbeg = grp(sd.qbeg, k);
+    sk.len = grp(sd.len, k);
+    const int k_cid = grp(cid, k);
+    const bool valid = has_s && k < d.ns;
+    // C: the region of seed j holds seed k (bwamem.c:682-696)
+    const bool inside = valid && i < k && computed &&
+                        !(sk.rbeg < pj.rb || sk.rbeg + sk.len > pj.re || sk.qbeg < pj.qb || sk.qbeg + sk.len > pj.qe) &&
+                        !(sk.len - sd.len >= rep_lim);
+    uint64_t cm = __builtin_amdgcn_ballot_w64(inside);
+    if (cm) cm = __builtin_amdgcn_ballot_w64(inside && seed_near(MG, sk, pj));
+    // O: seed j of k's chain overlaps it (bwamem.c:701-704; t->len < s->len * .95 <=> t->len < ceil(...))
+    const int len95 = (int)ceil(sk.len * .95);
+    const bool a1 = sk.qbeg <= sd.qbeg && sk.qbeg + sk.len - sd.qbeg >= sk.len >> 2 &&
+                    (int64_t)(sd.qbeg - sk.qbeg) != sd.rbeg - sk.rbeg;
+    const bool b1 = sd.qbeg <= sk.qbeg && sd.qbeg + sd.len - sk.qbeg >= sk.len >> 2 &&
+                    (int64_t)(sk.qbeg - sd.qbeg) != sk.rbeg - sd.rbeg;
+    const uint64_t om = __builtin_amdgcn_ballot_w64(valid && i < k && cid == k_cid && !j_pad && sd.len >= len95 && (a1 || b1));
+    C |= (uint64_t)byte_of(cm) << (8 * k);
+    O |= (uint64_t)byte_of(om) << (8 * k);
+    if (WRITE) {  // seedcov of k's region over its chain's seeds (bwamem.c:784-788)
+      const int64_t krb = grp64(x.rb, k), kre = grp64(x.re, k);
+      const int kqb = grp(x.qb, k), kqe = grp(x.qe, k);
+      int v = valid && cid == k_cid && sd.qbeg >= kqb && sd.qbeg + sd.len <= kqe && sd.rbeg >= krb &&
+                      sd.rbeg + sd.len <= kre ? sd.len : 0;
+      v += dpp<0xB1>(0, v);
+      v += dpp<0x4E>(0, v);
+      v += dpp<0x141>(0, v);
+      cov = i == k ? v : cov;
+    }
+  }
+  // ---- 2. the sequential decisions of the eight reads at once (light_read's, as selects)
+  uint32_t ext = 0, skip = pad_m, pend = 0, spend = 0, unc = 0;
+  bool missed = false;
+#pragma unroll
+  for (int k = 0; k < kPackW; ++k) {
+    const uint32_t bit = 1u << k;
+    const uint32_t cm = (uint32_t)(C >> (8 * k)) & 0xFFu, om = (uint32_t)(O >> (8 * k)) & 0xFFu;
+    const bool act = (present_m & bit) != 0 && !missed;
+    const bool done = (computed_m & bit) != 0;
+    const bool skp = act && (cm & ext) != 0 && !(om & ~skip);  // skipped: srt[k] = 0 (bwamem.c:709)
+    const bool sunc = skp && MODE == SEL_EMULATE && a.emu_strict && (!(cm & ext & ~unc) || (om & unc));
+    const bool nores = act && !skp && !done;  // must be extended, no result
+    const bool go = act && !skp && done;
+    skip |= skp ? bit : 0u;
+    spend |= sunc && !done ? bit : 0u;
+    if (MODE == SEL_EMULATE) {
+      unc |= sunc || nores || (go && pend) ? bit : 0u;  // (pend: of the steps before this one)
+      pend |= nores ? bit : 0u;
+    } else {
+      missed = missed || nores;
+    }
+    ext |= go ? bit : 0u;
+  }
+  // ---- 3. outputs
+  if constexpr (MODE == SEL_EMULATE) {
+    const bool pnd = nar && (((pend | spend) >> i) & 1u) != 0;
+    const int bin = spec_bin(d.lq);
+    for (int k = 0; k < kSpecBins; ++k) {  // the reads of a wave differ in length
+      const int list = kSpecBins + k;
+      const int p = wave_append(&a.ctr[SPC_CNT + list], pnd && bin == k);
+      if (p >= 0) a.tasks[spec_list_off(list, b.n_chains, b.n_seeds) + p] = make_int2(d.s0 + i, d.c0 + cid);
+    }
+    if (nar && pend && i == 0) atomicOr(&a.rbits[rd >> 5], 1u << (rd & 31));  // the final pass takes it first
+  } else {
+    const bool wr = nar && !missed;
+    if (wr && ((ext >> i) & 1u)) {  // the region of seed i, at its rank (bwamem.c:718-792 field by field; rest zero)
+      const int slot = (int)__popc(ext & ((1u << i) - 1u));
+      uint2* dst = reinterpret_cast<uint2*>(a.out + d.s0 + slot);
+      dst[0] = make_uint2((uint32_t)x.rb, (uint32_t)((uint64_t)x.rb >> 32));
+      dst[1] = make_uint2((uint32_t)x.re, (uint32_t)((uint64_t)x.re >> 32));
+      dst[2] = make_uint2((uint32_t)x.qb, (uint32_t)x.qe);
+      dst[3] = make_uint2((uint32_t)rid, (uint32_t)x.score);
+      dst[4] = make_uint2((uint32_t)x.truesc, 0u);
+      dst[5] = make_uint2(0u, 0u);
+      dst[6] = make_uint2(0u, (uint32_t)x.w);
+      dst[7] = make_uint2((uint32_t)cov, 0u);
+      dst[8] = make_uint2(0u, (uint32_t)sd.len);
+      dst[9] = make_uint2(0u, __float_as_uint(frac));
+      dst[10] = make_uint2(0u, 0u);
+      tl.cells += x.cells;
+      tl.rows += x.rows;
+      tl.calls += x.calls - 1;
+    }
+    if (wr && i == 0) a.out_n[rd] = (int)__popc(ext);
+  }
+  if (uint32_t* const tr = g_trace) {  // trace_read's record, a group's lanes one word each
+    const uint64_t t_end = __builtin_amdgcn_s_memrealtime();
+    uint32_t v = 1u;  // shape: light
+    v = i == 0 ? (uint32_t)t_start : v;
+    v = i == 1 ? (uint32_t)(t_start >> 32) : v;
+    v = i == 2 ? (uint32_t)t_end : v;
+    v = i == 3 ? (uint32_t)(t_end >> 32) : v;
+    v = i == 4 ? (uint32_t)d.ns : v;
+    v = i == 5 ? (uint32_t)__popc(ext) : v;
+    v = i == 6 ? __builtin_amdgcn_s_getreg((31 << 11) | 20) : v;
+    if (nar && !missed) tr[((size_t)MODE * b.n_reads + rd) * 8 + i] = v;
+  }
+  return __builtin_amdgcn_ballot_w64(nar && missed);
+}
+
+// The light reads of a batch.  With SpecArgs::light_pack (bwagpu_ctx_light_pack,
+// default) wave w takes the read-octets w, w + NW, ...: reads 8 * octet ...
+// 8 * octet + 7.  An octet's narrow reads run packed (light_packed), then its
+// wider ones and a narrow read the final pass missed a result for one after
+// another (light_read).  Without it, and with risky_first, every light read
+// of the wave's share goes through light_read.
+template <int MODE>
+__global__ void __launch_bounds__(kBlock) spec_select_light(DevOpt o, DevRef ref, DevBatch b, SpecArgs a,
+                                                            int tb_bytes) {
+  sel_prio();
+  constexpr bool WRITE = MODE != SEL_EMULATE;
+  __shared__ int32_t MG[kMglN];
+  extern __shared__ __attribute__((aligned(16))) uint8_t lrows[];  // per wave: target rows of an inline extension
+  uint8_t* const tbl = lrows + (threadIdx.x >> 6) * 2 * tb_bytes;
+  uint8_t* const tbr = tbl + tb_bytes;
+  constexpr int kLightList = 64;  // reads a wave lists for light_read before it runs them
+  __shared__ int32_t WL[kBlock / 64][kLightList];
+  int32_t* const wl = WL[threadIdx.x >> 6];
+  for (int x = threadIdx.x; x < kMglN; x += kBlock) MG[x] = max_gap_len(o, x);
+  __syncthreads();
+  const int r = (int)(threadIdx.x & 63);
+  Tally tl{0, 0, 0};
+  // static deal: wave w takes the octets (pack), else the reads w, w + NW, ...
+  // (light reads cost about the same; no queue atomics), the next descriptors
+  // in flight meanwhile.
+  // risky_first: the final pass first takes, in its static share, only the
+  // reads the emulate pass left a round-B task in (rbits): only those can miss, and a
+  // miss is extended inline (one wave, ~0.1 ms per extension, cascades of
+  // several in a read) — so they start first, and every other read is claimed
+  // afterwards in chunks of kLightChunk by whichever wave is free, instead of
+  // waiting behind a wave's misses in its static share.
+  const int NW = (int)gridDim.x * (kBlock / 64);
+  const int w0 = (int)blockIdx.x * (kBlock / 64) + uni((int)(threadIdx.x >> 6));
+  constexpr int kLightChunk = 16;
+  int ph = 0, cb = 0, ce = 0, pbase = w0 - 64 * NW;
+  uint64_t pm = 0;
+  const auto risky = [&](int x) { return ((a.rbits[x >> 5] >> (x & 31)) & 1u) != 0; };
+  const auto next_read = [&]() -> int {
+    if (ph == 0) {  // this wave's static share, the reads with a round-B task, 64 at a time
+      for (;;) {
+        if (pm) {
+          const int i = __builtin_ctzll(pm);
+          pm &= pm - 1;
+          return pbase + i * NW;
+        }
+        pbase += 64 * NW;
+        if (pbase >= b.n_reads) break;
+        const int x = pbase + r * NW;
+        pm = __builtin_amdgcn_ballot_w64(x < b.n_reads && risky(x));
+      }
+      ph = 1;
+    }
+    for (;;) {  // the rest, claimed
+      if (cb >= ce) {
+        int c = 0;
+        if (r == 0) c = atomicAdd(&a.ctr[SPC_LIGHT_CUR], kLightChunk);
+        c = __builtin_amdgcn_readfirstlane(__shfl(c, 0, 64));
+        if (c >= b.n_reads) return b.n_reads;
+        cb = c;
+        ce = min(c + kLightChunk, b.n_reads);
+      }
+      const int y = cb++;
+      if (!risky(y)) return y;
+    }
+  };
+  const bool dyn = MODE == SEL_FINAL && a.risky_first;
+  const bool pack = a.light_pack && !dyn;
+  // a unit: an octet of reads (pack: a group of eight lanes per read), else 64
+  // reads of the wave's share at once (a lane per read), or the one next_read() gives
+  const int n_units = pack ? (b.n_reads + kPackW - 1) / kPackW : b.n_reads;
+  const int unit_reads = pack ? kPackW : dyn ? 1 : 64;
+  const uint64_t first_lanes = pack ? 0x0101010101010101ull : dyn ? 1ull : ~0ull;  // a read's first lane
+  const auto lane_read = [&](int u) { return pack ? kPackW * u + (r >> 3) : dyn ? u : u + r * NW; };
+  // A wave first goes through units — the narrow reads packed, the others
+  // only listed (wl) — then through the list with light_read, and so on while
+  // units are left: the units' per-lane descriptors are not held over
+  // light_read, whose inline extension sets the kernel's register count.
+  const uint64_t lt_mask = r ? (~0ull >> (64 - r)) : 0ull;  // lanes below r
+  int un = dyn ? next_read() : w0;
+  while (un < n_units) {
+    int nw = 0;
+    ReadDesc dn{};
+    if (lane_read(un) < b.n_reads) dn = a.rdesc[lane_read(un)];
+    while (un < n_units && nw + unit_reads <= kLightList) {
+      const ReadDesc d = dn;
+      const int rd = lane_read(un);
+      un = dyn ? next_read() : pack ? un + NW : un + 64 * NW;
+      if (un < n_units && lane_read(un) < b.n_reads) dn = a.rdesc[lane_read(un)];
+      // not the heavy kernel's read, nor one flagged by spec_reads_kernel
+      const bool mine = rd < b.n_reads && !(d.ns > kSelLight || d.nch > kSelLight) && !(d.lq > a.lq_bound);
+      const bool nar = pack && mine && d.ns <= kPackW && d.nch <= kPackW;
+      if (WRITE && mine && !nar && d.ns == 0) a.out_n[rd] = 0;
+      uint64_t wide = __builtin_amdgcn_ballot_w64(mine && !nar && d.ns != 0);
+      if (pack) wide |= light_packed<MODE>(b, a, MG, rd, d, nar, tl);
+      wide &= first_lanes;
+      if ((wide >> r) & 1) wl[nw + (int)__popcll(wide & lt_mask)] = rd;
+      nw += (int)__popcll(wide);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    // the listed reads one after another, the next one's descriptor in flight meanwhile
+    ReadDesc wn{};
+    if (nw) wn = a.rdesc[uni(wl[0])];
+    for (int k = 0; k < nw; ++k) {
+      const ReadDesc u = uniform_desc(wn);
+      const int rd = uni(wl[k]);
+      if (k + 1 < nw) wn = a.rdesc[uni(wl[k + 1])];
+      light_read<MODE>(o, ref, b, a, MG, tbl, tbr, rd, u, tl);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   }
   if constexpr (WRITE) block_stats<64>(tl, a.stats);
 }
@@ -2012,6 +2244,37 @@ __global__ void __launch_bounds__(64) spec_scan_kernel(DevOpt o, DevRef ref, Dev
 // heavy reads (256-2048 measured within the noise)
 constexpr int kScanGrid = 1024;
 
+// The packed light path (bwagpu_ctx_light_pack):
+// BWAGPU_LIGHT_PACK sets the process default (0: one read per wave).
+#ifndef BWAGPU_LIGHT_PACK_DEFAULT
+#define BWAGPU_LIGHT_PACK_DEFAULT 1
+#endif
+int light_pack_default() {
+  static const int v = [] {
+    const char* e = getenv("BWAGPU_LIGHT_PACK");
+    return e && e[0] ? (atoi(e) != 0 ? 1 : 0) : BWAGPU_LIGHT_PACK_DEFAULT;
+  }();
+  return v;
+}
+// ... and its grid's workgroups per CU (BWAGPU_LIGHT_PACK_WGS, an A/B knob)
+#ifndef BWAGPU_LIGHT_PACK_WGS_DEFAULT
+#define BWAGPU_LIGHT_PACK_WGS_DEFAULT 2
+#endif
+static int light_pack_wgs() {
+  static const int v = [] {
+    const char* e = getenv("BWAGPU_LIGHT_PACK_WGS");
+    return std::min(std::max(e && e[0] ? atoi(e) : BWAGPU_LIGHT_PACK_WGS_DEFAULT, 1), 64);
+  }();
+  return v;
+}
+static int device_cus() {
+  int dev = 0, ncu = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu < 1)
+    return 256;
+  return ncu;
+}
+
 // The two selection shapes of one pass: heavy reads on `side` (when given)
 // concurrently with the light reads on `st`; `st` continues once both are done.
 template <int MODE>
@@ -2025,7 +2288,13 @@ static void launch_select(const DevOpt& o, const DevRef& ref, const DevBatch& b,
   }
   if (MODE != SEL_REDO) {  // target rows in LDS only for the final pass's inline extension
     const size_t lds = BWAGPU_LIGHT_INLINE && MODE == SEL_FINAL ? (size_t)(kBlock / 64) * 2 * tb_bytes : 0;
-    const int nb = resident_blocks(spec_select_light<MODE>, lds);
+    int nb = resident_blocks(spec_select_light<MODE>, lds);
+    // packed: the grid by the work (a C2 batch has 8.3 k octets), up to
+    // light_pack_wgs() workgroups per CU, and never more than are resident
+    if (a.light_pack && !(MODE == SEL_FINAL && a.risky_first)) {
+      const int octets = (b.n_reads + kPackW - 1) / kPackW, per_wg = kBlock / 64;
+      nb = std::min(nb, std::max(1, std::min((octets + per_wg - 1) / per_wg, light_pack_wgs() * device_cus())));
+    }
     hipLaunchKernelGGL((spec_select_light<MODE>), dim3(nb), dim3(kBlock), lds, st, o, ref, b, a, tb_bytes);
   }
   if (MODE != SEL_REDO) {  // heavy reads with pair matrices: all pairs at once, then one scan per read

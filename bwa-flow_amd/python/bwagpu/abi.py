@@ -213,6 +213,7 @@ PROTOS = {
     "bwagpu_ctx_ext_form": (C.c_int, [_VP, C.c_int]),
     "bwagpu_ctx_ext_short": (C.c_int, [_VP, C.c_int]),
     "bwagpu_ctx_ext_short_fill": (C.c_int, [_VP, C.c_int]),
+    "bwagpu_ctx_light_pack": (C.c_int, [_VP, C.c_int]),
     "bwagpu_debug_spec_short": (C.c_int, [_VP, _VP, _VP]),
     "bwagpu_ctx_row_bound": (C.c_int, [_VP, C.c_int]),
     "bwagpu_debug_ext_kernel": (C.c_int, [_VP, C.c_int32]),
@@ -273,8 +274,8 @@ def load() -> C.CDLL:
         raise RuntimeError(f"bwagpu: HIP engine library missing at {p}; run __graft_entry__.build()")
     lib = C.CDLL(p)
     for name, (res, args) in PROTOS.items():
-        if name.startswith("bwagpu_debug_") and not hasattr(lib, name):
-            continue  # an A/B build of an older tree (BWAGPU_LIB) may lack a newer diagnostic
+        if (name.startswith("bwagpu_debug_") or name == "bwagpu_ctx_light_pack") and not hasattr(lib, name):
+            continue  # an A/B build of an older tree (BWAGPU_LIB) may lack a newer diagnostic or A/B switch
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

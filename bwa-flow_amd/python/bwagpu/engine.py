@@ -320,6 +320,12 @@ class Engine:
         every short run); -> the previous value"""
         return self.lib.bwagpu_ctx_ext_short_fill(self.ctx, int(percent))
 
+    def light_pack(self, on: int = -1) -> int:
+        """this context's packed light selection (bwagpu_ctx_light_pack): reads
+        of up to eight seeds and chains eight per wave; 0 = one read per wave,
+        -1 = query; -> the previous setting"""
+        return self.lib.bwagpu_ctx_light_pack(self.ctx, int(on))
+
     def row_bound(self, on: int = -1) -> int:
         """this context's row bound in the packed extension kernels
         (bwagpu_ctx_row_bound, default on); -> the previous setting"""

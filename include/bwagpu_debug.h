@@ -102,6 +102,12 @@ int bwagpu_ctx_ext_short(bwagpu_ctx_t *ctx, int q);
    value.  A context starts with BWAGPU_EXT_SHORT_FILL if set, else the compiled
    default. */
 int bwagpu_ctx_ext_short_fill(bwagpu_ctx_t *ctx, int percent);
+/* the packed light selection (default on): spec_select_light runs the reads
+   with at most eight seeds and eight chains eight per wave, in groups of eight
+   lanes; 0: every light read has a wave of its own.  on < 0 only queries;
+   returns the previous setting.  A context starts with BWAGPU_LIGHT_PACK if
+   set, else the compiled default.  Results do not depend on it. */
+int bwagpu_ctx_light_pack(bwagpu_ctx_t *ctx, int on);
 /* diagnostics of the last device-entry batch on `stream` (waits for it), out: 9
    entries.  out[0] = the task sides run in the short phase, all rounds
    (bwagpu_debug_spec_counters' eight words are a fixed layout its callers size
