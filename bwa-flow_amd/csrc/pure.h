@@ -60,9 +60,18 @@ inline int tb_bytes_for(const DevOpt& o, int lq_max) {
   return (n + 15) & ~15;
 }
 
+// the 32-bit kernels (extend_wave, extend_pair): a row's maximum and its last
+// column are one reduction of the int key H << 10 | j (ksw_dev.h), exact while
+// every H of the call is below 2^21.  mem_chain2aln stays far below (a <= 127,
+// reads <= 1023); a bare task's h0 is the caller's (extend_plan refuses it).
+inline bool wave_bound_ok(long hb) { return hb < (1L << 21); }  // hb: a bound on every H of the call
+
 // the packed ranges (extend_quad) for reads up to lq: H <= lq * max(mat) < 4096
-// (the row-max key H << KS | c, KS <= 3), H * 2^sk + 128 < 2^15 (2^sk >
-// max(mat)), and the scan values H + 33 * CPL * e_ins < 2^15
+// (the row-max key H << KS | c is an unsigned 16-bit value: KS = 1..4 in-lane
+// column bits for CPL <= 2 / 4 / 8 / 16 columns per lane, so H < 2^12 at
+// KS = 4; it passes 32767 from H = 2048 on there, which the unsigned reduction
+// takes), H * 2^sk + 128 < 2^15 (2^sk > max(mat); M' is a signed minimum), and
+// the scan values H + 33 * CPL * e_ins < 2^15 (CPL <= 8 with 32 lanes, 16 with 16)
 inline bool quad_bound_ok(const DevOpt& o, long hb) {  // hb: a bound on every H of the call
   if (o.max_mat < 1 || o.max_mat > 15) return false;
   const int sk = 32 - __builtin_clz((unsigned)o.max_mat);

@@ -58,6 +58,8 @@ inline int extend_plan(const DevOpt& o, bool quad, int32_t n, const bwagpu_ext_t
         !in_pool(t.toff, t.tlen, tpool_len) || t.w < 0)
       return *why = "task outside its pools", BWAGPU_E_INVAL;
     if (t.qlen >= max_q) return *why = "qlen too long", BWAGPU_E_UNSUPPORTED;
+    if (!wave_bound_ok(t.h0 + (long)t.qlen * o.max_mat))
+      return *why = "h0 + qlen * max score >= 2^21: over the 32-bit kernels' row-max key", BWAGPU_E_UNSUPPORTED;
     int v = kNumExtVariants - 1;
     for (int i = kNumExtVariants - 1; i >= 0; --i)
       if (t.qlen + 1 <= kExtVariants[i].max_len()) v = i;

@@ -183,7 +183,11 @@ typedef struct {
   const bwagpu_seed_t *seeds;    /* [n_seeds]    */
 } bwagpu_batch_t;
 
-/* One ksw_extend2 call: query = qpool[qoff..qoff+qlen), target = tpool[toff..toff+tlen). */
+/* One ksw_extend2 call: query = qpool[qoff..qoff+qlen), target = tpool[toff..toff+tlen).
+   h0 is the caller's: a task with h0 <= 0 gets score -1 (the reference asserts h0 > 0), and
+   bwagpu_extend_batch refuses a batch with BWAGPU_E_UNSUPPORTED when some task's
+   h0 + qlen * max(mat) reaches 2^21 = 2097152 (no H of the call can pass that sum; the
+   kernels keep a row's maximum and its last column in one int, H << 10 | j). */
 typedef struct {
   int64_t qoff, toff;
   int32_t qlen, tlen;

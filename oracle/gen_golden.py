@@ -215,7 +215,31 @@ def gen_cigar(tmp):
               f"multi-try jobs={int((np.bincount(cc['task'], minlength=len(ct)) > 1).sum())}")
 
 
+def gen_range():
+    """the families of tests/range_cases.py (the edges of the packed kernels' range gates,
+    both sides) through the reference's own ksw_extend2 -> tests/golden/ksw_range.npz,
+    keys "<family>__<side>__<array>": options, tasks, pools, results"""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import range_cases
+    out, n = {}, 0
+    for name, side, f in range_cases.flat():
+        res, _ = oracle.extend("ref", f.opt, f.tasks, f.qpool, f.tpool)
+        k = f"{name}__{side}__"
+        out[k + "opt_int"] = np.array([f.opt[x] for x in ("a", "b", "o_del", "e_del", "o_ins", "e_ins", "pen_clip5",
+                                                          "pen_clip3", "w", "zdrop")], np.int32)
+        out[k + "opt_mat"] = np.asarray(f.opt["mat"], np.int8)
+        out[k + "tasks"], out[k + "task_res"], out[k + "qpool"], out[k + "tpool"] = f.tasks, res, f.qpool, f.tpool
+        n += len(f.tasks)
+    np.savez_compressed(os.path.join(GOLD, "ksw_range.npz"), **out)
+    print(f"[gen_golden] ksw_range: {len(out) // 6} family sides, {n} tasks")
+
+
 def main():
+    if "--only-range" in sys.argv:
+        if oracle.ref_lib() is None:
+            sys.exit("build the reference first: make -C oracle")
+        gen_range()
+        return
     if "--only-align2" in sys.argv:
         gen_align2(np.random.default_rng(2025))
         return
@@ -251,6 +275,7 @@ def main():
                             opt_mat=np.asarray(opt["mat"], np.int8), tasks=tasks, task_res=res, qpool=qp, tpool=tp)
         print(f"[gen_golden] {name}: tasks={len(tasks)} q={len(qp)} t={len(tp)}")
     gen_align2(np.random.default_rng(2025))
+    gen_range()
 
 
 if __name__ == "__main__":

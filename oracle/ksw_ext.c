@@ -35,7 +35,7 @@ static int gap_cap(int qlen, int best, int end_bonus, int o, int e)
 static int ksw_extend2_core(int qlen, const uint8_t *query, int tlen, const uint8_t *target, int m,
                             const int8_t *mat, int o_del, int e_del, int o_ins, int e_ins, int w,
                             int end_bonus, int zdrop, int h0, int *qle, int *tle, int *gtle,
-                            int *gscore, int *max_off, int64_t *cells, int row_bound)
+                            int *gscore, int *max_off, int64_t *cells, int row_bound, int64_t *ext)
 {
   const int oe_del = o_del + e_del, oe_ins = o_ins + e_ins;
   int32_t *hdiag, *ecol;
@@ -43,6 +43,7 @@ static int ksw_extend2_core(int qlen, const uint8_t *query, int tlen, const uint
   int best_mat = 0, lo, hi, i, j;
   int best, best_i, best_j, end_i, end_sc, off;
   int64_t n_cells = 0, n_rows = 0;
+  int64_t x_h = h0, x_e = 0, x_f = 0, x_z = 0; /* ext: the largest H, E, F and z-drop term */
 
   if (h0 <= 0) return -1; /* reference: assert(h0 > 0), ksw.c:385 */
 
@@ -88,6 +89,9 @@ static int ksw_extend2_core(int qlen, const uint8_t *query, int tlen, const uint
       if (h >= rmax) { rmax = h; rarg = j; } /* ties -> last column */
       ecol[j] = imax(ev - e_del, imax(mv - oe_del, 0));
       f = imax(f - e_ins, imax(mv - oe_ins, 0));
+      if (h > x_h) x_h = h;
+      if (ecol[j] > x_e) x_e = ecol[j];
+      if (f > x_f) x_f = f;
     }
     n_rows++;
     if (hi > lo) n_cells += hi - lo;
@@ -104,10 +108,11 @@ static int ksw_extend2_core(int qlen, const uint8_t *query, int tlen, const uint
       best_i = i;
       best_j = rarg;
       off = imax(off, abs(rarg - i));
-    } else if (zdrop > 0) {
+    } else {
       int di = i - best_i, dj = rarg - best_j;
-      int drop = di > dj ? best - rmax - (di - dj) * e_del : best - rmax - (dj - di) * e_ins;
-      if (drop > zdrop) break;
+      int term = di > dj ? (di - dj) * e_del : (dj - di) * e_ins; /* |di - dj| e, ksw.c:459-463 */
+      if (term > x_z) x_z = term;
+      if (zdrop > 0 && best - rmax - term > zdrop) break;
     }
     /* NOT part of ksw_extend2: the row bound the GPU kernels apply
        (ksw_dev.h extend_quad), here only to test its
@@ -138,6 +143,7 @@ static int ksw_extend2_core(int qlen, const uint8_t *query, int tlen, const uint
   if (gscore) *gscore = end_sc;
   if (max_off) *max_off = off;
   if (cells) { cells[0] += n_cells; cells[1] += n_rows; }
+  if (ext) { ext[0] = x_h; ext[1] = x_e; ext[2] = x_f; ext[3] = x_z; ext[4] = n_rows; }
   return best;
 }
 
@@ -147,7 +153,7 @@ int oracle_ksw_extend2(int qlen, const uint8_t *query, int tlen, const uint8_t *
                        int *gscore, int *max_off, int64_t *cells)
 {
   return ksw_extend2_core(qlen, query, tlen, target, m, mat, o_del, e_del, o_ins, e_ins, w, end_bonus, zdrop,
-                          h0, qle, tle, gtle, gscore, max_off, cells, 0);
+                          h0, qle, tle, gtle, gscore, max_off, cells, 0, NULL);
 }
 
 /* the same calls with the row bound (tests only: the bound's claim) */
@@ -160,7 +166,28 @@ int oracle_extend_batch_bounded(const bwagpu_opt_t *opt, int32_t n_tasks, const 
     bwagpu_ext_result_t *r = &results[k];
     r->score = ksw_extend2_core(t->qlen, qpool + t->qoff, t->tlen, tpool + t->toff, 5, opt->mat, opt->o_del,
                                 opt->e_del, opt->o_ins, opt->e_ins, t->w, t->end_bonus, t->zdrop, t->h0, &r->qle,
-                                &r->tle, &r->gtle, &r->gscore, &r->max_off, cells, 1);
+                                &r->tle, &r->gtle, &r->gscore, &r->max_off, cells, 1, NULL);
+  }
+  return 0;
+}
+
+/* the same calls (no row bound) with the extremes of each: ext[5 k ..] = the
+   largest H of any cell (h0 included), the largest E and F, the largest z-drop
+   term |(i - max_i) - (j - max_j)| e of a row that did not raise the maximum
+   (ksw.c:459-463; taken whether or not zdrop > 0), and the rows run.  Tests
+   only: how close a call comes to the GPU kernels' 16-bit range gates. */
+int oracle_extend_batch_extremes(const bwagpu_opt_t *opt, int32_t n_tasks, const bwagpu_ext_task_t *tasks,
+                                 const uint8_t *qpool, const uint8_t *tpool, bwagpu_ext_result_t *results,
+                                 int64_t *cells, int64_t *ext)
+{
+  for (int32_t k = 0; k < n_tasks; ++k) {
+    const bwagpu_ext_task_t *t = &tasks[k];
+    bwagpu_ext_result_t *r = &results[k];
+    int64_t *x = ext + 5 * (int64_t)k;
+    x[0] = x[1] = x[2] = x[3] = x[4] = 0; /* h0 <= 0: no DP */
+    r->score = ksw_extend2_core(t->qlen, qpool + t->qoff, t->tlen, tpool + t->toff, 5, opt->mat, opt->o_del,
+                                opt->e_del, opt->o_ins, opt->e_ins, t->w, t->end_bonus, t->zdrop, t->h0, &r->qle,
+                                &r->tle, &r->gtle, &r->gscore, &r->max_off, cells, 0, x);
   }
   return 0;
 }

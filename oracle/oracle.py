@@ -45,6 +45,8 @@ def oracle_lib():
     lib.oracle_extend_batch.restype = C.c_int
     lib.oracle_extend_batch_bounded.argtypes = [C.POINTER(abi.Opt), C.c_int32, _VP, _VP, _VP, _VP, _VP]
     lib.oracle_extend_batch_bounded.restype = C.c_int
+    lib.oracle_extend_batch_extremes.argtypes = [C.POINTER(abi.Opt), C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP]
+    lib.oracle_extend_batch_extremes.restype = C.c_int
     lib.oracle_align2_batch.argtypes = [C.POINTER(abi.Opt), C.c_int32, _VP, _VP, _VP, _VP, _VP]
     lib.oracle_align2_batch.restype = C.c_int
     lib.oracle_reg2aln_batch.argtypes = [C.POINTER(abi.Opt), C.POINTER(abi.Bns), _VP, C.c_int32, _VP, _VP,
@@ -172,6 +174,25 @@ def extend(which: str, opt: dict, tasks, qpool, tpool):
         raise RuntimeError("oracle/_ref/libbwaref.so not available")
     lib.ref_extend_batch(C.byref(o), len(tasks), _ptr(tasks), _ptr(qpool), _ptr(tpool), _ptr(res))
     return res[:len(tasks)], None
+
+
+EXTREMES = ("h", "e", "f", "zterm", "rows")
+
+
+def extend_extremes(opt: dict, tasks, qpool, tpool):
+    """oracle_extend_batch with each call's extremes -> (results, cells, int64[n, 5]: the
+    largest H, E, F, z-drop term |(i - max_i) - (j - max_j)| e, and the rows run; EXTREMES
+    names the columns)"""
+    o = abi.opt_from_dict(opt)
+    tasks = np.ascontiguousarray(tasks, abi.EXT_TASK_DTYPE)
+    qpool = np.ascontiguousarray(qpool, np.uint8)
+    tpool = np.ascontiguousarray(tpool, np.uint8)
+    res = np.zeros(max(len(tasks), 1), abi.EXT_RES_DTYPE)
+    cells = np.zeros(2, np.int64)
+    ext = np.zeros((max(len(tasks), 1), 5), np.int64)
+    oracle_lib().oracle_extend_batch_extremes(C.byref(o), len(tasks), _ptr(tasks), _ptr(qpool), _ptr(tpool),
+                                              _ptr(res), _ptr(cells), _ptr(ext))
+    return res[:len(tasks)], cells, ext[:len(tasks)]
 
 
 def align2(which: str, opt: dict, tasks, qpool, tpool):

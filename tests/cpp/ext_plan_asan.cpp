@@ -251,6 +251,44 @@ int main() {
   EXPECT(tb_bytes_for(wide, 160) > 1792);  // four waves x 4 groups x 2 rows pass 64 KB
   EXPECT(p.quad && p.bin[0].code == 18 && p.short_q == 0 && p.tb_short == 0);
 
+  // the plan at the edges of its gates (quad_scores_ok(o, 256), quad_rows_ok(o, tb_bytes),
+  // quad_key8_ok(o, 160); pure.h), the option sets of tests/test_gpu_packed_ranges.py:
+  auto scored = [](int a) {
+    DevOpt o = default_opt();
+    o.a = o.max_mat = a;
+    for (int i = 0; i < 4; ++i) o.mat[i * 5 + i] = (int8_t)a;
+    return o;
+  };
+  auto ext_gap = [](DevOpt o, int e) {
+    o.e_del = o.e_ins = e, o.oe_del = o.o_del + e, o.oe_ins = o.o_ins + e;
+    return o;
+  };
+  // max_mat 7: hb = 256 * 7 = 1792, (1792 << 3) + 128 = 14464; max_mat 8: (2048 << 4) + 128 = 32896
+  p = ext_plan(scored(7), 0, tb_bytes_for(scored(7), 257), 63);
+  EXPECT(p.quad && bin_is(p.bin[0], SIDE4, 32, 8, false, 15, true) && bin_is(p.bin[1], EXT4, 16, 16, false, 0, false));
+  p = ext_plan(scored(8), 0, tb_bytes_for(scored(8), 257), 63);
+  EXPECT(!p.quad && p.bin[0].code == 2 && p.bin[1].family == EXT2);
+  EXPECT(quad_scores_ok(scored(7), 256) && !quad_scores_ok(scored(8), 256));
+  // reads up to 250: the band cap (250 + 5 - 6) / e + 1 is 5 at e = 54 and 55, so 250 + 5 + 2 -> 272
+  // row bytes; (272 + 256) * 54 = 28512 < 28672 <= 29040 = 528 * 55.  Reads up to 257: 272 too.
+  for (int lq : {250, 257}) {
+    EXPECT(tb_bytes_for(ext_gap(d, 54), lq) == 272 && tb_bytes_for(ext_gap(d, 55), lq) == 272);
+    p = ext_plan(ext_gap(d, 54), 0, 272, 63);
+    EXPECT(p.quad && p.bin[0].code == 18);
+    p = ext_plan(ext_gap(d, 55), 0, 272, 63);
+    EXPECT(!p.quad && p.bin[0].code == 2);
+  }
+  // reads up to 150: the cap (150 + 5 - 6) / e + 1 is 3, 150 + 3 + 2 -> 160; 416 * 68 = 28288, 416 * 69 = 28704
+  EXPECT(tb_bytes_for(ext_gap(d, 68), 150) == 160 && tb_bytes_for(ext_gap(d, 69), 150) == 160);
+  EXPECT(ext_plan(ext_gap(d, 68), 0, 160, 63).quad && !ext_plan(ext_gap(d, 69), 0, 160, 63).quad);
+  EXPECT(quad_scores_ok(ext_gap(d, 69), 256));  // the rows gate alone refuses it
+  // max_mat 7 with e = 54: the cap grows with the scores ((257 * 7 + 5 - 6) / 54 + 1 = 34), 257 + 34 + 2 ->
+  // 304 row bytes, 560 * 54 = 30240: the rows gate refuses what either option alone passes
+  EXPECT(tb_bytes_for(ext_gap(scored(7), 54), 257) == 304 && quad_scores_ok(ext_gap(scored(7), 54), 256));
+  EXPECT(!ext_plan(ext_gap(scored(7), 54), 0, 304, 63).quad);
+  // the first bin's 8-bit key: 160 * max_mat <= 255
+  EXPECT(quad_key8_ok(d, 160) && quad_key8_ok(d, 255) && !quad_key8_ok(d, 256) && !quad_key8_ok(scored(2), 128));
+
   if (g_fail) {
     std::printf("ext_plan_asan: %d checks failed\n", g_fail);
     return 1;

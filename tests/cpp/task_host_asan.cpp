@@ -229,6 +229,118 @@ static void test_extend_mixed() {  // the plan of a mixed batch
   EXPECT((size_t)off == c.t.size() && p.count[3] > 0 && p.count[0] > 0 && p.count[2] > 0);
 }
 
+// ---------------------------------------------------------------- the range gates
+// Both sides of every boundary of the packed kernel's gates on the bare path
+// (task_host.h extend_plan: quad_bound_ok(h0 + qlen * max_mat) and
+// quad_rows_ok(tlen), pure.h): the last admitted value lands in list
+// kNumExtVariants (extend4_kernel), the first refused one in a wave list.  The
+// numbers are those of tests/range_cases.py, whose GPU test relies on this
+// routing to know which kernel it ran.
+static DevOpt scored_opt(int a, int b) {
+  DevOpt o = default_opt();
+  o.a = a, o.max_mat = a;
+  for (int i = 0; i < 4; ++i)
+    for (int j = 0; j < 4; ++j) o.mat[i * 5 + j] = (int8_t)(i == j ? a : -b);
+  return o;
+}
+static void set_gaps(DevOpt& o, int o_del, int e_del, int o_ins, int e_ins) {
+  o.o_del = o_del, o.e_del = e_del, o.o_ins = o_ins, o.e_ins = e_ins;
+  o.oe_del = o_del + e_del, o.oe_ins = o_ins + e_ins;
+}
+// one task -> the list it lands in (0 .. kNumExtVariants), or -rc
+static int list_of(const DevOpt& o, int qlen, int tlen, int h0, const char** why = nullptr) {
+  Ext c;
+  c.o = o;
+  c.quad = true;
+  c.q.assign(1024, 1);
+  c.tp.assign(16384, 2);
+  c.t = {ext(0, qlen, 0, tlen, h0)};
+  const int rc = c.run();
+  if (why) *why = c.why;
+  if (rc != BWAGPU_OK) return -rc;
+  for (int v = 0; v < kExtLists; ++v)
+    if (c.plan.count[v]) return v;
+  return -100;
+}
+static int wave_list(int qlen) { return qlen + 1 <= 192 ? 0 : (qlen + 1 <= 256 ? 1 : 2); }
+#define EXPECT_FLIP(o_in, o_out, qlen, tl_in, tl_out, h0_in, h0_out)        \
+  do {                                                                      \
+    EXPECT(list_of(o_in, qlen, tl_in, h0_in) == kNumExtVariants);           \
+    EXPECT(list_of(o_out, qlen, tl_out, h0_out) == wave_list(qlen));        \
+  } while (0)
+
+static void test_extend_ranges() {
+  const DevOpt d = default_opt();
+  // hb < 4096 (binding for max_mat 1 and 3)
+  EXPECT_FLIP(d, d, 255, 255, 255, 4095 - 255, 4096 - 255);
+  EXPECT_FLIP(d, d, 1, 1, 1, 4094, 4095);
+  const DevOpt a3 = scored_opt(3, 4);
+  EXPECT_FLIP(a3, a3, 255, 255, 255, 4095 - 765, 4096 - 765);
+  // (hb << sk) + 128 < 32768: sk = 3 for max_mat 4..7 -> hb <= 4079; sk = 4 for 8..15 -> hb <= 2039
+  const DevOpt a4 = scored_opt(4, 4), a7 = scored_opt(7, 4), a8 = scored_opt(8, 4), a15 = scored_opt(15, 4);
+  EXPECT_FLIP(a4, a4, 255, 255, 255, 4079 - 1020, 4080 - 1020);
+  EXPECT_FLIP(a7, a7, 255, 255, 255, 2294, 2295);
+  EXPECT_FLIP(a8, a8, 254, 254, 254, 2039 - 2032, 2040 - 2032);
+  EXPECT_FLIP(a15, a15, 135, 135, 135, 2039 - 2025, 2040 - 2025);
+  DevOpt diag = scored_opt(2, 4);  // one large diagonal cell decides max_mat
+  diag.mat[0] = 15, diag.max_mat = 15;
+  EXPECT_FLIP(diag, diag, 135, 135, 135, 14, 15);
+  DevOpt m127 = scored_opt(4, 127), m128 = scored_opt(4, 127);  // matrix entries in [-127, 127]
+  m128.mat[1] = (int8_t)-128;
+  EXPECT_FLIP(m127, m128, 255, 255, 255, 3059, 3059);
+  DevOpt m16 = scored_opt(15, 4), m0 = scored_opt(1, 4);  // max_mat 1..15
+  m16.mat[6] = 16, m16.max_mat = 16;
+  EXPECT_FLIP(a15, m16, 100, 100, 100, 1, 1);
+  for (int i = 0; i < 25; ++i) m0.mat[i] = (int8_t)std::min<int>(m0.mat[i], 0);
+  m0.max_mat = 0;
+  EXPECT_FLIP(d, m0, 100, 100, 100, 50, 50);
+  // o_del + 128 < 32768, oe_ins + 128 < 32768
+  DevOpt g_in = d, g_out = d;
+  set_gaps(g_in, 32639, 1, 6, 1), set_gaps(g_out, 32640, 1, 6, 1);
+  EXPECT_FLIP(g_in, g_out, 255, 255, 255, 3840, 3840);
+  set_gaps(g_in, 6, 1, 32638, 1), set_gaps(g_out, 6, 1, 32639, 1);
+  EXPECT_FLIP(g_in, g_out, 255, 255, 255, 3840, 3840);
+  set_gaps(g_in, 32638, 1, 32638, 1), set_gaps(g_out, 32639, 1, 32639, 1);  // o_del == o_ins
+  EXPECT_FLIP(g_in, g_out, 255, 255, 255, 3840, 3840);
+  // hb + 264 e_ins < 32768 at e_ins = 111 (two target rows at the most: the rows gate)
+  DevOpt sc = d;
+  set_gaps(sc, 6, 1, 1, 111);
+  EXPECT_FLIP(sc, sc, 255, 2, 2, 3463 - 255, 3464 - 255);
+  EXPECT_FLIP(sc, sc, 1, 2, 3, 3462, 3462);  // 258 * 111 = 28638, 259 * 111 = 28749
+  // (tlen + 256) * max(e_del, e_ins) < 28672
+  const int te[3][2] = {{1, 111}, {256, 55}, {768, 27}};
+  for (auto& x : te) {
+    DevOpt r_in = d, r_out = d;
+    set_gaps(r_in, 6, x[1], 6, x[1]), set_gaps(r_out, 6, x[1] + 1, 6, x[1] + 1);
+    EXPECT_FLIP(r_in, r_out, 255, x[0], x[0], 3000 - 255, 3000 - 255);
+    set_gaps(r_out, 6, x[1] + 1, 6, 1);  // either extension penalty alone
+    EXPECT(list_of(r_out, 255, x[0], 2745) == 1);
+    set_gaps(r_out, 6, 1, 6, x[1] + 1);
+    EXPECT(list_of(r_out, 255, x[0], 2745) == 1);
+  }
+  EXPECT_FLIP(d, d, 255, 16383, 16384, 3840, 3840);  // rows < 16384
+  // the 32-bit kernels' own ceiling (wave_bound_ok): hb < 2^21, whichever list
+  const char* why = nullptr;
+  const int ql[] = {100, 255, 700, 1022};
+  for (int q : ql) {
+    EXPECT(list_of(d, q, q, (1 << 21) - 1 - q) == wave_list(q));
+    EXPECT(list_of(d, q, q, (1 << 21) - q, &why) == -BWAGPU_E_UNSUPPORTED);
+    EXPECT(is(why, "h0 + qlen * max score >= 2^21: over the 32-bit kernels' row-max key"));
+  }
+  EXPECT(list_of(a15, 1022, 100, (1 << 21) - 1 - 15 * 1022) == 2);
+  EXPECT(list_of(a15, 1022, 100, (1 << 21) - 15 * 1022) == -BWAGPU_E_UNSUPPORTED);
+  EXPECT(list_of(d, 0, 0, (1 << 21) - 1) == 0 && list_of(d, 0, 0, 1 << 21) == -BWAGPU_E_UNSUPPORTED);
+  EXPECT(list_of(d, 1000, 10, I32MAX) == -BWAGPU_E_UNSUPPORTED);  // the sum is taken in 64 bits
+  {  // in task order with the other refusals; wave-only plans (quad off) refuse it too
+    Ext c = ext_base();
+    c.t[1].h0 = 1 << 21;
+    c.t[2].qlen = 1024;
+    EXPECT(c.run() == BWAGPU_E_UNSUPPORTED && std::strstr(c.why, "2^21"));
+    c.t[0].qlen = 1024;
+    EXPECT(c.run() == BWAGPU_E_UNSUPPORTED && is(c.why, "qlen too long"));
+  }
+}
+
 // ---------------------------------------------------------------- align2
 struct A2 {
   DevOpt o = default_opt();
@@ -429,6 +541,7 @@ static void test_stream() {
 int main() {
   test_extend();
   test_extend_mixed();
+  test_extend_ranges();
   test_align2();
   test_stream();
   if (g_fail) {

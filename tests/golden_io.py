@@ -58,6 +58,23 @@ def load_tasks(name):
         z["qpool"], z["tpool"]
 
 
+def load_range():
+    """tests/golden/ksw_range.npz (oracle/gen_golden.py --only-range: the families of
+    tests/range_cases.py through the reference's ksw_extend2) ->
+    {(family, side): (opt, tasks, expected results, qpool, tpool)}"""
+    z = _npz("ksw_range")
+    out = {}
+    for key in z.files:
+        if key.endswith("__tasks"):
+            name, side, _ = key.split("__")
+            k = f"{name}__{side}__"
+            opt = dict(zip(OPT_KEYS, z[k + "opt_int"].tolist()))
+            opt["mat"] = z[k + "opt_mat"].astype(np.int8)
+            out[(name, side)] = (opt, z[k + "tasks"].astype(abi.EXT_TASK_DTYPE),
+                                 z[k + "task_res"].astype(abi.EXT_RES_DTYPE), z[k + "qpool"], z[k + "tpool"])
+    return out
+
+
 def load_align2(name):
     """ksw_align2 set -> opt, tasks, expected kswr_t records, qpool, tpool"""
     z = _npz(name)
