@@ -347,6 +347,8 @@ void destroy_ctx(bwagpu_ctx_t* ctx) {
   }
   if (ctx->ch_cs.fork) (void)hipEventDestroy(ctx->ch_cs.fork);
   ctx->ch_slot.d_out.release(); ctx->ch_slot.d_n.release(); ctx->ch_slot.d_stats.release();
+  // the last bwagpu_reg2aln_device / _jobs_device call may still be running on the r2d_* scratch
+  if (ctx->r2d_done && ctx->r2d_pending) (void)hipEventSynchronize(ctx->r2d_done);
   for (DevBuf* b : {&ctx->ex_tasks, &ctx->ex_list, &ctx->ex_q, &ctx->ex_t, &ctx->ex_res, &ctx->ex_stats, &ctx->a2_tasks,
                     &ctx->a2_q, &ctx->a2_t, &ctx->a2_out, &ctx->a2_scratch, &ctx->a2_lists, &ctx->a2_counts, &ctx->a2_boff,
                     &ctx->r2_tasks, &ctx->r2_q, &ctx->r2_out, &ctx->r2_cig, &ctx->r2_md, &ctx->r2_lists, &ctx->r2_z,
@@ -361,8 +363,12 @@ void destroy_ctx(bwagpu_ctx_t* ctx) {
                     &ctx->ch_cso, &ctx->ch_rid, &ctx->ch_cfrac, &ctx->ch_out, &ctx->ch_seeds, &ctx->ch_regoff,
                     &ctx->ch_regc, &ctx->rp_stats, &ctx->pe_isize, &ctx->pe_cnt, &ctx->rs_pair, &ctx->rs_soff,
                     &ctx->rs_tab, &ctx->rs_toff, &ctx->rs_boff, &ctx->rs_qpool, &ctx->rs_ctr, &ctx->rs_scr,
-                    &ctx->ps_scratch, &ctx->ps_log, &ctx->ps_erfc})
+                    &ctx->ps_scratch, &ctx->ps_log, &ctx->ps_erfc, &ctx->r2d_keys, &ctx->r2d_lists, &ctx->r2d_tab,
+                    &ctx->r2d_z, &ctx->r2d_sums})
     b->release();
+  ctx->r2d_htab.release();
+  for (hipEvent_t e : {ctx->r2d_done, ctx->r2d_ev[0], ctx->r2d_ev[1]})
+    if (e) (void)hipEventDestroy(e);
   ctx->stg.release();
   for (hipEvent_t e : ctx->rs_ev)
     if (e) (void)hipEventDestroy(e);

@@ -259,6 +259,172 @@ int bwagpu_reg2aln_batch(bwagpu_ctx_t* ctx, int32_t n, const bwagpu_reg2aln_task
   return BWAGPU_OK;
 }
 
+// The CIGAR kernel on jobs that are already in device memory.
+// The device classifies and bins (reg2aln_classify_kernel), the bin table comes
+// to the host once, and from its measured maxima the bins get the capacities,
+// grids and HBM slices of bwagpu_reg2aln_batch's make_args — those formulas are
+// written a second time here on purpose (§19: that body is left alone).
+int bwagpu_reg2aln_device(bwagpu_ctx_t* ctx, int32_t n_cap, const int32_t* dev_n_tasks,
+                          const bwagpu_reg2aln_task_t* dev_tasks, const uint8_t* dev_qpool, int64_t qpool_len,
+                          int32_t max_ops, int32_t max_md, bwagpu_aln_t* dev_out, uint32_t* dev_cigar, char* dev_md,
+                          void* stream) {
+  if (!ctx || n_cap < 0 || max_ops < 1 || max_md < 1 || qpool_len < 0 ||
+      (n_cap && (!dev_tasks || !dev_out || !dev_cigar || !dev_md || (qpool_len && !dev_qpool))))
+    return BWAGPU_E_INVAL;
+  if (n_cap == 0) return BWAGPU_OK;
+  const bool timing = ctx->r2d_timing;  // bwagpu_debug_reg2aln_times
+  const auto t_call = std::chrono::steady_clock::now();
+  const DevOpt& o = ctx->opt;
+  hipStream_t st = nullptr;
+  TRY(entry_stream(ctx, stream, &st));
+  constexpr int kKeys = kR2Bins * kR2CostClasses;
+  const size_t list_bytes = sizeof(int32_t) * (size_t)n_cap, tab_bytes = sizeof(int32_t) * (kR2TabWords + kKeys);
+  // an earlier device-form call, on any stream, may still be running on the scratch: a buffer grows
+  // (is freed) only once that call has finished, and this call's stream touches none of it before
+  if (ctx->r2d_pending && (list_bytes > ctx->r2d_keys.cap || list_bytes > ctx->r2d_lists.cap ||
+                           tab_bytes > ctx->r2d_tab.cap))
+    HIPC(hipEventSynchronize(ctx->r2d_done), "event sync");
+  if (ctx->r2d_pending) HIPC(hipStreamWaitEvent(st, ctx->r2d_done, 0), "stream wait");
+  HIPC(ctx->r2d_keys.ensure(list_bytes), "hipMalloc");
+  HIPC(ctx->r2d_lists.ensure(list_bytes), "hipMalloc");
+  HIPC(ctx->r2d_tab.ensure(tab_bytes), "hipMalloc");  // table | scatter cursors
+  HIPC(ctx->r2d_htab.ensure(sizeof(int32_t) * kR2TabWords), "hipHostMalloc");
+  if (!ctx->r2d_done) HIPC(hipEventCreateWithFlags(&ctx->r2d_done, hipEventDisableTiming), "event");
+  if (timing)
+    for (hipEvent_t& e : ctx->r2d_ev)
+      if (!e) HIPC(hipEventCreate(&e), "event");
+  int32_t* const d_tab = ctx->r2d_tab.as<int32_t>();
+  int32_t* const keys = ctx->r2d_keys.as<int32_t>();
+  const int32_t* const h = ctx->r2d_htab.as<int32_t>();
+  ctx->r2d_timed = false;
+  // every way out from here on leaves the event behind what this call enqueued
+  struct Done {
+    bwagpu_ctx_t* ctx;
+    hipStream_t st;
+    ~Done() { ctx->r2d_pending = hipEventRecord(ctx->r2d_done, st) == hipSuccess || ctx->r2d_pending; }
+  } done{ctx, st};
+  HIPC(hipMemsetAsync(d_tab, 0, sizeof(int32_t) * (kR2TabWords + kKeys), st), "memset");
+  HIPC(launch_reg2aln_classify(o, ctx->ref.l_pac, qpool_len, n_cap, dev_n_tasks, dev_tasks, keys, dev_out, d_tab, st),
+       "reg2aln classify launch");
+  HIPC(hipMemcpyAsync(ctx->r2d_htab.p, d_tab, sizeof(int32_t) * kR2TabWords, hipMemcpyDeviceToHost, st), "D2H");
+  const auto t_wait = std::chrono::steady_clock::now();
+  // the stream waited for the previous device-form call first, so that call has finished too
+  HIPC(hipStreamSynchronize(st), "reg2aln classification");
+  if (timing)
+    ctx->r2d_wait_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_wait).count();
+  // the one list: bins in order, inside a bin the cost classes from the largest down
+  R2Offsets off{};
+  int32_t bin_off[kR2Bins], at = 0;
+  for (int b = 0; b < kR2Bins; ++b) {
+    bin_off[b] = at;
+    for (int c = 0; c < kR2CostClasses; ++c) {
+      off.at[b * kR2CostClasses + c] = at;
+      at += h[kR2TabClass + b * kR2CostClasses + c];
+    }
+    if (at - bin_off[b] != h[4 * b] || at > n_cap) return fail(ctx, BWAGPU_E_DEVICE, "reg2aln bin table is inconsistent");
+  }
+  struct Launch { int bk, cls, n; int32_t off; int64_t work; int wpb, waves; R2AArgs a; };
+  std::vector<Launch> launches;
+  for (int b = 0; b < kR2Bins; ++b)
+    if (h[4 * b])
+      launches.push_back({b / 3, b % 3, h[4 * b], bin_off[b], (int64_t)h[4 * b] * ((int64_t)h[4 * b + 3] + h[4 * b + 1] + h[4 * b + 2])});
+  std::sort(launches.begin(), launches.end(), [](const Launch& x, const Launch& y) { return x.work > y.work; });
+  // capacities, grids (HBM matrix slices: one per launched wave, at most 1 GiB per bin)
+  size_t zoff = 0;
+  for (Launch& L : launches) {
+    const int b = L.bk * 3 + L.cls;
+    R2AArgs& a = L.a;
+    a = R2AArgs{};
+    a.tasks = dev_tasks, a.qpool = dev_qpool, a.list = ctx->r2d_lists.as<int32_t>() + L.off, a.n = L.n;
+    a.max_ops = max_ops, a.max_md = max_md, a.out = dev_out, a.cigar = dev_cigar, a.md = dev_md;
+    // the issue of this field: a producer's count that stays on the device.  Here it is the table word
+    // the host has just read into a.n, so min(a.n, *dev_n) = a.n; but the running bins now read the
+    // table, which the next call zeroes: one more reason why r2d_done orders the calls
+    a.dev_n = d_tab + 4 * b;
+    a.lds_per_wave = r2_lds_per_wave(h[4 * b + 1], h[4 * b + 2], L.cls, &a.qcap, &a.rcap, &a.ocap);
+    L.wpb = L.cls == 1 ? 1 : 4;  // LDS-heavy bins: one wave per workgroup packs LDS finer
+    // every job fits a workgroup on its own (r2_classify); the longest query and
+    // the longest window of a bin may come from two jobs and fit only fewer waves
+    while ((size_t)L.wpb * a.lds_per_wave > (size_t)kR2LdsPerBlock && L.wpb > 1) L.wpb >>= 1;
+    if ((size_t)L.wpb * a.lds_per_wave > (size_t)kR2LdsPerBlock)
+      return fail(ctx, BWAGPU_E_DEVICE, "reg2aln bin needs more LDS than a workgroup has");
+    a.zstride = L.cls == 2 ? (((int64_t)h[4 * b + 3] + 255) & ~(int64_t)255) : 0;
+    L.waves = r2_resident_waves(kR2CD[L.bk], (size_t)L.wpb * a.lds_per_wave, L.wpb);
+    if (L.cls == 2) {
+      L.waves = (int)std::min<int64_t>(L.waves, std::max<int64_t>(4, ((int64_t)1 << 30) / a.zstride));
+      zoff += (size_t)a.zstride * L.waves;
+    }
+  }
+  HIPC(ctx->r2d_z.ensure(std::max<size_t>(zoff, 256)), "hipMalloc(reg2aln matrices)");  // idle: see the wait above
+  if (at) HIPC(launch_reg2aln_scatter(n_cap, keys, off, d_tab + kR2TabWords, ctx->r2d_lists.as<int32_t>(), st),
+               "reg2aln scatter launch");
+  if (timing) HIPC(hipEventRecord(ctx->r2d_ev[0], st), "event");
+  if (!launches.empty()) {
+    int used = 0;
+    TRY(side_fork(ctx, st, launches.size(), &used));
+    zoff = 0;
+    for (size_t li = 0; li < launches.size(); ++li) {
+      Launch& L = launches[li];
+      if (L.cls == 2) {
+        L.a.zglob = ctx->r2d_z.as<uint8_t>() + zoff;
+        zoff += (size_t)L.a.zstride * L.waves;
+      }
+      const int blocks = std::max(1, std::min((L.n + L.wpb - 1) / L.wpb, L.waves / L.wpb));
+      HIPC(launch_reg2aln(kR2CD[L.bk], o, ctx->ref, L.a, blocks, L.wpb, ctx->a2_st[li % used]), "reg2aln launch");
+    }
+    TRY(side_join(ctx, st, used));
+  }
+  if (timing) {
+    HIPC(hipEventRecord(ctx->r2d_ev[1], st), "event");
+    ctx->r2d_timed = true;
+    ctx->r2d_jobs = h[kR2TabJobs];
+    ctx->r2d_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+  }
+  // as bwagpu_mate_rescue_device: zeros (nothing moved, no kernel timed: the bins are still running)
+  // but the count.  Refused jobs are counted by their status.
+  bwagpu_stats_t& last = ctx->slot[0].last = bwagpu_stats_t{};
+  last.ext_calls = h[kR2TabJobs];
+  return BWAGPU_OK;
+}
+
+int bwagpu_debug_reg2aln_times(bwagpu_ctx_t* ctx, double* out) {
+  if (!ctx || !out) return BWAGPU_E_INVAL;
+  out[0] = out[1] = out[2] = out[3] = 0;
+  ctx->r2d_timing = true;  // from the first use on, the device-form calls of this context are timed
+  if (!ctx->r2d_timed) return BWAGPU_OK;
+  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
+  HIPC(hipEventSynchronize(ctx->r2d_ev[1]), "event sync");
+  float ms = 0;
+  HIPC(hipEventElapsedTime(&ms, ctx->r2d_ev[0], ctx->r2d_ev[1]), "event time");
+  out[0] = ctx->r2d_wait_ms, out[1] = ms, out[2] = ctx->r2d_call_ms, out[3] = ctx->r2d_jobs;
+  return BWAGPU_OK;
+}
+
+int bwagpu_reg2aln_jobs_device(bwagpu_ctx_t* ctx, int32_t n_reads, const int64_t* dev_reg_off,
+                               const bwagpu_alnreg_t* dev_regs, const int32_t* dev_n, const int32_t* dev_select,
+                               const int64_t* dev_seq_off, int32_t job_cap, bwagpu_reg2aln_task_t* dev_tasks,
+                               int32_t* dev_job_of, int32_t* dev_n_jobs, void* stream) {
+  if (!ctx || n_reads < 0 || job_cap < 0 || !dev_n_jobs || (job_cap && !dev_tasks) ||
+      (n_reads && (!dev_reg_off || !dev_regs || !dev_n || !dev_select || !dev_seq_off || !dev_job_of)))
+    return BWAGPU_E_INVAL;
+  hipStream_t st = nullptr;
+  TRY(entry_stream(ctx, stream, &st));
+  if (n_reads == 0) {
+    HIPC(hipMemsetAsync(dev_n_jobs, 0, 2 * sizeof(int32_t), st), "memset");
+    return BWAGPU_OK;
+  }
+  const size_t sum_bytes = sizeof(int32_t) * (((size_t)n_reads + 255) / 256);
+  if (!ctx->r2d_done) HIPC(hipEventCreateWithFlags(&ctx->r2d_done, hipEventDisableTiming), "event");
+  if (ctx->r2d_pending && sum_bytes > ctx->r2d_sums.cap) HIPC(hipEventSynchronize(ctx->r2d_done), "event sync");
+  if (ctx->r2d_pending) HIPC(hipStreamWaitEvent(st, ctx->r2d_done, 0), "stream wait");
+  HIPC(ctx->r2d_sums.ensure(sum_bytes), "hipMalloc");
+  const hipError_t e = launch_reg2aln_jobs(n_reads, dev_reg_off, dev_regs, dev_n, dev_select, dev_seq_off, job_cap,
+                                           dev_tasks, dev_job_of, dev_n_jobs, ctx->r2d_sums.as<int32_t>(), st);
+  if (hipEventRecord(ctx->r2d_done, st) == hipSuccess) ctx->r2d_pending = true;
+  HIPC(e, "reg2aln jobs launch");
+  return BWAGPU_OK;
+}
+
 int bwagpu_align2_batch(bwagpu_ctx_t* ctx, int32_t n, const bwagpu_align2_task_t* tasks, const uint8_t* qpool,
                         int64_t qpool_len, const uint8_t* tpool, int64_t tpool_len, bwagpu_kswr_t* results) {
   if (!ctx) return BWAGPU_E_INVAL;

@@ -163,6 +163,18 @@ struct bwagpu_ctx {
   DevBuf a2_tasks, a2_q, a2_t, a2_out, a2_scratch, a2_lists, a2_counts, a2_boff;
   // mem_reg2aln batches (bwagpu_reg2aln_batch)
   DevBuf r2_tasks, r2_q, r2_out, r2_cig, r2_md, r2_lists, r2_z, r2_stats;
+  // bwagpu_reg2aln_device / bwagpu_reg2aln_jobs_device: their own scratch (keys, the one list, the
+  // bin table and the scatter cursors, the HBM matrix slices, the job builder's block sums) and the
+  // table's pinned copy.  r2d_done is recorded at the end of each of those calls and the next one's
+  // stream waits for it before it touches the scratch.  Only once bwagpu_debug_reg2aln_times has
+  // been used (r2d_timing): r2d_ev around the bin launches of the last call, the host's wait at the
+  // read-back and its whole call.
+  DevBuf r2d_keys, r2d_lists, r2d_tab, r2d_z, r2d_sums;
+  HostBuf r2d_htab;
+  hipEvent_t r2d_done = nullptr, r2d_ev[2] = {};
+  bool r2d_pending = false, r2d_timing = false, r2d_timed = false;
+  double r2d_wait_ms = 0, r2d_call_ms = 0;
+  int32_t r2d_jobs = 0;
   // bins run concurrently on these (fork/join with events from the caller's stream)
   static constexpr int kA2Streams = 4;
   hipStream_t a2_st[kA2Streams] = {};

@@ -130,4 +130,104 @@ BWAGPU_HD inline int r2_bucket_of(int qlen) {
 constexpr int kR2ZSmall = 8 * 1024, kR2ZLarge = 24 * 1024;
 constexpr int kR2MaxRef = 8192;  // reference window bytes per job (LDS)
 
+// bwagpu_reg2aln_device: one job's place among the kernel's bins, by the
+// arithmetic of bwagpu_reg2aln_batch's validation loop (capi_tasks.hip).  On
+// every job this accepts, lq / rl / zb / bucket / cls are what that loop
+// computes; a job that loop refuses with an error code is R2_REFUSED here.
+// Two bounds are this function's own: truesc within [-2^24, 2^24] and w within
+// [0, 2^24] (no real score reaches them: a <= 127, reads <= 1023 bp).  With
+// them, lq <= 1023, rl <= 8192 and the context's option ranges (make_opt) no
+// 32-bit expression of the band inference wraps, here or in reg2aln_kernel's
+// infer_bw_dev: the kernel trusts its bin's LDS capacities, so a job whose
+// real band is wider than the one that sized zb would write past its wave's LDS.
+enum { R2_ACCEPTED = 0, R2_REFUSED = 1 };
+constexpr int kR2Bins = kR2Buckets * 3;  // bin = bucket * 3 + cls
+constexpr int kR2CostClasses = 8;        // inside a bin, 0 = the largest matrices
+constexpr int kR2ScoreBound = 1 << 24;
+constexpr int kR2LdsPerBlock = 160 * 1024;
+struct R2Class {
+  int verdict;  // R2_*
+  int lq, rl;   // 0 for a job that gets no DP (unmapped, no CIGAR)
+  int64_t zb;   // bytes of the widest try's direction matrix
+  int bucket, cls;
+};
+
+// per-wave LDS bytes of a bin whose longest query is qmax, longest window rmax
+BWAGPU_HD inline int r2_lds_per_wave(int qmax, int rmax, int cls, int* qcap, int* rcap, int* ocap) {
+  *qcap = (qmax + 16) & ~15;
+  *rcap = (rmax + 16) & ~15;
+  *ocap = *qcap + *rcap + 4;
+  int lpw = *qcap + *rcap + 4 * *ocap;
+  if (cls < 2) lpw += cls == 0 ? kR2ZSmall : kR2ZLarge;
+  return (lpw + 15) & ~15;
+}
+
+BWAGPU_HD inline int r2_infer_bw(int lq, int rl, int a, int truesc, int q_, int r_) {  // infer_bw, bwamem.c:801-808
+  if (lq == rl && lq * a - truesc < (q_ + r_ - a) * 2) return 0;
+  const int w = (int)((double)((lq < rl ? lq : rl) * a - truesc - q_) / r_ + 2.);
+  const int d = lq > rl ? lq - rl : rl - lq;
+  return w > d ? w : d;
+}
+
+BWAGPU_HD inline R2Class r2_classify(const DevOpt& o, int64_t l_pac, int64_t qpool_len,
+                                     const bwagpu_reg2aln_task_t& t) {
+  R2Class c{R2_REFUSED, 0, 0, 0, 0, 0};
+  if (t.l_seq < 0 || t.qoff < 0 || t.qoff > qpool_len - t.l_seq) return c;  // read outside the pool
+  if (t.truesc < -kR2ScoreBound || t.truesc > kR2ScoreBound || t.w < 0 || t.w > kR2ScoreBound) return c;
+  const int64_t two = l_pac << 1;
+  if (t.rb >= 0 && t.re >= 0) {
+    const int64_t beg = t.rb, end = t.re > two ? two : t.re;
+    const bool ok = t.qe > t.qb && t.rb < t.re && !(t.rb < l_pac && t.re > l_pac) &&
+                    (beg >= l_pac || end <= l_pac) && end - beg == t.re - t.rb;
+    if (ok) {
+      if (t.qb < 0 || t.qe > t.l_seq) return c;                     // qb/qe outside the read
+      if ((int64_t)t.qe - t.qb > BWAGPU_MAX_READ_LEN) return c;
+      if (t.re - t.rb > kR2MaxRef) return c;
+      const int lq = t.qe - t.qb, rl = (int)(t.re - t.rb);
+      // the widest band any try can use: the first try's w2 (bwamem.c:1123-1126)
+      // doubled at most twice (1132), capped at opt->w << 2, then bwa.c:152-159
+      const int wmax = o.w << 2;
+      int w2 = r2_infer_bw(lq, rl, o.a, t.truesc, o.o_del, o.e_del);
+      const int w2i = r2_infer_bw(lq, rl, o.a, t.truesc, o.o_ins, o.e_ins);
+      if (w2i > w2) w2 = w2i;
+      if (w2 > o.w) w2 = w2 < t.w ? w2 : t.w;
+      if (w2 > wmax) w2 = wmax;
+      const int64_t w24 = (int64_t)w2 * 4;
+      const int w2max = (int)(w24 < wmax ? w24 : wmax);
+      const int half = (lq + 1) >> 1;
+      const int mi = (int)((double)(half * o.mat[0] - o.o_ins) / o.e_ins + 1.);
+      const int mdl = (int)((double)(half * o.mat[0] - o.o_del) / o.e_del + 1.);
+      int mg = mi > mdl ? mi : mdl;
+      if (mg < 1) mg = 1;
+      const int dl = rl > lq ? rl - lq : lq - rl;
+      int wb = (mg + dl + 1) >> 1;
+      if (wb > w2max) wb = w2max;
+      if (wb < dl + 3) wb = dl + 3;
+      c.lq = lq, c.rl = rl;
+      c.zb = (int64_t)(lq < 2 * wb + 1 ? lq : 2 * wb + 1) * rl;
+      c.cls = c.zb <= kR2ZSmall ? 0 : (c.zb <= kR2ZLarge ? 1 : 2);
+      // a single-job batch of the host form: its bin's LDS must fit a workgroup
+      int qc, rc, oc;
+      if ((c.cls == 1 ? 1 : 4) * r2_lds_per_wave(lq, rl, c.cls, &qc, &rc, &oc) > kR2LdsPerBlock) return c;
+    }
+  }
+  c.bucket = r2_bucket_of(c.lq);
+  c.verdict = R2_ACCEPTED;
+  return c;
+}
+
+// the coarse order inside a bin: 0 holds the largest zb + lq + rl.  Steps of 512
+// in the small LDS class (they part the jobs whose first try is the ungapped
+// shortcut, zb = 7 rl and most regions of a real batch, from the narrowest
+// banded ones at 100, 150 and 250 bp; everything from 3584 up runs first),
+// steps of 4096 in the large one, octaves in the HBM class.  Finer classes were
+// measured and bring nothing.
+BWAGPU_HD inline int r2_cost_class(int cls, int64_t cost) {
+  int64_t s = cls == 0 ? cost >> 9 : (cls == 1 ? (cost - kR2ZSmall) >> 12 : 0);
+  if (cls == 2)
+    for (int64_t v = cost >> 15; v > 0; v >>= 1) ++s;
+  if (s < 0) s = 0;
+  return s >= kR2CostClasses ? 0 : kR2CostClasses - 1 - (int)s;
+}
+
 }  // namespace bwagpu

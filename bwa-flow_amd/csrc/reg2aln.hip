@@ -79,7 +79,8 @@ __global__ void __launch_bounds__(256) reg2aln_kernel(DevOpt o, DevRef ref, R2AA
   const int64_t l_pac = ref.l_pac, two = l_pac << 1;
   const int wmax = o.w << 2;
   int64_t t_cells = 0, t_rows = 0, t_calls = 0;
-  for (int li = wave; li < a.n; li += nwaves) {
+  const int n_jobs = a.dev_n ? min(a.n, uni(*a.dev_n)) : a.n;
+  for (int li = wave; li < n_jobs; li += nwaves) {
     const int k = uni(a.list[li]);
     const bwagpu_reg2aln_task_t* tp = a.tasks + k;
     const int64_t rb = uni64(tp->rb), re = uni64(tp->re), qoff = uni64(tp->qoff);
@@ -344,6 +345,202 @@ __global__ void __launch_bounds__(256) reg2aln_kernel(DevOpt o, DevRef ref, R2AA
     if (t_rows) atomicAdd((unsigned long long*)&a.stats[ST_ROWS], (unsigned long long)t_rows);
     if (t_calls) atomicAdd((unsigned long long*)&a.stats[ST_CALLS], (unsigned long long)t_calls);
   }
+}
+
+// ---------------------------------------------------------------- bwagpu_reg2aln_device
+// A lane per job: r2_classify (pure.h) decides; a refused job gets its record
+// here and no key.  Counts and maxima are gathered per workgroup in LDS and
+// leave it as one atomic per word that is not zero.
+__global__ void __launch_bounds__(256) reg2aln_classify_kernel(DevOpt o, int64_t l_pac, int64_t qpool_len, int n_cap,
+                                                               const int32_t* __restrict__ dev_n_tasks,
+                                                               const bwagpu_reg2aln_task_t* __restrict__ tasks,
+                                                               int32_t* __restrict__ keys,
+                                                               bwagpu_aln_t* __restrict__ out,
+                                                               int32_t* __restrict__ table) {
+  __shared__ int32_t tab[kR2TabWords];
+  for (int x = (int)threadIdx.x; x < kR2TabWords; x += (int)blockDim.x) tab[x] = 0;
+  __syncthreads();
+  int n = n_cap;
+  if (dev_n_tasks) n = max(0, min(n_cap, *dev_n_tasks));
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // n_cap may be near INT_MAX
+  if (k < n_cap) {
+    int key = -1;
+    if (k < n) {
+      const R2Class c = r2_classify(o, l_pac, qpool_len, tasks[k]);
+      if (c.verdict == R2_ACCEPTED) {
+        const int bin = c.bucket * 3 + c.cls;
+        key = bin * kR2CostClasses + r2_cost_class(c.cls, c.zb + c.lq + c.rl);
+        atomicAdd(&tab[4 * bin], 1);
+        atomicMax(&tab[4 * bin + 1], c.lq);
+        atomicMax(&tab[4 * bin + 2], c.rl);
+        atomicMax(&tab[4 * bin + 3], (int32_t)c.zb);  // <= 1023 * 8192
+        atomicAdd(&tab[kR2TabClass + key], 1);
+      } else {
+        bwagpu_aln_t res{};
+        res.rid = -1;
+        res.pos = -1;
+        res.status = BWAGPU_ALN_REFUSED;
+        out[k] = res;
+        atomicAdd(&tab[kR2TabRefused], 1);
+      }
+    }
+    keys[k] = key;
+  }
+  __syncthreads();
+  for (int x = (int)threadIdx.x; x < kR2TabJobs; x += (int)blockDim.x) {
+    const int32_t v = tab[x];
+    if (!v) continue;
+    if (x < kR2TabClass && (x & 3)) atomicMax(&table[x], v);
+    else atomicAdd(&table[x], v);
+  }
+  if (threadIdx.x == 0) {
+    if (tab[kR2TabRefused]) atomicAdd(&table[kR2TabRefused], tab[kR2TabRefused]);
+    if (blockIdx.x == 0) table[kR2TabJobs] = n;
+  }
+}
+
+// Job ids into the one list, every (bin, cost class) from its offset on: one
+// atomic per distinct key per wave.  The order inside a key is free.
+__global__ void __launch_bounds__(256) reg2aln_scatter_kernel(int n_cap, const int32_t* __restrict__ keys, R2Offsets off,
+                                                              int32_t* __restrict__ cursors,
+                                                              int32_t* __restrict__ list) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = (int)(threadIdx.x & 63);
+  const int key = k < n_cap ? keys[k] : -1;
+  const bool live = key >= 0 && key < kR2Bins * kR2CostClasses;
+  unsigned long long todo = __builtin_amdgcn_ballot_w64(live);
+  while (todo) {
+    const int leader = __builtin_ctzll(todo);
+    const int b = __builtin_amdgcn_readlane(key, leader);
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(live && key == b);
+    int pos0 = 0;
+    if (lane == leader) pos0 = atomicAdd(&cursors[b], __builtin_popcountll(m));
+    pos0 = __builtin_amdgcn_readlane(pos0, leader);
+    if (live && key == b) list[off.at[b] + pos0 + __builtin_popcountll(m & ((1ull << lane) - 1))] = (int32_t)k;
+    todo &= ~m;
+  }
+}
+
+hipError_t launch_reg2aln_classify(const DevOpt& o, int64_t l_pac, int64_t qpool_len, int n_cap,
+                                   const int32_t* dev_n_tasks, const bwagpu_reg2aln_task_t* tasks, int32_t* keys,
+                                   bwagpu_aln_t* out, int32_t* table, hipStream_t st) {
+  hipLaunchKernelGGL(reg2aln_classify_kernel, dim3((unsigned)(((int64_t)n_cap + 255) / 256)), dim3(256), 0, st, o, l_pac, qpool_len, n_cap,
+                     dev_n_tasks, tasks, keys, out, table);
+  return hipGetLastError();
+}
+
+hipError_t launch_reg2aln_scatter(int n_cap, const int32_t* keys, const R2Offsets& off, int32_t* cursors,
+                                  int32_t* list, hipStream_t st) {
+  hipLaunchKernelGGL(reg2aln_scatter_kernel, dim3((unsigned)(((int64_t)n_cap + 255) / 256)), dim3(256), 0, st, n_cap, keys, off, cursors,
+                     list);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- bwagpu_reg2aln_jobs_device
+namespace {
+
+__device__ __forceinline__ int r2j_count(int r, int n_reads, const int64_t* reg_off, const int32_t* n,
+                                         const int32_t* select) {
+  if (r >= n_reads) return 0;
+  const int64_t base = reg_off[r];
+  int c = 0;
+  for (int k = 0; k < n[r]; ++k) c += select[base + k] >= 0;
+  return c;
+}
+
+// exclusive prefix of v over the workgroup's 256 threads; *total = the workgroup's sum
+__device__ __forceinline__ int block_excl_scan(int v, int* total) {
+  __shared__ int wsum[4];
+  const int lane = (int)(threadIdx.x & 63), w = (int)(threadIdx.x >> 6);
+  int incl = v;
+  for (int o = 1; o < 64; o <<= 1) {
+    const int y = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += y;
+  }
+  __syncthreads();  // wsum of an earlier call has been read
+  if (lane == 63) wsum[w] = incl;
+  __syncthreads();
+  int before = 0, all = 0;
+  for (int x = 0; x < 4; ++x) {
+    before += x < w ? wsum[x] : 0;
+    all += wsum[x];
+  }
+  *total = all;
+  return before + incl - v;
+}
+
+}  // namespace
+
+__global__ void __launch_bounds__(256) reg2aln_jobs_count_kernel(int n_reads, const int64_t* __restrict__ reg_off,
+                                                                 const int32_t* __restrict__ n,
+                                                                 const int32_t* __restrict__ select,
+                                                                 int32_t* __restrict__ block_sums) {
+  const int r = (int)min((int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)n_reads);  // n_reads: no read
+  int total = 0;
+  (void)block_excl_scan(r2j_count(r, n_reads, reg_off, n, select), &total);
+  if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
+}
+
+// one workgroup: block_sums -> their exclusive prefix, in place; the two counts
+__global__ void __launch_bounds__(256) reg2aln_jobs_scan_kernel(int n_blocks, int job_cap,
+                                                                int32_t* __restrict__ block_sums,
+                                                                int32_t* __restrict__ n_jobs) {
+  int carry = 0;
+  for (int x0 = 0; x0 < n_blocks; x0 += 256) {
+    const int x = x0 + (int)threadIdx.x;
+    const int v = x < n_blocks ? block_sums[x] : 0;
+    int total = 0;
+    const int ex = block_excl_scan(v, &total);
+    if (x < n_blocks) block_sums[x] = carry + ex;
+    carry += total;
+  }
+  if (threadIdx.x == 0) {
+    n_jobs[0] = min(carry, job_cap);
+    n_jobs[1] = carry;
+  }
+}
+
+__global__ void __launch_bounds__(256) reg2aln_jobs_write_kernel(int n_reads, const int64_t* __restrict__ reg_off,
+                                                                 const bwagpu_alnreg_t* __restrict__ regs,
+                                                                 const int32_t* __restrict__ n,
+                                                                 const int32_t* __restrict__ select,
+                                                                 const int64_t* __restrict__ seq_off, int job_cap,
+                                                                 bwagpu_reg2aln_task_t* __restrict__ tasks,
+                                                                 int32_t* __restrict__ job_of,
+                                                                 const int32_t* __restrict__ block_sums) {
+  const int r = (int)min((int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)n_reads);  // n_reads: no read
+  int total = 0;
+  int j = block_sums[blockIdx.x] + block_excl_scan(r2j_count(r, n_reads, reg_off, n, select), &total);
+  if (r >= n_reads) return;
+  const int64_t base = reg_off[r], qoff = seq_off[r];
+  const int l_seq = (int)(seq_off[r + 1] - qoff);
+  for (int k = 0; k < n[r]; ++k) {
+    if (select[base + k] < 0) {
+      job_of[base + k] = -1;
+      continue;
+    }
+    if (j < job_cap) {
+      const bwagpu_alnreg_t& g = regs[base + k];
+      bwagpu_reg2aln_task_t t{};
+      t.rb = g.rb, t.re = g.re, t.qoff = qoff, t.l_seq = l_seq, t.qb = g.qb, t.qe = g.qe, t.truesc = g.truesc,
+      t.w = g.w;
+      tasks[j] = t;
+    }
+    job_of[base + k] = j < job_cap ? j : -1;
+    ++j;
+  }
+}
+
+hipError_t launch_reg2aln_jobs(int n_reads, const int64_t* reg_off, const bwagpu_alnreg_t* regs, const int32_t* n,
+                               const int32_t* select, const int64_t* seq_off, int job_cap,
+                               bwagpu_reg2aln_task_t* tasks, int32_t* job_of, int32_t* n_jobs, int32_t* block_sums,
+                               hipStream_t st) {
+  const int nb = (int)(((int64_t)n_reads + 255) / 256);
+  hipLaunchKernelGGL(reg2aln_jobs_count_kernel, dim3(nb), dim3(256), 0, st, n_reads, reg_off, n, select, block_sums);
+  hipLaunchKernelGGL(reg2aln_jobs_scan_kernel, dim3(1), dim3(256), 0, st, nb, job_cap, block_sums, n_jobs);
+  hipLaunchKernelGGL(reg2aln_jobs_write_kernel, dim3(nb), dim3(256), 0, st, n_reads, reg_off, regs, n, select, seq_off,
+                     job_cap, tasks, job_of, block_sums);
+  return hipGetLastError();
 }
 
 int r2_resident_waves(int cd, size_t lds_per_block, int wpb) {

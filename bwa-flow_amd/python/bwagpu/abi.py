@@ -45,7 +45,7 @@ REG2ALN_TASK_DTYPE = np.dtype([("rb", "<i8"), ("re", "<i8"), ("qoff", "<i8"), ("
                                ("qe", "<i4"), ("truesc", "<i4"), ("w", "<i4"), ("pad", "<i4")])
 ALN_DTYPE = np.dtype([("pos", "<i8"), ("rid", "<i4"), ("is_rev", "<i4"), ("n_cigar", "<i4"), ("NM", "<i4"),
                       ("md_len", "<i4"), ("score", "<i4"), ("w", "<i4"), ("status", "<i4")])
-ALN_OK, ALN_NO_CIGAR, ALN_OVERFLOW, ALN_UNMAPPED = 0, 1, 2, 3
+ALN_OK, ALN_NO_CIGAR, ALN_OVERFLOW, ALN_UNMAPPED, ALN_REFUSED = 0, 1, 2, 3, 4
 assert REG2ALN_TASK_DTYPE.itemsize == 48 and ALN_DTYPE.itemsize == 40
 assert SEED_DTYPE.itemsize == 24 and ALNREG_DTYPE.itemsize == 88
 assert ALIGN2_TASK_DTYPE.itemsize == 32 and KSWR_DTYPE.itemsize == 28
@@ -196,6 +196,10 @@ PROTOS = {
     "bwagpu_align2_batch": (C.c_int, [_VP, C.c_int32, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP]),
     "bwagpu_align2_device": (C.c_int, [_VP, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "bwagpu_reg2aln_batch": (C.c_int, [_VP, C.c_int32, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, _VP, _VP, _VP]),
+    "bwagpu_reg2aln_device": (C.c_int, [_VP, C.c_int32, _VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, _VP, _VP,
+                                        _VP, _VP]),
+    "bwagpu_reg2aln_jobs_device": (C.c_int, [_VP, C.c_int32, _VP, _VP, _VP, _VP, _VP, C.c_int32, _VP, _VP, _VP, _VP]),
+    "bwagpu_debug_reg2aln_times": (C.c_int, [_VP, _VP]),
     "bwagpu_last_stats": (C.c_int, [_VP, C.c_int, C.POINTER(Stats)]),
     "bwagpu_debug_set_trace": (C.c_int, [_VP, _VP]),
     "bwagpu_prof_start": (C.c_int, [_VP, C.c_int]),

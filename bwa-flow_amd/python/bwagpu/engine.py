@@ -253,6 +253,38 @@ class Engine:
                                                   _ptr(out), _ptr(cig), _ptr(md)), "reg2aln_batch")
         return out[:n], cig[:n], md[:n]
 
+    def reg2aln_device(self, n_cap: int, dev_tasks: int, dev_qpool: int, qpool_len: int, dev_out: int,
+                       dev_cigar: int, dev_md: int, max_ops: int = 64, max_md: int = 512,
+                       dev_n_tasks: int | None = None, stream: int | None = None):
+        """the same on device buffers (pointers as ints, e.g. torch data_ptr()), on stream: records at
+        dev_out, job k's CIGAR at dev_cigar[k * max_ops], its MD at dev_md[k * max_md]; the job count is
+        n_cap, or min(n_cap, *dev_n_tasks).  A job the kernel cannot take gets abi.ALN_REFUSED.  Waits for
+        the stream once (the bin table); the bin kernels are left running and stream is ordered after them"""
+        self._check(self.lib.bwagpu_reg2aln_device(
+            self.ctx, int(n_cap), C.c_void_p(dev_n_tasks) if dev_n_tasks else None, C.c_void_p(dev_tasks),
+            C.c_void_p(dev_qpool) if dev_qpool else None, int(qpool_len), int(max_ops), int(max_md),
+            C.c_void_p(dev_out), C.c_void_p(dev_cigar), C.c_void_p(dev_md),
+            C.c_void_p(stream) if stream else None), "reg2aln_device")
+
+    def reg2aln_jobs_device(self, n_reads: int, dev_reg_off: int, dev_regs: int, dev_n: int, dev_select: int,
+                            dev_seq_off: int, job_cap: int, dev_tasks: int, dev_job_of: int, dev_n_jobs: int,
+                            stream: int | None = None):
+        """the CIGAR jobs of the regions with dev_select >= 0 (pair_select_device's out_mapq fits), in
+        (read, k) order, asynchronous on stream: dev_tasks[job_cap], dev_job_of parallel to the regions,
+        dev_n_jobs = (written, needed); dev_n_jobs feeds reg2aln_device's dev_n_tasks"""
+        self._check(self.lib.bwagpu_reg2aln_jobs_device(
+            self.ctx, int(n_reads), C.c_void_p(dev_reg_off), C.c_void_p(dev_regs), C.c_void_p(dev_n),
+            C.c_void_p(dev_select), C.c_void_p(dev_seq_off), int(job_cap),
+            C.c_void_p(dev_tasks) if dev_tasks else None, C.c_void_p(dev_job_of), C.c_void_p(dev_n_jobs),
+            C.c_void_p(stream) if stream else None), "reg2aln_jobs_device")
+
+    def debug_reg2aln_times(self) -> dict:
+        """the last reg2aln_device call (waits for it): the host's wait at the read-back, the bin kernels'
+        span by HIP events, the host time of the call.  The first use only switches the timing on"""
+        out = np.zeros(4, np.float64)
+        self._check(self.lib.bwagpu_debug_reg2aln_times(self.ctx, _ptr(out)), "debug_reg2aln_times")
+        return dict(wait_ms=float(out[0]), bins_ms=float(out[1]), call_ms=float(out[2]), jobs=int(out[3]))
+
     def set_bwt(self, hdr, words, sa=None, sa_intv: int = 32):
         """make the FM-index resident (hdr = primary, L2[0..4], seq_len as bwa's bwt_t;
         sa = the sampled suffix array, for bwt_sa)"""

@@ -236,6 +236,8 @@ typedef struct {
                                  reference's mem_reg2aln would dereference NULL here */
 #define BWAGPU_ALN_OVERFLOW 2 /* more than max_ops CIGAR ops or max_md MD bytes */
 #define BWAGPU_ALN_UNMAPPED 3 /* rb < 0 || re < 0: rid = -1, pos = -1 (bwamem.c:1112-1115) */
+#define BWAGPU_ALN_REFUSED 4  /* bwagpu_reg2aln_device only: the job is outside what the kernel
+                                 takes; rid = -1, pos = -1, n_cigar = 0, md_len = 0 */
 
 /* The alignment fields mem_reg2aln fills in mem_aln_t (bwa/bwamem.h:81-92)
    besides mapq/flag/sub/alt_sc (which need the other regions): CIGAR with
@@ -427,6 +429,52 @@ int bwagpu_align2_device(bwagpu_ctx_t *ctx, int32_t n_tasks, const bwagpu_align2
 int bwagpu_reg2aln_batch(bwagpu_ctx_t *ctx, int32_t n_tasks, const bwagpu_reg2aln_task_t *tasks,
                          const uint8_t *qpool, int64_t qpool_len, int32_t max_ops, int32_t max_md,
                          bwagpu_aln_t *out, uint32_t *cigar, char *md);
+/* The same records, CIGAR slots (k * max_ops) and MD slots (k * max_md) with
+   jobs, pool and outputs in device memory, on stream (hipStream_t, NULL = the
+   context's slot-0 stream).  The job count is n_cap, or min(n_cap,
+   *dev_n_tasks) when dev_n_tasks is not NULL (a producer's count that stayed
+   on the device: bwagpu_reg2aln_jobs_device's dev_n_jobs fits).  Records and
+   slots at or beyond the job count are not touched.
+   Before any launch: NULLs with n_cap > 0, n_cap < 0, max_ops < 1, max_md < 1
+   and qpool_len < 0 return BWAGPU_E_INVAL.  Nothing else is validated on the
+   host.  On the device a job is judged alone and never fails the call: it gets
+   status BWAGPU_ALN_REFUSED (rid = -1, pos = -1, n_cigar = 0, md_len = 0, its
+   CIGAR and MD slots untouched) when bwagpu_reg2aln_batch would have refused
+   the batch for it (read outside the pool; on an otherwise valid window qb /
+   qe outside the read, qe - qb > BWAGPU_MAX_READ_LEN, re - rb > 8192, more
+   LDS than a workgroup has), or when its truesc is outside [-2^24, 2^24] or
+   its w outside [0, 2^24] (no real score reaches these; inside them no 32-bit
+   expression of the band inference wraps).  BWAGPU_ALN_UNMAPPED and
+   BWAGPU_ALN_NO_CIGAR are decided as in the batch form.
+   The call waits for the stream once: the device bins the jobs, and the bin
+   table (under 1 KB) comes to the host, which sizes the launches from its
+   counts and maxima.  The bin kernels are then left running: they are
+   enqueued on the context's side streams and stream is ordered after them.
+   Calls on different streams are ordered among themselves by an event (they
+   share the context's scratch).  bwagpu_last_stats(ctx, 0) after the call is
+   all zeros but ext_calls = the job count, as bwagpu_mate_rescue_device
+   leaves it: h2d_bytes = d2h_bytes = 0, and kernel_ms = 0 because no _device
+   entry takes a kernel time (the kernels are still running when it returns;
+   bwagpu_mark_primary_device does not write the stats at all).  Refused jobs
+   are counted from their status.  n_cap may be any int32 >= 0. */
+int bwagpu_reg2aln_device(bwagpu_ctx_t *ctx, int32_t n_cap, const int32_t *dev_n_tasks,
+                          const bwagpu_reg2aln_task_t *dev_tasks, const uint8_t *dev_qpool, int64_t qpool_len,
+                          int32_t max_ops, int32_t max_md, bwagpu_aln_t *dev_out, uint32_t *dev_cigar,
+                          char *dev_md, void *stream);
+/* The jobs of a selection over regions in device memory, asynchronous on
+   stream (no host wait).  Read r's region k is dev_regs[dev_reg_off[r] + k],
+   k < dev_n[r]; it gets a job iff dev_select[dev_reg_off[r] + k] >= 0
+   (bwagpu_pair_select_device's out_mapq fits).  Jobs come in (read, k) order:
+   rb, re, qb, qe, truesc, w from the region, qoff = dev_seq_off[r], l_seq =
+   dev_seq_off[r + 1] - dev_seq_off[r].  dev_job_of is parallel to the regions
+   (only the entries of the reads' regions are written): the job's index, or
+   -1 for a region without a job or whose job is past job_cap.  dev_n_jobs[0] =
+   jobs written (<= job_cap), dev_n_jobs[1] = jobs needed.  Negative n_reads or
+   job_cap and NULLs return BWAGPU_E_INVAL before any launch. */
+int bwagpu_reg2aln_jobs_device(bwagpu_ctx_t *ctx, int32_t n_reads, const int64_t *dev_reg_off,
+                               const bwagpu_alnreg_t *dev_regs, const int32_t *dev_n, const int32_t *dev_select,
+                               const int64_t *dev_seq_off, int32_t job_cap, bwagpu_reg2aln_task_t *dev_tasks,
+                               int32_t *dev_job_of, int32_t *dev_n_jobs, void *stream);
 
 /* The FPGA wire format.  i_buf/i_words: one or more
    read records exactly as packReadData writes them (FPGAPipeline.cpp:252-336),

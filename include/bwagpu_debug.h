@@ -149,6 +149,14 @@ int bwagpu_debug_rescue_drop(bwagpu_ctx_t *ctx, int32_t k);
    the scans, the wait for the task count and the emitting pass), out[1] the
    batched ksw_align2, out[2] the replay, out[3] the rounds run */
 int bwagpu_debug_rescue_times(bwagpu_ctx_t *ctx, double *out);
+/* timing (tools_dev/reg2aln_device_bench.py).  The first use switches the timing
+   of this context's later bwagpu_reg2aln_device calls on (two events and two
+   clock readings per call; off by default) and returns zeros.  Afterwards: the
+   last such call (waits for it): out[0] ms the host waited at the bin table's
+   read-back, out[1] ms by HIP events on its stream from before the first bin
+   launch to after the last one's end, out[2] ms the host spent in the call,
+   out[3] the call's job count */
+int bwagpu_debug_reg2aln_times(bwagpu_ctx_t *ctx, double *out);
 int bwagpu_prof_intervals(bwagpu_ctx_t *ctx, double *start_ms, double *end_ms, int32_t max, int32_t *n);
 
 #ifdef __cplusplus
