@@ -38,9 +38,10 @@ struct A2Args {
 // one bin's kernel; n_hint = its task count when the host knows it (grid
 // sized to it), 0 = unknown (grid = resident capacity, tasks read from *count)
 hipError_t launch_align2(int bin, const A2Args& a, const A2Prof& P, int n_hint, hipStream_t st);
-// device-side binning (bwagpu_align2_device): lists is [kA2Bins][n]
-hipError_t launch_align2_bins(const bwagpu_align2_task_t* tasks, int n, int32_t* lists, int32_t* counts,
-                              int64_t* boff, unsigned long long* cursor, bwagpu_kswr_t* out, int64_t* stats,
-                              hipStream_t st);
+// device-side binning (bwagpu_align2_device): lists is [kA2Bins][n]; tasks the
+// options or their length rule out get seven -1 and an ST_ERR bit instead of a bin
+hipError_t launch_align2_bins(const DevOpt& o, const bwagpu_align2_task_t* tasks, int n, int32_t* lists,
+                              int32_t* counts, int64_t* boff, unsigned long long* cursor, bwagpu_kswr_t* out,
+                              int64_t* stats, hipStream_t st);
 
 }  // namespace bwagpu

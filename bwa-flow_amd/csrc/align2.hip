@@ -300,11 +300,17 @@ __global__ __launch_bounds__(256) void align2_kernel(A2Args a, A2Prof P) {
 
 // Device-side binning for bwagpu_align2_device: bucket of the first pass's
 // segment count and width, scratch region from a cursor; wave-aggregated
-// atomics (one per distinct bin per wave).
+// atomics (one per distinct bin per wave).  The per-task refusals of
+// align2_plan (task_host.h) are made here, since only the device sees the
+// tasks: a task over the length limit (ERR_LEN), a byte task under options the
+// 8-bit pass cannot hold (byte_ok == 0: align2_byte_ok, pure.h) and a word task
+// whose 16-bit scores could saturate (both ERR_A2_RANGE) get a record of seven
+// -1 and no bin.
 __global__ __launch_bounds__(256) void align2_bin_kernel(const bwagpu_align2_task_t* __restrict__ tasks, int n,
-                                                         int32_t* __restrict__ lists, int32_t* __restrict__ counts,
-                                                         int64_t* __restrict__ boff, unsigned long long* cursor,
-                                                         bwagpu_kswr_t* __restrict__ out, int64_t* stats) {
+                                                         int byte_ok, int max_mat, int32_t* __restrict__ lists,
+                                                         int32_t* __restrict__ counts, int64_t* __restrict__ boff,
+                                                         unsigned long long* cursor, bwagpu_kswr_t* __restrict__ out,
+                                                         int64_t* stats) {
   const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   const int lane = (int)(threadIdx.x & 63);
   bool live = k < n;
@@ -312,12 +318,17 @@ __global__ __launch_bounds__(256) void align2_bin_kernel(const bwagpu_align2_tas
   long long need = 0;
   if (live) {
     const bwagpu_align2_task_t t = tasks[k];
+    const bool u8 = (t.xtra & BWAGPU_KSW_XBYTE) != 0;
     if (t.qlen < 0 || t.qlen > BWAGPU_MAX_READ_LEN || t.tlen < 0) {
       out[k] = bwagpu_kswr_t{-1, -1, -1, -1, -1, -1, -1};
       atomicOr((unsigned long long*)&stats[ST_ERR], (unsigned long long)ERR_LEN);
       live = false;
+    } else if (u8 ? !byte_ok : !align2_word_fits(t.qlen, max_mat)) {
+      out[k] = bwagpu_kswr_t{-1, -1, -1, -1, -1, -1, -1};
+      atomicOr((unsigned long long*)&stats[ST_ERR], (unsigned long long)ERR_A2_RANGE);
+      live = false;
     } else {
-      bin = a2_bin_of(t.qlen, (t.xtra & BWAGPU_KSW_XBYTE) != 0);
+      bin = a2_bin_of(t.qlen, u8);
       need = (long long)t.tlen + 1;
     }
   }
@@ -384,12 +395,12 @@ hipError_t launch_align2(int bin, const A2Args& a, const A2Prof& P, int n_hint, 
                            : launch_bucket<false>(bin, a, P, n_hint, st);
 }
 
-hipError_t launch_align2_bins(const bwagpu_align2_task_t* tasks, int n, int32_t* lists, int32_t* counts,
-                              int64_t* boff, unsigned long long* cursor, bwagpu_kswr_t* out, int64_t* stats,
-                              hipStream_t st) {
+hipError_t launch_align2_bins(const DevOpt& o, const bwagpu_align2_task_t* tasks, int n, int32_t* lists,
+                              int32_t* counts, int64_t* boff, unsigned long long* cursor, bwagpu_kswr_t* out,
+                              int64_t* stats, hipStream_t st) {
   if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(align2_bin_kernel, dim3((n + 255) / 256), dim3(256), 0, st, tasks, n, lists, counts, boff,
-                     cursor, out, stats);
+  hipLaunchKernelGGL(align2_bin_kernel, dim3((n + 255) / 256), dim3(256), 0, st, tasks, n, (int)align2_byte_ok(o),
+                     o.max_mat, lists, counts, boff, cursor, out, stats);
   return hipGetLastError();
 }
 

@@ -302,6 +302,7 @@ extern "C" int bwagpu_mate_rescue_device(bwagpu_ctx_t* ctx, const bwagpu_pairopt
   if (b->n_reads & 1) return fail(ctx, BWAGPU_E_INVAL, "odd read count: reads 2i and 2i+1 are a pair");
   if (!dev_pes) return fail(ctx, BWAGPU_E_INVAL, "NULL pes");
   if (const char* why = align2_opt_unsupported(ctx->opt)) return fail(ctx, BWAGPU_E_UNSUPPORTED, why);
+  if (!align2_byte_ok(ctx->opt)) return fail(ctx, BWAGPU_E_UNSUPPORTED, kA2ByteRescueWhy);
   if (b->n_reads == 0) return BWAGPU_OK;
   if (!b->seq_off || !b->seq || b->seq_bytes < 0 || !dev_reg_off || !dev_regs || !dev_n || !dev_out_off ||
       !dev_out_regs || !dev_out_n || !dev_status || !dev_n_sw)
@@ -335,6 +336,7 @@ extern "C" int bwagpu_mate_rescue(bwagpu_ctx_t* ctx, const bwagpu_pairopt_t* pop
                             &plan, &why))
     return fail(ctx, rc, why);
   if (const char* w = align2_opt_unsupported(ctx->opt)) return fail(ctx, BWAGPU_E_UNSUPPORTED, w);
+  if (!align2_byte_ok(ctx->opt)) return fail(ctx, BWAGPU_E_UNSUPPORTED, kA2ByteRescueWhy);
   if (n_reads == 0) return BWAGPU_OK;
   const size_t nr = (size_t)n_reads, np = nr / 2;
   int32_t hctr[RC_WORDS] = {};  // before hc: a copy into it may be in flight until hc is gone

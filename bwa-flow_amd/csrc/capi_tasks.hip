@@ -478,8 +478,8 @@ int bwagpu_align2_device(bwagpu_ctx_t* ctx, int32_t n, const bwagpu_align2_task_
   unsigned long long* cursor = (unsigned long long*)(d_counts + 2 * kA2Bins);
   int64_t* d_stats = (int64_t*)(cursor + 1);
   HIPC(hipMemsetAsync(d_counts, 0, cbytes, st), "memset");
-  HIPC(launch_align2_bins(dev_tasks, n, ctx->a2_lists.as<int32_t>(), d_counts, ctx->a2_boff.as<int64_t>(), cursor,
-                          dev_results, d_stats, st),
+  HIPC(launch_align2_bins(ctx->opt, dev_tasks, n, ctx->a2_lists.as<int32_t>(), d_counts, ctx->a2_boff.as<int64_t>(),
+                          cursor, dev_results, d_stats, st),
        "align2 bin launch");
   // counts are on the device only: every bin's kernel is launched with a
   // resident-capacity grid; an empty bin's waves exit on their first claim

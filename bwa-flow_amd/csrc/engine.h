@@ -50,7 +50,7 @@ struct DevRef {
 
 // stats words (int64): [0] cells [1] rows [2] ext calls [3] error flags
 enum { ST_CELLS = 0, ST_ROWS = 1, ST_CALLS = 2, ST_ERR = 3, ST_N = 4 };
-enum { ERR_RID = 1, ERR_LEN = 2 };
+enum { ERR_RID = 1, ERR_LEN = 2, ERR_A2_RANGE = 4 };  // (8: ERR_POST, regpost.h)
 
 // limits of the fast kernel: one lane (slot) per seed / chain / region of a read
 constexpr int kFastMaxSeeds = 32;

@@ -106,15 +106,39 @@ BWAGPU_HD inline int a2_bin_of(int qlen, bool u8) {
   return (u8 ? kA2Buckets : 0) + b;
 }
 
-// scoring limits of the align2 kernels (reasons are the E_UNSUPPORTED text)
+// scoring limits of the align2 kernels (reasons are the E_UNSUPPORTED text).
+// The reference holds e_del, e_ins, o_del + e_del and o_ins + e_ins in SIMD
+// lanes of the pass's width and keeps their low bits only: 16 in ksw_i16
+// (_mm_set1_epi16, ksw.c:252-255), 8 in ksw_u8 (_mm_set1_epi8, ksw.c:132-135).
+// The kernels compute with the untruncated values, so a penalty the reference
+// would truncate is refused, not emulated (the closed-form F of align2.hip is
+// proved for o_ins > 0 only, and a truncated o_ins + e_ins can fall to e_ins or
+// below).  The word limit holds for every task, the byte limit for tasks that
+// carry BWAGPU_KSW_XBYTE; these two functions are the only place either is written.
+inline constexpr const char* kA2WordWhy =
+    "ksw_align2 with o_del + e_del or o_ins + e_ins > 65535: the reference keeps 16 bits of them "
+    "(_mm_set1_epi16, ksw.c:252-255)";
+inline constexpr const char* kA2ByteWhy =
+    "ksw_align2 XBYTE task with e_del, e_ins, o_del + e_del or o_ins + e_ins > 255: the reference's 8-bit pass "
+    "keeps 8 bits of them (_mm_set1_epi8, ksw.c:132-135)";
+inline constexpr const char* kA2ByteRescueWhy =
+    "mate rescue with e_del, e_ins, o_del + e_del or o_ins + e_ins > 255: whether a read is short enough for "
+    "ksw_align2's 8-bit pass (l_ms * a < 250) is known only on the device, and that pass keeps 8 bits of them "
+    "(_mm_set1_epi8, ksw.c:132-135)";
 inline const char* align2_opt_unsupported(const DevOpt& o) {
   if (o.o_ins <= 0)
     return "ksw_align2 with o_ins == 0: the reference's lazy-F early exit (ksw.c:180) then depends on "
            "its SIMD lane order; run it on the CPU";
   if (o.max_mat <= 0) return "ksw_align2 needs a positive match score (ksw.c:216 divides by it)";
   if (o.o_ins > 65535 || o.e_ins > 65535 || o.o_del > 65535 || o.e_del > 65535) return "gap penalty > 65535";
+  if (o.oe_del > 65535 || o.oe_ins > 65535) return kA2WordWhy;
   return nullptr;
 }
+BWAGPU_HD inline bool align2_byte_ok(const DevOpt& o) {
+  return o.e_del <= 255 && o.e_ins <= 255 && o.oe_del <= 255 && o.oe_ins <= 255;
+}
+// a word task whose 16-bit scores could saturate (ksw_i16 clamps at 32767)
+BWAGPU_HD inline bool align2_word_fits(int qlen, int max_mat) { return (int64_t)qlen * max_mat <= 32767; }
 
 // mem_reg2aln's CIGAR (reg2aln.hip).  Query-length buckets: one compiled
 // kernel per strided segment count CD (eh[] slots 0..qlen over 64 lanes:

@@ -115,6 +115,7 @@ inline int align2_plan(const DevOpt& o, int32_t n, const bwagpu_align2_task_t* t
     return BWAGPU_E_INVAL;
   if (n == 0) return BWAGPU_OK;
   if (const char* w = align2_opt_unsupported(o)) return *why = w, BWAGPU_E_UNSUPPORTED;
+  const bool byte_ok = align2_byte_ok(o);
   std::vector<int32_t> lists[kA2Bins];
   plan->boff.resize((size_t)n);
   for (int32_t k = 0; k < n; ++k) {
@@ -124,7 +125,8 @@ inline int align2_plan(const DevOpt& o, int32_t n, const bwagpu_align2_task_t* t
       return *why = "task outside its pools", BWAGPU_E_INVAL;
     if (t.qlen > BWAGPU_MAX_READ_LEN) return *why = "qlen > BWAGPU_MAX_READ_LEN", BWAGPU_E_UNSUPPORTED;
     const bool u8 = (t.xtra & BWAGPU_KSW_XBYTE) != 0;
-    if (!u8 && (int64_t)t.qlen * o.max_mat > 32767)
+    if (u8 && !byte_ok) return *why = kA2ByteWhy, BWAGPU_E_UNSUPPORTED;  // word tasks of the batch stay admitted
+    if (!u8 && !align2_word_fits(t.qlen, o.max_mat))
       return *why = "i16 scores could saturate (qlen * max score > 32767)", BWAGPU_E_UNSUPPORTED;
     lists[a2_bin_of(t.qlen, u8)].push_back(k);
     plan->boff[(size_t)k] = plan->scratch;

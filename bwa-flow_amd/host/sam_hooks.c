@@ -20,7 +20,8 @@
  *
  * Requirements: the ksw_align2 calls answered from the cache are mem_matesw's
  * (m = 5, the stage's opt->mat / gap penalties, qry = NULL); any other call
- * (qry != NULL, m != 5) goes to bwa's function.  The cache's bwagpu context
+ * (qry != NULL, m != 5, or gap penalties the reference truncates to its SIMD
+ * lane width and the device therefore refuses) goes to bwa's function.  The cache's bwagpu context
  * must have been created from the same mem_opt_t.
  */
 #define _GNU_SOURCE
@@ -127,7 +128,14 @@ int bwagpu_sam_hooks_errors(void)
 kswr_t ksw_align2(int qlen, uint8_t *query, int tlen, uint8_t *target, int m, const int8_t *mat, int o_del,
                   int e_del, int o_ins, int e_ins, int xtra, kswq_t **qry)
 {
-  if (!g_cache || qry || m != 5) {
+  /* gap penalties past the reference's SIMD lanes (align2_opt_unsupported's word limit and
+     align2_byte_ok, bwa-flow_amd/csrc/pure.h, restated here because this file is C compiled
+     with bwa): bwagpu_align2_batch refuses such a call, so a flush could never answer it.
+     bwa's own function computes it, truncation included. */
+  const int oe_del = o_del + e_del, oe_ins = o_ins + e_ins;
+  const int past_lanes = oe_del > 65535 || oe_ins > 65535 ||
+                         ((xtra & KSW_XBYTE) && (e_del > 255 || e_ins > 255 || oe_del > 255 || oe_ins > 255));
+  if (!g_cache || qry || m != 5 || past_lanes) {
     if (!real_align2) resolve_real();
     return real_align2(qlen, query, tlen, target, m, mat, o_del, e_del, o_ins, e_ins, xtra, qry);
   }

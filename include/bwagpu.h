@@ -414,12 +414,32 @@ int bwagpu_extend_batch(bwagpu_ctx_t *ctx, int32_t n_tasks, const bwagpu_ext_tas
                         const uint8_t *qpool, int64_t qpool_len, const uint8_t *tpool,
                         int64_t tpool_len, bwagpu_ext_result_t *results);
 
+/* ksw_align2 per task.  BWAGPU_E_UNSUPPORTED before anything is enqueued (the
+   caller runs ksw_align2 on the CPU; bwagpu_last_error says which):
+     - o_ins == 0, no positive match score, a gap penalty over 65535;
+     - o_del + e_del or o_ins + e_ins over 65535: the reference keeps 16 bits
+       of them (_mm_set1_epi16, ksw.c:252-255) -- for every batch;
+     - a task with BWAGPU_KSW_XBYTE while e_del, e_ins, o_del + e_del or
+       o_ins + e_ins is over 255: the reference's 8-bit pass keeps 8 bits of
+       them (_mm_set1_epi8, ksw.c:132-135) -- a batch without such a task runs
+       under the same options;
+     - a task without BWAGPU_KSW_XBYTE whose qlen * max(mat) is over 32767 (the
+       16-bit scores could saturate), or a qlen over BWAGPU_MAX_READ_LEN.
+   The first such task in task order decides. */
 int bwagpu_align2_batch(bwagpu_ctx_t *ctx, int32_t n_tasks, const bwagpu_align2_task_t *tasks,
                         const uint8_t *qpool, int64_t qpool_len, const uint8_t *tpool, int64_t tpool_len,
                         bwagpu_kswr_t *results);
 /* the same with tasks/pools/results in device memory; asynchronous on stream
    (hipStream_t, NULL = slot-0 stream).  dev_scratch: 8 x (sum of tlen + n_tasks)
-   bytes of device memory for the row-maxima lists (ksw.c:191-198) */
+   bytes of device memory for the row-maxima lists (ksw.c:191-198).
+   Options are refused as above (BWAGPU_E_UNSUPPORTED, nothing enqueued).  The
+   host cannot see the tasks, so the per-task refusals are made on the device:
+   a task with qlen outside 0..BWAGPU_MAX_READ_LEN or a negative tlen, a
+   BWAGPU_KSW_XBYTE task under options over the 8-bit limit, and a task without
+   it whose qlen * max(mat) is over 32767 are not computed.  Their records come
+   back as seven -1 (score -1 is no value ksw_align2 returns), the other tasks
+   of the batch are computed, and the call still returns BWAGPU_OK: a caller
+   that can pass such tasks checks score < 0. */
 int bwagpu_align2_device(bwagpu_ctx_t *ctx, int32_t n_tasks, const bwagpu_align2_task_t *dev_tasks,
                          const uint8_t *dev_qpool, const uint8_t *dev_tpool, bwagpu_kswr_t *dev_results,
                          void *dev_scratch, void *stream);

@@ -234,7 +234,66 @@ def gen_range():
     print(f"[gen_golden] ksw_range: {len(out) // 6} family sides, {n} tasks")
 
 
+def a2_limit_counts():
+    """how often the ungated int arithmetic (oracle_align2_batch_ungated) differs from the reference around the
+    SIMD width limits, on 300 mate-rescue-shaped tasks a row (DESIGN.md §8f-limits prints this table)"""
+    from bwagpu import synth
+    X = abi.KSW_XBYTE
+    rows = [("defaults", {}, None), ("o_del=254 (oe_del = 255)", dict(o_del=254), None),
+            ("b=127", dict(b=127), None), ("a=b=127", dict(a=127, b=127), None),
+            ("o_del=255 (oe_del = 256 -> 0), byte tasks", dict(o_del=255), "byte"),
+            ("o_ins=255, byte tasks", dict(o_ins=255), "byte"), ("e_del=256, byte tasks", dict(e_del=256), "byte"),
+            ("o_del=300, byte tasks", dict(o_del=300), "byte"), ("o_del=300, XBYTE cleared", dict(o_del=300), "word"),
+            ("o_del=65534 (oe_del = 65535), word tasks", dict(o_del=65534), "word"),
+            ("o_del=65535 (oe_del = 65536 -> 0), word tasks", dict(o_del=65535), "word"),
+            ("o_ins=65535, word tasks", dict(o_ins=65535), "word"),
+            ("e_ins=65535, o_ins=1, word tasks", dict(e_ins=65535, o_ins=1), "word")]
+    out = []
+    for label, kw, width in rows:
+        opt = dict(abi.default_opt(), **kw)
+        opt["mat"] = abi.fill_scmat(opt["a"], opt["b"])
+        tasks, qp, tp = synth.mate_rescue_tasks(np.random.default_rng(300), 300, a=opt["a"], qlens=(50, 100, 150),
+                                                win=(0, 300), xtra_mode="mix")
+        if width == "word":
+            tasks["xtra"] &= ~X
+        if width == "byte":
+            tasks["xtra"] |= X
+        if opt["a"] == 127:  # 16-bit scores must not saturate: that limit has its own family
+            tasks["xtra"] |= X
+        a, _ = oracle.align2("oracle_ungated", opt, tasks, qp, tp)
+        b, _ = oracle.align2("ref", opt, tasks, qp, tp)
+        n = int((a.view(np.int32).reshape(-1, 7) != b.view(np.int32).reshape(-1, 7)).any(axis=1).sum())
+        out.append((label, n))
+        print(f"[gen_golden] align2 limits: {label}: ungated oracle != reference on {n}/300 tasks")
+    return out
+
+
+def gen_align2_range():
+    """the families of tests/align2_cases.py (ksw_align2 at the reference's SIMD width limits, both sides)
+    through the reference's own ksw_align2 -> tests/golden/align2_range.npz, keys
+    "<family>__<side>__<array>": options, tasks, pools, the reference's kswr_t"""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import align2_cases
+    out, n = {}, 0
+    for name, side, f in align2_cases.flat():
+        res, _ = oracle.align2("ref", f.opt, f.tasks, f.qpool, f.tpool)
+        k = f"{name}__{side}__"
+        out[k + "opt_int"] = np.array([f.opt[x] for x in ("a", "b", "o_del", "e_del", "o_ins", "e_ins", "pen_clip5",
+                                                          "pen_clip3", "w", "zdrop")], np.int32)
+        out[k + "opt_mat"] = np.asarray(f.opt["mat"], np.int8)
+        out[k + "tasks"], out[k + "task_res"], out[k + "qpool"], out[k + "tpool"] = f.tasks, res, f.qpool, f.tpool
+        n += len(f.tasks)
+    np.savez_compressed(os.path.join(GOLD, "align2_range.npz"), **out)
+    print(f"[gen_golden] align2_range: {len(out) // 6} family sides, {n} tasks")
+    a2_limit_counts()
+
+
 def main():
+    if "--only-align2-range" in sys.argv:
+        if oracle.ref_lib() is None:
+            sys.exit("build the reference first: make -C oracle")
+        gen_align2_range()
+        return
     if "--only-range" in sys.argv:
         if oracle.ref_lib() is None:
             sys.exit("build the reference first: make -C oracle")
@@ -276,6 +335,7 @@ def main():
         print(f"[gen_golden] {name}: tasks={len(tasks)} q={len(qp)} t={len(tp)}")
     gen_align2(np.random.default_rng(2025))
     gen_range()
+    gen_align2_range()
 
 
 if __name__ == "__main__":

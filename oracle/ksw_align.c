@@ -25,10 +25,33 @@
  *     F from h_fp (the GPU kernel's form); for o_ins == 0 it can (equality
  *     case), which is why this oracle keeps the literal loop.
  *
- * In u8 the M path saturates: max(min(H + S + shift, 255) - shift, 0).
  * Everything else (row maxima list for the 2nd best score, qe ties to the
  * smallest column, XSTOP/XSUBO/XSTART, the reverse pass for the start) is
  * restated from ksw.c:191-231 and 343-356.
+ *
+ * The restatement computes in plain int.  The reference computes in SIMD lanes
+ * of the pass's width (8 bits in ksw_u8, 16 in ksw_i16), and the two agree
+ * only while everything the lanes would clip is restated or ruled out:
+ *
+ *   restated  u8: the M path, max(min(H + S + shift, 255) - shift, 0), with the
+ *             profile byte (uint8)(S + shift) (ksw.c:93, 153-154); every
+ *             subtraction of a gap penalty floors at 0 (subs_epu8 / subs_epu16);
+ *             the early stop at gmax + shift >= 255 and its score 255.
+ *   assumed   1. o_del + e_del <= 65535 and o_ins + e_ins <= 65535: ksw_i16
+ *                keeps 16 bits of them (_mm_set1_epi16, ksw.c:252-255), and
+ *                ksw_u8's caller is bounded by 2. (ORACLE_A2_WORD)
+ *             2. in u8 (KSW_XBYTE): e_del, e_ins, o_del + e_del, o_ins + e_ins
+ *                <= 255: ksw_u8 keeps 8 bits of them (_mm_set1_epi8,
+ *                ksw.c:132-135). (ORACLE_A2_BYTE)
+ *             3. in i16: qlen * max(mat) <= 32767, so that no H reaches the
+ *                ceiling adds_epi16 (ksw.c:270) clamps at; E and F are below H.
+ *                (ORACLE_A2_SAT)
+ *             4. every matrix entry is an int8 and the query / target bases
+ *                are 0..4 (m = 5).
+ *   oracle_align2_outside says which of 1-3 a call breaks, and
+ *   oracle_align2_batch refuses a batch that holds such a call; only
+ *   oracle_ksw_align2 and oracle_align2_batch_ungated run the int arithmetic
+ *   regardless (tests/test_align2_range.py measures how often it then differs).
  */
 #include <limits.h>
 #include <stdlib.h>
@@ -174,8 +197,27 @@ void oracle_ksw_align2(int qlen, const uint8_t *query, int tlen, const uint8_t *
   if (r->score == rr.score) r->tb = r->te - rr.te, r->qb = r->qe - rr.qe;
 }
 
+int oracle_align2_outside(const bwagpu_opt_t *opt, int qlen, int xtra)
+{
+  const int oe_del = opt->o_del + opt->e_del, oe_ins = opt->o_ins + opt->e_ins;
+  int i, mx = 0;
+  if (oe_del > 65535 || oe_ins > 65535) return ORACLE_A2_WORD;
+  if (xtra & KSW_XBYTE)
+    return opt->e_del > 255 || opt->e_ins > 255 || oe_del > 255 || oe_ins > 255 ? ORACLE_A2_BYTE : 0;
+  for (i = 0; i < 25; ++i) mx = imax2(mx, opt->mat[i]);
+  return (int64_t)qlen * mx > 32767 ? ORACLE_A2_SAT : 0;
+}
+
 int oracle_align2_batch(const bwagpu_opt_t *opt, int32_t n_tasks, const bwagpu_align2_task_t *tasks,
                         const uint8_t *qpool, const uint8_t *tpool, bwagpu_kswr_t *results, int64_t *cells)
+{
+  for (int32_t k = 0; k < n_tasks; ++k)
+    if (oracle_align2_outside(opt, tasks[k].qlen, tasks[k].xtra)) return -(k + 1);
+  return oracle_align2_batch_ungated(opt, n_tasks, tasks, qpool, tpool, results, cells);
+}
+
+int oracle_align2_batch_ungated(const bwagpu_opt_t *opt, int32_t n_tasks, const bwagpu_align2_task_t *tasks,
+                                const uint8_t *qpool, const uint8_t *tpool, bwagpu_kswr_t *results, int64_t *cells)
 {
   for (int32_t k = 0; k < n_tasks; ++k) {
     const bwagpu_align2_task_t *t = &tasks[k];

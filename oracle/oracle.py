@@ -49,6 +49,10 @@ def oracle_lib():
     lib.oracle_extend_batch_extremes.restype = C.c_int
     lib.oracle_align2_batch.argtypes = [C.POINTER(abi.Opt), C.c_int32, _VP, _VP, _VP, _VP, _VP]
     lib.oracle_align2_batch.restype = C.c_int
+    lib.oracle_align2_batch_ungated.argtypes = lib.oracle_align2_batch.argtypes
+    lib.oracle_align2_batch_ungated.restype = C.c_int
+    lib.oracle_align2_outside.argtypes = [C.POINTER(abi.Opt), C.c_int, C.c_int]
+    lib.oracle_align2_outside.restype = C.c_int
     lib.oracle_reg2aln_batch.argtypes = [C.POINTER(abi.Opt), C.POINTER(abi.Bns), _VP, C.c_int32, _VP, _VP,
                                          C.c_int, C.c_int, _VP, _VP, _VP]
     lib.oracle_reg2aln_batch.restype = C.c_int
@@ -195,17 +199,33 @@ def extend_extremes(opt: dict, tasks, qpool, tpool):
     return res[:len(tasks)], cells, ext[:len(tasks)]
 
 
+class Align2Outside(ValueError):
+    """oracle.align2("oracle", ...) on a task whose reference result the restatement does not give"""
+
+
 def align2(which: str, opt: dict, tasks, qpool, tpool):
-    """ksw_align2 over a task batch -> (kswr records, cells[cells, rows] or None)"""
+    """ksw_align2 over a task batch -> (kswr records, cells[cells, rows] or None).
+
+    "oracle" raises Align2Outside for a batch that holds a task outside the limits under which
+    the restatement equals the reference (ksw_align.c's header: gap penalties past the SIMD
+    lane width, 16-bit scores that could saturate), so that nothing is ever compared with its
+    idealised numbers; "oracle_ungated" computes them regardless (tests/test_align2_range.py
+    alone: the proof that each gate is needed); "ref" is the compiled reference."""
     o = abi.opt_from_dict(opt)
     tasks = np.ascontiguousarray(tasks, abi.ALIGN2_TASK_DTYPE)
     qpool = np.ascontiguousarray(qpool, np.uint8)
     tpool = np.ascontiguousarray(tpool, np.uint8)
     res = np.zeros(max(len(tasks), 1), abi.KSWR_DTYPE)
-    if which == "oracle":
+    if which in ("oracle", "oracle_ungated"):
         cells = np.zeros(2, np.int64)
-        oracle_lib().oracle_align2_batch(C.byref(o), len(tasks), _ptr(tasks), _ptr(qpool), _ptr(tpool),
-                                         _ptr(res), _ptr(cells))
+        lib = oracle_lib()
+        fn = lib.oracle_align2_batch if which == "oracle" else lib.oracle_align2_batch_ungated
+        rc = fn(C.byref(o), len(tasks), _ptr(tasks), _ptr(qpool), _ptr(tpool), _ptr(res), _ptr(cells))
+        if rc:
+            k = -rc - 1
+            what = lib.oracle_align2_outside(C.byref(o), int(tasks["qlen"][k]), int(tasks["xtra"][k]))
+            limit = {1: "o + e > 65535", 2: "XBYTE with e or o + e > 255", 3: "qlen * max(mat) > 32767"}[what]
+            raise Align2Outside(f"task {k} is outside the oracle's limits: {limit}")
         return res[:len(tasks)], cells
     lib = ref_lib()
     if lib is None or not hasattr(lib, "ref_align2_batch"):

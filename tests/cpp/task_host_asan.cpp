@@ -497,6 +497,82 @@ static void test_align2() {
       if (i) EXPECT(work[(size_t)p.bins[i - 1]] >= work[(size_t)p.bins[i]]);
     }
   }
+  {  // the reference's SIMD lane widths (pure.h): each quantity's last admitted value plans, the
+     // next is refused with its reason.  Byte quantities: a batch with a byte task (a2_base's first).
+    const char* const kByte =
+        "ksw_align2 XBYTE task with e_del, e_ins, o_del + e_del or o_ins + e_ins > 255: the reference's 8-bit pass "
+        "keeps 8 bits of them (_mm_set1_epi8, ksw.c:132-135)";
+    const char* const kWord =
+        "ksw_align2 with o_del + e_del or o_ins + e_ins > 65535: the reference keeps 16 bits of them "
+        "(_mm_set1_epi16, ksw.c:252-255)";
+    auto with = [](int o_del, int e_del, int o_ins, int e_ins) {
+      A2 c = a2_base();
+      c.o.o_del = o_del, c.o.e_del = e_del, c.o.o_ins = o_ins, c.o.e_ins = e_ins;
+      c.o.oe_del = o_del + e_del, c.o.oe_ins = o_ins + e_ins;
+      return c;
+    };
+    struct Edge { int o_del, e_del, o_ins, e_ins; };
+    const Edge byte_in[] = {{254, 1, 6, 1}, {6, 1, 254, 1}, {0, 255, 6, 1}, {6, 1, 1, 254}, {1, 254, 6, 1}, {254, 1, 254, 1}};
+    const Edge byte_out[] = {{255, 1, 6, 1}, {6, 1, 255, 1}, {0, 256, 6, 1}, {6, 1, 1, 255}, {1, 255, 6, 1}, {300, 1, 6, 1}};
+    for (const Edge& e : byte_in) {
+      A2 c = with(e.o_del, e.e_del, e.o_ins, e.e_ins);
+      EXPECT(align2_byte_ok(c.o) && c.run() == BWAGPU_OK);
+    }
+    for (const Edge& e : byte_out) {
+      A2 c = with(e.o_del, e.e_del, e.o_ins, e.e_ins);
+      EXPECT(!align2_byte_ok(c.o) && c.run() == BWAGPU_E_UNSUPPORTED && is(c.why, kByte));
+      // the same options with no byte task in the batch: word tasks stay admitted
+      for (auto& t : c.t) t.xtra &= ~BWAGPU_KSW_XBYTE;
+      EXPECT(c.run() == BWAGPU_OK && c.plan.all.size() == c.t.size());
+    }
+    {  // e_del alone: 255 is the last value a lane holds; it needs o_del = 0 to keep o_del + e_del there
+      DevOpt o = default_opt();
+      o.o_del = 0, o.e_del = 255, o.oe_del = 255;
+      EXPECT(align2_byte_ok(o));
+      o.e_del = 256;
+      o.oe_del = 255;  // (not reachable from bwagpu_opt_t: the clause on e_del itself)
+      EXPECT(!align2_byte_ok(o));
+      o = default_opt();
+      o.o_ins = 1, o.e_ins = 254, o.oe_ins = 255;
+      EXPECT(align2_byte_ok(o));
+      o.e_ins = 256, o.oe_ins = 255;
+      EXPECT(!align2_byte_ok(o));
+    }
+    {  // a mixed batch is refused at its first byte task: the verdict of an earlier word task wins
+      A2 c = with(300, 1, 6, 1);
+      c.t = {a2(0, 100, 0, 150, 0), a2(100, 50, 150, 80, BWAGPU_KSW_XBYTE), a2(0, BWAGPU_MAX_READ_LEN + 1, 0, 80, 0)};
+      EXPECT(c.run() == BWAGPU_E_UNSUPPORTED && is(c.why, kByte));
+      c.t[0].qlen = BWAGPU_MAX_READ_LEN + 1;
+      EXPECT(c.run() == BWAGPU_E_UNSUPPORTED && is(c.why, "qlen > BWAGPU_MAX_READ_LEN"));
+      c.t[0] = a2(0, 100, 0, 150, 0);
+      c.t[1].toff = 4096;  // a byte task outside its pools is a bad argument first
+      EXPECT(c.run() == BWAGPU_E_INVAL && is(c.why, "task outside its pools"));
+    }
+    // the word sums: 65535 plans (word tasks; a byte task is over the byte limit there), 65536 is refused for all
+    const Edge word_in[] = {{65534, 1, 6, 1}, {6, 1, 65534, 1}, {1, 65534, 6, 1}, {6, 1, 1, 65534}};
+    const Edge word_out[] = {{65535, 1, 6, 1}, {6, 1, 65535, 1}, {1, 65535, 6, 1}, {6, 1, 1, 65535}};
+    for (const Edge& e : word_in) {
+      A2 c = with(e.o_del, e.e_del, e.o_ins, e.e_ins);
+      EXPECT(align2_opt_unsupported(c.o) == nullptr);
+      EXPECT(c.run() == BWAGPU_E_UNSUPPORTED && is(c.why, kByte));
+      for (auto& t : c.t) t.xtra &= ~BWAGPU_KSW_XBYTE;
+      EXPECT(c.run() == BWAGPU_OK);
+    }
+    for (const Edge& e : word_out) {
+      A2 c = with(e.o_del, e.e_del, e.o_ins, e.e_ins);
+      for (auto& t : c.t) t.xtra &= ~BWAGPU_KSW_XBYTE;
+      EXPECT(c.run() == BWAGPU_E_UNSUPPORTED && is(c.why, kWord) && is(align2_opt_unsupported(c.o), kWord));
+    }
+    // the 16-bit ceiling at a = 127: 258 columns (32766) plan, 259 (32893) do not
+    A2 c = a2_base();
+    c.o.max_mat = 127;
+    c.t[1].qlen = 258;
+    EXPECT(align2_word_fits(258, 127) && c.run() == BWAGPU_OK);
+    c.t[1].qlen = 259;
+    EXPECT(!align2_word_fits(259, 127) && c.run() == BWAGPU_E_UNSUPPORTED &&
+           is(c.why, "i16 scores could saturate (qlen * max score > 32767)"));
+    EXPECT(align2_word_fits(32767, 1) && !align2_word_fits(32768, 1));
+  }
 }
 
 // ---------------------------------------------------------------- stream

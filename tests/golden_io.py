@@ -82,6 +82,23 @@ def load_align2(name):
         z["qpool"], z["tpool"]
 
 
+def load_align2_range():
+    """tests/golden/align2_range.npz (oracle/gen_golden.py --only-align2-range: the families of
+    tests/align2_cases.py through the reference's ksw_align2) ->
+    {(family, side): (opt, tasks, the reference's kswr_t records, qpool, tpool)}"""
+    z = _npz("align2_range")
+    out = {}
+    for key in z.files:
+        if key.endswith("__tasks"):
+            name, side, _ = key.split("__")
+            k = f"{name}__{side}__"
+            opt = dict(zip(OPT_KEYS, z[k + "opt_int"].tolist()))
+            opt["mat"] = z[k + "opt_mat"].astype(np.int8)
+            out[(name, side)] = (opt, z[k + "tasks"].astype(abi.ALIGN2_TASK_DTYPE),
+                                 z[k + "task_res"].astype(abi.KSWR_DTYPE), z[k + "qpool"], z[k + "tpool"])
+    return out
+
+
 def kswr_mismatch(tasks, got, want) -> str | None:
     g, w = got.view(np.int32).reshape(-1, 7), want.view(np.int32).reshape(-1, 7)
     bad = np.nonzero((g != w).any(axis=1))[0]
