@@ -269,7 +269,9 @@ class GoldenInGrch38:
         ann_len[len(gl) + len(grch.ann_len) - 1] += self.off_b - self.off_grch - lr
         self.ann_len = ann_len.astype(np.int32)
         self.rid_b = len(gl) + len(grch.ann_len)
-        self.pac = np.concatenate([body(golden.pac, lg), body(grch.pac, lr), body(golden.pac, lg)])
+        # l_pac // 4 + 1 bytes as in a .pac file: one more, zero, when the small genome's length is a multiple of 4
+        tail = np.zeros(self.l_pac // 4 + 1 - (self.off_b >> 2) - (lg + 3) // 4, np.uint8)
+        self.pac = np.concatenate([body(golden.pac, lg), body(grch.pac, lr), body(golden.pac, lg), tail])
 
     def translate(self, b: Batch) -> Batch:
         """a batch on the golden genome -> the same batch here (even reads on

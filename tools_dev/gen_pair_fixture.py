@@ -296,8 +296,8 @@ class RefSel(RefPair):
         return recs, regs
 
 
-def run_set(name, rs: RefSel, pes, seqs, regs_by_read, pair_id0, out_dir, extra=None):
-    """both passes of the reference over every pair -> coverage counts"""
+def select_pairs(name, rs: RefSel, pes, seqs, regs_by_read, pair_id0):
+    """both passes of the reference over every pair -> (the fixture's result arrays, coverage counts)"""
     nr = len(regs_by_read)
     assert nr % 2 == 0
     cov = dict.fromkeys(COVERAGE_KEYS, 0)
@@ -336,16 +336,23 @@ def run_set(name, rs: RefSel, pes, seqs, regs_by_read, pair_id0, out_dir, extra=
             sel[nopair].append(rec)
             mapq[nopair] += om
     cat = lambda v, dt: np.concatenate(v) if len(v) else np.zeros(0, dt)  # noqa: E731
+    res = dict(n=np.array([len(a) for a in regs_by_read], np.int32), n_pri=np.array(n_pri, np.int32),
+               marked=cat(marked, abi.ALNREG_DTYPE), final=cat(fin, abi.ALNREG_DTYPE),
+               sel=np.array(sel[0], abi.PAIRSEL_DTYPE), sel_nopair=np.array(sel[1], abi.PAIRSEL_DTYPE),
+               out_mapq=cat(mapq[0], np.int32), out_mapq_nopair=cat(mapq[1], np.int32))
+    return res, cov
+
+
+def run_set(name, rs: RefSel, pes, seqs, regs_by_read, pair_id0, out_dir, extra=None):
+    """the reference over every pair, written to pair_<name>.npz -> coverage counts"""
+    nr = len(regs_by_read)
+    res, cov = select_pairs(name, rs, pes, seqs, regs_by_read, pair_id0)
     o = rs.o
     path = os.path.join(out_dir, f"pair_{name}.npz")
     np.savez_compressed(
         path, **(extra or {}), pair_id0=np.array([pair_id0], np.int64),
         selopt_int=np.array([getattr(o, k) for k in SELOPT_KEYS_I], np.int32),
-        selopt_f=np.array([getattr(o, k) for k in SELOPT_KEYS_F], np.float32),
-        n=np.array([len(a) for a in regs_by_read], np.int32), n_pri=np.array(n_pri, np.int32),
-        marked=cat(marked, abi.ALNREG_DTYPE), final=cat(fin, abi.ALNREG_DTYPE),
-        sel=np.array(sel[0], abi.PAIRSEL_DTYPE), sel_nopair=np.array(sel[1], abi.PAIRSEL_DTYPE),
-        out_mapq=cat(mapq[0], np.int32), out_mapq_nopair=cat(mapq[1], np.int32),
+        selopt_f=np.array([getattr(o, k) for k in SELOPT_KEYS_F], np.float32), **res,
         coverage=np.array([int(cov[k]) for k in COVERAGE_KEYS], np.int64))
     size = os.path.getsize(path)
     print(f"[gen_pair] pair_{name}: {nr // 2} pairs, {sum(len(a) for a in regs_by_read)} regions, {size} bytes, "

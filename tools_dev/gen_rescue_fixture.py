@@ -104,8 +104,7 @@ class RefPair:
         self.l_pac = rp.l_pac
         self.ann_off = np.asarray(refd["ann_offset"], np.int64)
         self.ann_len = np.asarray(refd["ann_len"], np.int64)
-        g = genome_bases(refd).astype(np.uint8)
-        self.both = np.concatenate([g, (3 - g[::-1]).astype(np.uint8)])  # bns_get_seq's two strands
+        self.both = self.strands(refd)
         vp = C.c_void_p
         lib = self.lib
         lib.mem_pestat.argtypes = [C.POINTER(MemOpt), C.c_int64, C.c_int, vp, vp]
@@ -114,6 +113,12 @@ class RefPair:
         lib.mem_matesw.restype = C.c_int
         lib.ksw_align2.argtypes = [C.c_int, vp, C.c_int, vp, C.c_int, vp] + [C.c_int] * 5 + [vp]
         lib.ksw_align2.restype = Kswr
+
+    @staticmethod
+    def strands(refd):
+        """bns_get_seq's two strands; the walk reads window slices [rb:re) of it"""
+        g = genome_bases(refd).astype(np.uint8)
+        return np.concatenate([g, (3 - g[::-1]).astype(np.uint8)])
 
     def pestat(self, regs_by_read):
         """mem_pestat over per-read region arrays -> PESTAT_DTYPE[4]"""
@@ -253,12 +258,11 @@ class RefPair:
         return n, ma, peak
 
 
-def run_pairs(name, opt, pairopt, refd, genome_id, alt, seq_off, seq, regs_by_read, out_dir, own_genome=None):
-    """the reference over every pair -> the fixture's coverage counts"""
-    rp = RefPair(opt, pairopt, refd, alt)
+def rescue_pairs(name, rp, pairopt, pes, seq_off, seq, regs_by_read, per_pair=None):
+    """the rescue loop of mem_sam_pe over every pair, with the observing walk beside it ->
+    (regions per read, out_n, n_sw, peak_n, coverage counts); per_pair, if a list, gets every pair's events"""
     nr = len(regs_by_read)
     assert nr % 2 == 0
-    pes = rp.pestat(regs_by_read)
     cov = dict.fromkeys(COVERAGE_KEYS, 0)
     out, out_n, n_sw, peak_n = [], [], [], []
     for p in range(nr // 2):
@@ -296,6 +300,17 @@ def run_pairs(name, opt, pairopt, refd, genome_id, alt, seq_off, seq, regs_by_re
         for k in ("regs_added", "regs_added_rev", "regs_added_to_empty", "sw_no_region", "dedup_removed",
                   "windows_changed", "windows_rejected", "spec_ignored", "needed_not_speculated"):
             cov[k] += int(ev[k])
+        if per_pair is not None:
+            per_pair.append(ev)
+    return out, out_n, n_sw, peak_n, cov
+
+
+def run_pairs(name, opt, pairopt, refd, genome_id, alt, seq_off, seq, regs_by_read, out_dir, own_genome=None):
+    """the reference over every pair -> the fixture's coverage counts"""
+    rp = RefPair(opt, pairopt, refd, alt)
+    nr = len(regs_by_read)
+    pes = rp.pestat(regs_by_read)
+    out, out_n, n_sw, peak_n, cov = rescue_pairs(name, rp, pairopt, pes, seq_off, seq, regs_by_read)
     reg_n = np.array([len(a) for a in regs_by_read], np.int32)
     # The tests give every read an output span of n + HEADROOM regions and expect every pair to
     # finish.  The reference itself grows a few reads by more (reads in repeats with ten and more
