@@ -9,6 +9,7 @@
 #include "ctx.h"
 #include "engine.h"
 #include "reg2aln.h"
+#include "samtext.h"
 
 using namespace bwagpu;
 
@@ -422,6 +423,30 @@ int bwagpu_reg2aln_jobs_device(bwagpu_ctx_t* ctx, int32_t n_reads, const int64_t
                                            dev_tasks, dev_job_of, dev_n_jobs, ctx->r2d_sums.as<int32_t>(), st);
   if (hipEventRecord(ctx->r2d_done, st) == hipSuccess) ctx->r2d_pending = true;
   HIPC(e, "reg2aln jobs launch");
+  return BWAGPU_OK;
+}
+
+int bwagpu_xa_select_device(bwagpu_ctx_t* ctx, const bwagpu_samopt_t* xopt, int32_t n_reads,
+                            const int64_t* dev_reg_off, const bwagpu_alnreg_t* dev_regs, const int32_t* dev_n,
+                            const bwagpu_pairsel_t* dev_sel, const int32_t* dev_out_mapq, int32_t* dev_xa_of,
+                            int32_t* dev_job_select, void* stream) {
+  if (!ctx) return BWAGPU_E_INVAL;
+  if (!xopt) return fail(ctx, BWAGPU_E_INVAL, "NULL bwagpu_samopt_t");
+  const char* why = "";
+  if (int rc = sel_flags_check(xopt->flags, &why)) return fail(ctx, rc, why);
+  if (n_reads < 0) return fail(ctx, BWAGPU_E_INVAL, "negative read count");
+  if (n_reads & 1) return fail(ctx, BWAGPU_E_INVAL, "odd read count: reads 2i and 2i+1 are a pair");
+  if (n_reads == 0) return BWAGPU_OK;
+  if (!dev_reg_off || !dev_regs || !dev_n || !dev_sel || !dev_out_mapq || !dev_xa_of || !dev_job_select)
+    return fail(ctx, BWAGPU_E_INVAL, "NULL array");
+  hipStream_t st = nullptr;
+  TRY(entry_stream(ctx, stream, &st));
+  XaSelArgs a{};
+  a.n_reads = n_reads, a.max_hits = xopt->max_XA_hits, a.max_hits_alt = xopt->max_XA_hits_alt;
+  a.drop_ratio = xopt->XA_drop_ratio;  // float -> double, as get_pri_idx's caller passes it
+  a.reg_off = dev_reg_off, a.regs = dev_regs, a.n = dev_n, a.sel = dev_sel, a.out_mapq = dev_out_mapq;
+  a.xa_of = dev_xa_of, a.job_select = dev_job_select;
+  HIPC(launch_xa_select(a, st), "xa_select launch");
   return BWAGPU_OK;
 }
 

@@ -254,4 +254,20 @@ BWAGPU_HD inline int r2_cost_class(int cls, int64_t cost) {
   return s >= kR2CostClasses ? 0 : kR2CostClasses - 1 - (int)s;
 }
 
+// mem_gen_alt's selection (samtext.hip).  get_pri_idx (bwa/bwamem_extra.c:90-95)
+// on a read's n regions: the region whose XA string region i would join, or -1.
+// The reference hands its float option to a double parameter, so the product is
+// a double one: 0.8f is 0.800000011920929, and a hit of 80 under a primary of 100
+// is dropped.  A secondary_all outside the read (the reference would read past
+// its array) joins nothing.
+BWAGPU_HD inline int xa_pri_idx(double drop_ratio, const bwagpu_alnreg_t* a, int n, int i) {
+  const int k = a[i].secondary_all;
+  if (k >= 0 && k < n && a[i].score >= a[k].score * drop_ratio) return k;
+  return -1;
+}
+// the two caps (bwamem_extra.c:118): cnt hits joined the string, has_alt = one of them is an ALT hit
+BWAGPU_HD inline bool xa_over_cap(int cnt, bool has_alt, int max_hits, int max_hits_alt) {
+  return cnt > max_hits_alt || (!has_alt && cnt > max_hits);
+}
+
 }  // namespace bwagpu

@@ -169,6 +169,17 @@ PAIRSEL_DTYPE = np.dtype([("status", "<i4"), ("branch", "<i4"), ("n_pri", "<i4",
 assert PAIRSEL_DTYPE.itemsize == 64 and C.sizeof(SelOpt) == 32
 
 
+class SamOpt(C.Structure):
+    """bwagpu_samopt_t: mem_opt_t's fields of mem_gen_alt's selection"""
+    _fields_ = [("flags", C.c_int32), ("XA_drop_ratio", C.c_float), ("max_XA_hits", C.c_int32),
+                ("max_XA_hits_alt", C.c_int32)]
+
+
+def default_samopt(flags: int = 0) -> SamOpt:
+    """mem_opt_init's defaults (bwa/bwamem.c:71-76)"""
+    return SamOpt(int(flags), 0.80, 5, 200)
+
+
 def default_chainopt() -> dict:
     """mem_opt_init's chaining defaults (bwa/bwamem.c:62-72)"""
     return dict(max_occ=500, max_chain_gap=10000, min_chain_weight=0, max_chain_extend=1 << 30, mask_level=0.5,
@@ -199,6 +210,7 @@ PROTOS = {
     "bwagpu_reg2aln_device": (C.c_int, [_VP, C.c_int32, _VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, _VP, _VP,
                                         _VP, _VP]),
     "bwagpu_reg2aln_jobs_device": (C.c_int, [_VP, C.c_int32, _VP, _VP, _VP, _VP, _VP, C.c_int32, _VP, _VP, _VP, _VP]),
+    "bwagpu_xa_select_device": (C.c_int, [_VP, C.POINTER(SamOpt), C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "bwagpu_debug_reg2aln_times": (C.c_int, [_VP, _VP]),
     "bwagpu_last_stats": (C.c_int, [_VP, C.c_int, C.POINTER(Stats)]),
     "bwagpu_debug_set_trace": (C.c_int, [_VP, _VP]),

@@ -278,6 +278,18 @@ class Engine:
             C.c_void_p(dev_tasks) if dev_tasks else None, C.c_void_p(dev_job_of), C.c_void_p(dev_n_jobs),
             C.c_void_p(stream) if stream else None), "reg2aln_jobs_device")
 
+    def xa_select_device(self, n_reads: int, dev_reg_off: int, dev_regs: int, dev_n: int, dev_sel: int,
+                         dev_out_mapq: int, dev_xa_of: int, dev_job_select: int, xopt: abi.SamOpt | None = None,
+                         stream: int | None = None):
+        """mem_gen_alt's selection on what pair_select_device left, asynchronous on stream: dev_xa_of (the
+        region whose XA string a region joins, or -1) and dev_job_select (>= 0: the region needs a CIGAR),
+        both parallel to the regions; dev_job_select feeds reg2aln_jobs_device's dev_select"""
+        xo = abi.default_samopt() if xopt is None else xopt
+        self._check(self.lib.bwagpu_xa_select_device(
+            self.ctx, C.byref(xo), int(n_reads), C.c_void_p(dev_reg_off), C.c_void_p(dev_regs), C.c_void_p(dev_n),
+            C.c_void_p(dev_sel), C.c_void_p(dev_out_mapq), C.c_void_p(dev_xa_of), C.c_void_p(dev_job_select),
+            C.c_void_p(stream) if stream else None), "xa_select_device")
+
     def debug_reg2aln_times(self) -> dict:
         """the last reg2aln_device call (waits for it): the host's wait at the read-back, the bin kernels'
         span by HIP events, the host time of the call.  The first use only switches the timing on"""

@@ -75,8 +75,12 @@
  *       what mem_sam_pe does after the rescue loop up to its first
  *       mem_reg2aln: mem_mark_primary_se on both reads (bwamem_pair.c:280-281),
  *       mem_pair (:185-246), the proper-pair / unpaired decision and the mapq
- *       arithmetic (:288-336, :374-390, mem_approx_mapq_se).  mem_gen_alt / XA,
- *       the CIGARs and the SAM text stay on the host.
+ *       arithmetic (:288-336, :374-390, mem_approx_mapq_se).
+ *   bwagpu_xa_select_device
+ *       the selection of mem_gen_alt (bwa/bwamem_extra.c:90-118): which regions
+ *       are hits of which record's XA string, and so which regions need a
+ *       CIGAR (bwagpu_reg2aln_jobs_device, bwagpu_reg2aln_device).  The XA
+ *       strings themselves and the SAM text (mem_aln2sam) stay on the host.
  *   bwagpu_last_error
  *       the what() of fpgaHangError / fpgaResultsError / std::runtime_error
  *       (src/util.h:16-32, OpenCLEnv.h:21-31).
@@ -826,7 +830,9 @@ typedef struct {
    in_status[i] != 0 (bwagpu_mate_rescue's status array fits) gets
    BWAGPU_SEL_SKIPPED.  A pair with a non-zero status keeps its regions
    untouched, its out_mapq entries are -1 and the caller keeps the CPU path for
-   it.  mem_gen_alt / XA, CIGARs and the SAM text stay on the host.
+   it.  mem_gen_alt's selection is bwagpu_xa_select_device, the CIGARs are
+   bwagpu_reg2aln_jobs_device and bwagpu_reg2aln_device; the XA strings and the
+   SAM text stay on the host.
    Before any launch: odd n_reads, negative counts, n_pri outside [0, n], a rid
    outside the reference, overlapping spans and NULLs return BWAGPU_E_INVAL;
    the refused flags and a live orientation with high - low over 2^20 return
@@ -846,6 +852,49 @@ int bwagpu_pair_select_device(bwagpu_ctx_t *ctx, const bwagpu_selopt_t *sopt, co
                               bwagpu_alnreg_t *dev_regs, const int32_t *dev_n, const int32_t *dev_n_pri,
                               const int32_t *dev_in_status, bwagpu_pairsel_t *dev_sel, int32_t *dev_out_mapq,
                               void *stream);
+
+/* ---- paired ends: the selection of mem_gen_alt (XA) on the device ---- */
+
+/* mem_opt_t's fields the SAM stage reads after the pair selection: so far those
+   of mem_gen_alt's selection (bwa/bwamem.h:50, 56; defaults 0.80f, 5, 200:
+   bwamem.c:71-76).  flags are mem_opt_t.flag's bits:
+   the four bwagpu_selopt_t refuses return BWAGPU_E_UNSUPPORTED (with MEM_F_ALL
+   the reference does not call mem_gen_alt at all), every other bit is ignored. */
+typedef struct {
+  int32_t flags;
+  float XA_drop_ratio;
+  int32_t max_XA_hits, max_XA_hits_alt;
+} bwagpu_samopt_t;
+
+/* The selection of mem_gen_alt (bwa/bwamem_extra.c:90-118, as called at
+   bwamem_pair.c:337-340 and bwamem.c:1026-1027) for every read of a batch, on
+   device memory, asynchronous on stream (hipStream_t, NULL = the context's
+   slot-0 stream; no host wait): directly after bwagpu_pair_select_device on
+   that stream, on the regions, dev_sel and dev_out_mapq it leaves.
+   dev_xa_of and dev_job_select are parallel to the regions; only the entries of
+   the reads' regions are written.  For a pair with sel.status ==
+   BWAGPU_SEL_DONE, with i and r indices into one read's regions:
+   dev_xa_of[reg_off + i] = r when region i is a hit of the XA string that the
+   record of region r prints, else -1.  That is: get_pri_idx(i) == r (in
+   double, as the reference computes it), the string's hit count cnt[r] within
+   max_XA_hits, or within max_XA_hits_alt when one of its hits is an ALT hit,
+   and out_mapq[reg_off + r] >= 0 (a string is only ever printed on an emitted
+   record; the counts and caps run over all regions).  The hits of r's string
+   are the regions with xa_of == r in index order.
+   dev_job_select[reg_off + i] = 0 when region i needs a CIGAR: it has a record
+   (out_mapq >= 0), or it is an XA hit (xa_of >= 0), or it is sel.z of a
+   BWAGPU_SEL_NO_PAIRING pair (the mate record the other read's lines refer
+   to, which may have no record of its own); else -1.  It is what
+   bwagpu_reg2aln_jobs_device takes as dev_select in the place of out_mapq.
+   A pair with another status gets -1 in both arrays.
+   Before any launch: NULLs, negative or odd n_reads return BWAGPU_E_INVAL, the
+   refused flags BWAGPU_E_UNSUPPORTED.  Nothing is validated on the device
+   except what keeps the kernel inside the reads' spans: a secondary_all
+   outside its read joins no string. */
+int bwagpu_xa_select_device(bwagpu_ctx_t *ctx, const bwagpu_samopt_t *xopt, int32_t n_reads,
+                            const int64_t *dev_reg_off, const bwagpu_alnreg_t *dev_regs, const int32_t *dev_n,
+                            const bwagpu_pairsel_t *dev_sel, const int32_t *dev_out_mapq, int32_t *dev_xa_of,
+                            int32_t *dev_job_select, void *stream);
 
 /* Tuning, test and profiling entry points (bwagpu_debug_*, bwagpu_prof_*,
    bwagpu_ctx_ext_form / _row_bound, bwagpu_streams_concurrent) are declared
