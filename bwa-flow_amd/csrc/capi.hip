@@ -303,80 +303,34 @@ std::vector<Slot*> all_slots(bwagpu_ctx_t* ctx) {
 
 void destroy_ctx(bwagpu_ctx_t* ctx) {
   if (!ctx) return;
+  // 1. every wait, free and destroy below is on the context's device, whatever the calling thread had current
   (void)hipSetDevice(ctx->device);
-  for (auto& s : ctx->slot) {
-    if (s.stream) (void)hipStreamSynchronize(s.stream);
-    s.d_in.release(); s.release_scratch();
-    s.d_out.release(); s.d_n.release(); s.d_stats.release();
-    s.h_in.release(); s.h_out.release(); s.h_n.release(); s.h_stats.release();
-    s.h_dense.release(); s.h_off.release(); s.d_off.release();
-    if (s.ev0) (void)hipEventDestroy(s.ev0);
-    if (s.ev1) (void)hipEventDestroy(s.ev1);
-    if (s.ev2) (void)hipEventDestroy(s.ev2);
-    if (s.ev3) (void)hipEventDestroy(s.ev3);
-    if (s.stream) (void)hipStreamDestroy(s.stream);
-  }
-  for (int k = 0; k < BWAGPU_NUM_SLOTS; ++k) {
-    if (ctx->dev_stream[k]) (void)hipStreamSynchronize(ctx->dev_stream[k]);
-    Slot& s = ctx->dev_scratch[k];
-    s.release_scratch();
-    s.d_stats.release();
-  }
-  if (ctx->sdh_done) {
-    (void)hipEventSynchronize(ctx->sdh_done);
-    (void)hipEventDestroy(ctx->sdh_done);
-  }
-  for (hipStream_t x : ctx->side_graveyard) {
-    (void)hipStreamSynchronize(x);
-    (void)hipStreamDestroy(x);
-  }
-  ctx->side_graveyard.clear();
-  for (hipEvent_t e : ctx->prof_ev) (void)hipEventDestroy(e);
-  ctx->prof_ev.clear();
-  for (int i = 0; i < bwagpu_ctx::kA2Streams; ++i) {
-    if (ctx->a2_st[i]) (void)hipStreamSynchronize(ctx->a2_st[i]);
-    if (ctx->a2_st[i]) (void)hipStreamDestroy(ctx->a2_st[i]);
-    if (ctx->a2_join[i]) (void)hipEventDestroy(ctx->a2_join[i]);
-  }
-  if (ctx->a2_fork) (void)hipEventDestroy(ctx->a2_fork);
-  ctx->ch_slot.release_scratch();
-  for (int k = 0; k < 2; ++k) {
-    if (ctx->ch_cs.side[k]) (void)hipStreamSynchronize(ctx->ch_cs.side[k]);
-    if (ctx->ch_cs.side[k]) (void)hipStreamDestroy(ctx->ch_cs.side[k]);
-    if (ctx->ch_cs.join[k]) (void)hipEventDestroy(ctx->ch_cs.join[k]);
-  }
-  if (ctx->ch_cs.fork) (void)hipEventDestroy(ctx->ch_cs.fork);
-  ctx->ch_slot.d_out.release(); ctx->ch_slot.d_n.release(); ctx->ch_slot.d_stats.release();
-  // the last bwagpu_reg2aln_device / _jobs_device call may still be running on the r2d_* scratch
+  // 2. before anything is freed: every stream and pending event the context can have work on (only
+  //    those: other contexts and the caller's own streams share the device).  A half-built context
+  //    has null handles.
+  std::vector<hipStream_t> busy = ctx->side_graveyard;
+  for (Slot* s : all_slots(ctx)) busy.insert(busy.end(), {s->stream, s->spec.side});
+  busy.insert(busy.end(), ctx->dev_stream, ctx->dev_stream + BWAGPU_NUM_SLOTS);
+  busy.insert(busy.end(), ctx->a2_st, ctx->a2_st + bwagpu_ctx::kA2Streams);
+  busy.insert(busy.end(), ctx->ch_cs.side, ctx->ch_cs.side + 2);
+  for (hipStream_t x : busy)
+    if (x) (void)hipStreamSynchronize(x);
+  if (ctx->sdh_done) (void)hipEventSynchronize(ctx->sdh_done);
   if (ctx->r2d_done && ctx->r2d_pending) (void)hipEventSynchronize(ctx->r2d_done);
-  for (DevBuf* b : {&ctx->ex_tasks, &ctx->ex_list, &ctx->ex_q, &ctx->ex_t, &ctx->ex_res, &ctx->ex_stats, &ctx->a2_tasks,
-                    &ctx->a2_q, &ctx->a2_t, &ctx->a2_out, &ctx->a2_scratch, &ctx->a2_lists, &ctx->a2_counts, &ctx->a2_boff,
-                    &ctx->r2_tasks, &ctx->r2_q, &ctx->r2_out, &ctx->r2_cig, &ctx->r2_md, &ctx->r2_lists, &ctx->r2_z,
-                    &ctx->r2_stats, &ctx->bwt_words, &ctx->sa_d, &ctx->sa_in, &ctx->sa_out, &ctx->occ_d, &ctx->sup_d, &ctx->sa_full, &ctx->sd_off,
-                    &ctx->sd_seq, &ctx->sd_out, &ctx->sd_n, &ctx->sd_scratch, &ctx->sd_poff, &ctx->sd_pack,
-                    &ctx->sd_heavy, &ctx->sd_dbg, &ctx->st_buf, &ctx->st_start, &ctx->st_q, &ctx->st_tasks, &ctx->st_lists,
-                    &ctx->st_seen, &ctx->st_ctr, &ctx->st_out, &ctx->ch_npos, &ctx->ch_posoff, &ctx->ch_frac,
-                    &ctx->ch_nout, &ctx->ch_noseed, &ctx->ch_nsw, &ctx->ch_need, &ctx->ch_swtab, &ctx->ch_alt,
-                    &ctx->ch_kpos, &ctx->ch_rbeg, &ctx->ch_qinfo, &ctx->ch_label, &ctx->ch_score, &ctx->ch_slist,
-                    &ctx->ch_ord, &ctx->ch_chains, &ctx->ch_nodes, &ctx->ch_ochains, &ctx->ch_oslist, &ctx->ch_bins, &ctx->ch_dbg, &ctx->ch_swoff, &ctx->ch_swtasks, &ctx->ch_swt,
-                    &ctx->ch_swskip, &ctx->ch_swres, &ctx->ch_swscr, &ctx->ch_ocoff, &ctx->ch_osoff, &ctx->ch_rco,
-                    &ctx->ch_cso, &ctx->ch_rid, &ctx->ch_cfrac, &ctx->ch_out, &ctx->ch_seeds, &ctx->ch_regoff,
-                    &ctx->ch_regc, &ctx->rp_stats, &ctx->pe_isize, &ctx->pe_cnt, &ctx->rs_pair, &ctx->rs_soff,
-                    &ctx->rs_tab, &ctx->rs_toff, &ctx->rs_boff, &ctx->rs_qpool, &ctx->rs_ctr, &ctx->rs_scr,
-                    &ctx->ps_scratch, &ctx->ps_log, &ctx->ps_erfc, &ctx->r2d_keys, &ctx->r2d_lists, &ctx->r2d_tab,
-                    &ctx->r2d_z, &ctx->r2d_sums})
-    b->release();
-  ctx->r2d_htab.release();
-  for (hipEvent_t e : {ctx->r2d_done, ctx->r2d_ev[0], ctx->r2d_ev[1]})
+  // 3. only now, with nothing left running: the handles the context owns outside its slots (the
+  //    caller's dev_stream[] are not ours), the reference, and with `delete` every slot and buffer
+  std::vector<hipStream_t> own = ctx->side_graveyard;
+  own.insert(own.end(), ctx->a2_st, ctx->a2_st + bwagpu_ctx::kA2Streams);
+  own.insert(own.end(), ctx->ch_cs.side, ctx->ch_cs.side + 2);
+  for (hipStream_t x : own)
+    if (x) (void)hipStreamDestroy(x);
+  std::vector<hipEvent_t> evs = ctx->prof_ev;
+  evs.insert(evs.end(), {ctx->sdh_done, ctx->r2d_done, ctx->r2d_ev[0], ctx->r2d_ev[1], ctx->a2_fork, ctx->ch_cs.fork,
+                         ctx->ch_cs.join[0], ctx->ch_cs.join[1]});
+  evs.insert(evs.end(), ctx->a2_join, ctx->a2_join + bwagpu_ctx::kA2Streams);
+  evs.insert(evs.end(), ctx->rs_ev, ctx->rs_ev + 4 * kRescueMaxRounds);
+  for (hipEvent_t e : evs)
     if (e) (void)hipEventDestroy(e);
-  ctx->stg.release();
-  for (hipEvent_t e : ctx->rs_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (int k = 0; k < kRescueMaxRounds; ++k)
-    for (DevBuf* b : {&ctx->rs_tasks[k], &ctx->rs_tpool[k], &ctx->rs_res[k]}) b->release();
-  for (HostBuf* b : {&ctx->sdh_in, &ctx->chh_tot, &ctx->chh_rco, &ctx->chh_cso, &ctx->chh_chains, &ctx->chh_seeds, &ctx->chh_regs,
-                     &ctx->chh_n})
-    b->release();
   if (ctx->own_pac && ctx->d_pac) (void)hipFree(ctx->d_pac);
   if (ctx->d_ann_off) (void)hipFree(ctx->d_ann_off);
   if (ctx->d_ann_len) (void)hipFree(ctx->d_ann_len);
@@ -635,59 +589,35 @@ int enqueue_spec(bwagpu_ctx_t* ctx, Slot& s, const DevBatch& db, int lq_max, bwa
                  int64_t* d_stats, hipStream_t st) {
   const size_t nc = (size_t)std::max(db.n_chains, 1), ns = (size_t)std::max(db.n_seeds, 1),
                nr = (size_t)std::max(db.n_reads, 1);
-  HIPC(s.d_win.ensure(sizeof(ChainWin) * nc), "hipMalloc(win)");
-  HIPC(s.d_cread.ensure(sizeof(int32_t) * nc), "hipMalloc(chain_read)");
-  HIPC(s.d_prog.ensure(sizeof(bwagpu_seed_t) * ns), "hipMalloc(prog)");
-  HIPC(s.d_ext.ensure(sizeof(SeedExt) * ns), "hipMalloc(ext)");
-  HIPC(s.d_tasks.ensure(sizeof(int2) * kSpecBins * (nc + (kSpecRounds - 1) * ns)), "hipMalloc(tasks)");
-  HIPC(s.d_ctr.ensure(sizeof(int32_t) * SPC_WORDS), "hipMalloc(ctr)");
-  HIPC(s.d_regpos.ensure(sizeof(int32_t) * ns), "hipMalloc(regpos)");
-  HIPC(s.d_skipf.ensure(sizeof(int32_t) * ns), "hipMalloc(skipf)");
-  HIPC(s.d_heavy.ensure(sizeof(int32_t) * nr), "hipMalloc(heavy)");
-  HIPC(s.d_redo.ensure(sizeof(int32_t) * nr), "hipMalloc(redo)");
-  HIPC(s.d_rbits.ensure(sizeof(uint32_t) * (nr / 32 + 1)), "hipMalloc(rbits)");
-  HIPC(s.d_desc.ensure(sizeof(ReadDesc) * nr), "hipMalloc(desc)");
-  HIPC(s.d_schain.ensure(sizeof(int32_t) * ns), "hipMalloc(seedchain)");
-  HIPC(s.d_hinfo.ensure(sizeof(int4) * nr), "hipMalloc(hinfo)");
-  HIPC(s.d_cov.ensure(sizeof(int32_t) * ns), "hipMalloc(cov)");
-  HIPC(s.d_hflag.ensure(sizeof(int32_t) * ns), "hipMalloc(hflag)");
-  HIPC(s.d_colent.ensure(sizeof(int32_t) * ns), "hipMalloc(colent)");
-  HIPC(s.d_longc.ensure(sizeof(int32_t) * nc), "hipMalloc(longc)");
-  HIPC(s.d_qh.ensure(sizeof(int32_t) * kQHWords), "hipMalloc(qh)");
-  HIPC(s.d_sorth.ensure(sizeof(int32_t) * kSortWords), "hipMalloc(sorth)");
-  HIPC(s.d_stasks.ensure(sizeof(int2) * kSpecBins * (nc + (kSpecRounds - 1) * ns)), "hipMalloc(stasks)");
-  HIPC(s.d_ftask.ensure(sizeof(FatTask) * kSpecBins * (nc + (kSpecRounds - 1) * ns)), "hipMalloc(ftask)");
-  HIPC(s.d_ftaskR.ensure(sizeof(FatTask) * kSpecBins * (nc + (kSpecRounds - 1) * ns)), "hipMalloc(ftaskR)");
+  const size_t n_tasks = kSpecBins * (nc + (kSpecRounds - 1) * ns);  // every list of every round
+  SpecArgs a;
+  HIPC(s.d_win.get(a.win, nc), "hipMalloc(win)");
+  HIPC(s.d_cread.get(a.chain_read, nc), "hipMalloc(chain_read)");
+  HIPC(s.d_prog.get(a.prog, ns), "hipMalloc(prog)");
+  HIPC(s.d_ext.get(a.ext, ns), "hipMalloc(ext)");
+  HIPC(s.d_tasks.get(a.tasks, n_tasks), "hipMalloc(tasks)");
+  HIPC(s.d_ctr.get(a.ctr, SPC_WORDS), "hipMalloc(ctr)");
+  HIPC(s.d_regpos.get(a.regpos, ns), "hipMalloc(regpos)");
+  HIPC(s.d_skipf.get(a.skipf, ns), "hipMalloc(skipf)");
+  HIPC(s.d_heavy.get(a.heavy, nr), "hipMalloc(heavy)");
+  HIPC(s.d_redo.get(a.redo, nr), "hipMalloc(redo)");
+  HIPC(s.d_rbits.get(a.rbits, nr / 32 + 1), "hipMalloc(rbits)");
+  HIPC(s.d_desc.get(a.rdesc, nr), "hipMalloc(desc)");
+  HIPC(s.d_schain.get(a.seedchain, ns), "hipMalloc(seedchain)");
+  HIPC(s.d_hinfo.get(a.hinfo, nr), "hipMalloc(hinfo)");
+  HIPC(s.d_cov.get(a.cov, ns), "hipMalloc(cov)");
+  HIPC(s.d_hflag.get(a.hflag, ns), "hipMalloc(hflag)");
+  HIPC(s.d_colent.get(a.colent, ns), "hipMalloc(colent)");
+  HIPC(s.d_longc.get(a.longc, nc), "hipMalloc(longc)");
+  HIPC(s.d_qh.get(a.qh, kQHWords), "hipMalloc(qh)");
+  HIPC(s.d_sorth.get(a.sorth, kSortWords), "hipMalloc(sorth)");
+  HIPC(s.d_stasks.get(a.stasks, n_tasks), "hipMalloc(stasks)");
+  HIPC(s.d_ftask.get(a.ftask, n_tasks), "hipMalloc(ftask)");
+  HIPC(s.d_ftaskR.get(a.ftaskR, n_tasks), "hipMalloc(ftaskR)");
   // pair matrices of heavy reads: sum over them of 2 * ns * ceil(ns / 64) words,
   // <= 2 * ns_total * (1 + ns_max / 64); reads that do not fit take the per-seed kernel
-  const int64_t mat_words = std::max<int64_t>(1 << 20, 16 * (int64_t)ns);
-  HIPC(s.d_mat.ensure(sizeof(uint64_t) * (size_t)mat_words), "hipMalloc(mat)");
-  SpecArgs a;
-  a.win = s.d_win.as<ChainWin>();
-  a.chain_read = s.d_cread.as<int32_t>();
-  a.prog = s.d_prog.as<bwagpu_seed_t>();
-  a.ext = s.d_ext.as<SeedExt>();
-  a.tasks = s.d_tasks.as<int2>();
-  a.ctr = s.d_ctr.as<int32_t>();
-  a.regpos = s.d_regpos.as<int32_t>();
-  a.skipf = s.d_skipf.as<int32_t>();
-  a.heavy = s.d_heavy.as<int32_t>();
-  a.redo = s.d_redo.as<int32_t>();
-  a.rbits = s.d_rbits.as<uint32_t>();
-  a.rdesc = s.d_desc.as<ReadDesc>();
-  a.seedchain = s.d_schain.as<int32_t>();
-  a.hinfo = s.d_hinfo.as<int4>();
-  a.mat = s.d_mat.as<uint64_t>();
+  HIPC(s.d_mat.get(a.mat, (size_t)std::max<int64_t>(1 << 20, 16 * (int64_t)ns)), "hipMalloc(mat)");
   a.mat_words = (int64_t)(s.d_mat.cap / sizeof(uint64_t));
-  a.cov = s.d_cov.as<int32_t>();
-  a.hflag = s.d_hflag.as<int32_t>();
-  a.colent = s.d_colent.as<int32_t>();
-  a.longc = s.d_longc.as<int32_t>();
-  a.qh = s.d_qh.as<int32_t>();
-  a.sorth = s.d_sorth.as<int32_t>();
-  a.stasks = s.d_stasks.as<int2>();
-  a.ftask = s.d_ftask.as<FatTask>();
-  a.ftaskR = s.d_ftaskR.as<FatTask>();
   static const int ext_prefetch = [] {  // A/B knob of the claim-ahead
     const char* e = getenv("BWAGPU_EXT_PREFETCH");
     return e ? std::max(0, atoi(e)) : 0;
@@ -729,31 +659,28 @@ int enqueue_spec(bwagpu_ctx_t* ctx, Slot& s, const DevBatch& db, int lq_max, bwa
 int enqueue_chain2aln(bwagpu_ctx_t* ctx, Slot& s, const DevBatch& db, int lq_max, bwagpu_alnreg_t* d_out,
                       int32_t* d_n, int64_t* d_stats, hipStream_t st) {
   if (!use_read_kernels()) return enqueue_spec(ctx, s, db, lq_max, d_out, d_n, d_stats, st);
-  HIPC(s.d_win.ensure(sizeof(ChainWin) * (size_t)std::max(db.n_chains, 1)), "hipMalloc(win)");
-  HIPC(s.d_srt.ensure(sizeof(uint64_t) * (size_t)std::max(db.n_seeds, 1)), "hipMalloc(srt)");
-  HIPC(s.d_prog.ensure(sizeof(bwagpu_seed_t) * (size_t)std::max(db.n_seeds, 1)), "hipMalloc(prog)");
+  ChainWin* win = nullptr;
+  bwagpu_seed_t* prog = nullptr;
+  ReadDesc* desc = nullptr;
+  C2AArgs a;
+  HIPC(s.d_win.get(win, (size_t)db.n_chains), "hipMalloc(win)");
+  HIPC(s.d_srt.get(a.srt, (size_t)db.n_seeds), "hipMalloc(srt)");
+  HIPC(s.d_prog.get(prog, (size_t)db.n_seeds), "hipMalloc(prog)");
   const size_t nr = (size_t)std::max(db.n_reads, 1);
-  HIPC(s.d_desc.ensure(sizeof(ReadDesc) * nr), "hipMalloc(desc)");
+  HIPC(s.d_desc.get(desc, nr), "hipMalloc(desc)");
   // bins | read_list, n_reads each
   HIPC(s.d_lists.ensure(2 * sizeof(int32_t) * nr), "hipMalloc(lists)");
   int32_t* bins = s.d_lists.as<int32_t>();
   int32_t* read_list = bins + nr;
-  HIPC(s.d_counts.ensure(sizeof(int32_t) * kCountWords), "hipMalloc(counts)");
-  HIPC(hipMemsetAsync(s.d_counts.p, 0, sizeof(int32_t) * kCountWords, st), "memset counts");
+  HIPC(s.d_counts.get(a.counts, kCountWords), "hipMalloc(counts)");
+  HIPC(hipMemsetAsync(a.counts, 0, sizeof(int32_t) * kCountWords, st), "memset counts");
   if (db.n_reads) HIPC(hipMemsetAsync(d_n, 0, sizeof(int32_t) * db.n_reads, st), "memset out_n");
-  HIPC(launch_chain_prep(ctx->opt, ctx->ref, db, s.d_win.as<ChainWin>(), s.d_srt.as<uint64_t>(),
-                         s.d_prog.as<bwagpu_seed_t>(), d_stats, st),
-       "chain_prep launch");
-  HIPC(launch_read_order(db, bins, s.d_counts.as<int32_t>() + kHistOff, s.d_counts.as<int32_t>(),
-                         s.d_desc.as<ReadDesc>(), read_list, d_stats, st),
-       "read order launch");
-  C2AArgs a;
+  HIPC(launch_chain_prep(ctx->opt, ctx->ref, db, win, a.srt, prog, d_stats, st), "chain_prep launch");
+  HIPC(launch_read_order(db, bins, a.counts + kHistOff, a.counts, desc, read_list, d_stats, st), "read order launch");
   a.read_list = read_list;
-  a.desc = s.d_desc.as<ReadDesc>();
-  a.counts = s.d_counts.as<int32_t>();
-  a.win = s.d_win.as<ChainWin>();
-  a.srt = s.d_srt.as<uint64_t>();
-  a.prog = s.d_prog.as<bwagpu_seed_t>();
+  a.desc = desc;
+  a.win = win;
+  a.prog = prog;
   a.out = d_out;
   a.out_n = d_n;
   a.stats = d_stats;
@@ -864,14 +791,17 @@ int bwagpu_chain2aln_submit(bwagpu_ctx_t* ctx, int slot, const bwagpu_batch_t* b
   L.make(*b);
   HIPC(s.h_in.ensure(L.total), "hipHostMalloc(in)");
   HIPC(s.d_in.ensure(L.total), "hipMalloc(in)");
-  HIPC(s.d_out.ensure(sizeof(bwagpu_alnreg_t) * (size_t)std::max(b->n_seeds, 1)), "hipMalloc(out)");
-  HIPC(s.d_n.ensure(sizeof(int32_t) * (size_t)std::max(b->n_reads, 1)), "hipMalloc(out_n)");
-  HIPC(s.d_stats.ensure(sizeof(int64_t) * ST_N), "hipMalloc(stats)");
-  HIPC(s.h_dense.ensure(sizeof(bwagpu_alnreg_t) * (size_t)std::max(b->n_seeds, 1)), "hipHostMalloc(out)");
-  HIPC(s.h_n.ensure(sizeof(int32_t) * (size_t)std::max(b->n_reads, 1)), "hipHostMalloc(out_n)");
-  HIPC(s.h_off.ensure(sizeof(int32_t) * (size_t)(b->n_reads + 1)), "hipHostMalloc(out_off)");
-  HIPC(s.d_off.ensure(sizeof(int32_t) * (size_t)(b->n_reads + 1)), "hipMalloc(out_off)");
-  HIPC(s.h_stats.ensure(sizeof(int64_t) * ST_N), "hipHostMalloc(stats)");
+  bwagpu_alnreg_t *d_out = nullptr, *h_dense = nullptr;
+  int32_t *d_n = nullptr, *h_n = nullptr, *h_off = nullptr, *d_off = nullptr;
+  int64_t *d_stats = nullptr, *h_stats = nullptr;
+  HIPC(s.d_out.get(d_out, (size_t)b->n_seeds), "hipMalloc(out)");
+  HIPC(s.d_n.get(d_n, (size_t)b->n_reads), "hipMalloc(out_n)");
+  HIPC(s.d_stats.get(d_stats, ST_N), "hipMalloc(stats)");
+  HIPC(s.h_dense.get(h_dense, (size_t)b->n_seeds), "hipHostMalloc(out)");
+  HIPC(s.h_n.get(h_n, (size_t)b->n_reads), "hipHostMalloc(out_n)");
+  HIPC(s.h_off.get(h_off, (size_t)b->n_reads + 1), "hipHostMalloc(out_off)");
+  HIPC(s.d_off.get(d_off, (size_t)b->n_reads + 1), "hipMalloc(out_off)");
+  HIPC(s.h_stats.get(h_stats, ST_N), "hipHostMalloc(stats)");
   s.slot_view = false;
   // stage into pinned memory so the caller's buffers are free on return —
   // unless the caller packed into that memory already (bwagpu_chain2aln_stage)
@@ -897,7 +827,7 @@ int bwagpu_chain2aln_submit(bwagpu_ctx_t* ctx, int slot, const bwagpu_batch_t* b
   HIPC(lazy_stream(s, &st), "hipStreamCreate");
   HIPC(hipEventRecord(s.ev0, st), "event");
   HIPC(hipMemcpyAsync(s.d_in.p, s.h_in.p, L.total, hipMemcpyHostToDevice, st), "H2D batch");
-  HIPC(hipMemsetAsync(s.d_stats.p, 0, sizeof(int64_t) * ST_N, st), "memset stats");
+  HIPC(hipMemsetAsync(d_stats, 0, sizeof(int64_t) * ST_N, st), "memset stats");
   char* d = s.d_in.as<char>();
   DevBatch db;
   db.n_reads = b->n_reads;
@@ -911,8 +841,7 @@ int bwagpu_chain2aln_submit(bwagpu_ctx_t* ctx, int slot, const bwagpu_batch_t* b
   db.chain_frac_rep = (const float*)(d + L.frac);
   db.seeds = (const bwagpu_seed_t*)(d + L.seeds);
   HIPC(hipEventRecord(s.ev1, st), "event");
-  rc = enqueue_chain2aln(ctx, s, db, lq_max, s.d_out.as<bwagpu_alnreg_t>(), s.d_n.as<int32_t>(),
-                         s.d_stats.as<int64_t>(), st);
+  rc = enqueue_chain2aln(ctx, s, db, lq_max, d_out, d_n, d_stats, st);
   if (rc) {
     // work already queued on the slot's stream may still read h_in / d_in:
     // drain it before the caller may reuse the slot
@@ -921,8 +850,7 @@ int bwagpu_chain2aln_submit(bwagpu_ctx_t* ctx, int slot, const bwagpu_batch_t* b
   }
   if (ctx->post_flags && b->n_reads) {  // bwagpu_set_regs_post: in place on the slot layout, before the dense copy
     rc = enqueue_regpost(ctx, ctx->post_opt, ctx->post_flags, ctx->post_id0, b->n_reads, db.seq_off, db.seq, nullptr,
-                         db.read_chain_off, db.chain_seed_off, s.d_out.as<bwagpu_alnreg_t>(), s.d_n.as<int32_t>(),
-                         s.d_stats.as<int64_t>(), st);
+                         db.read_chain_off, db.chain_seed_off, d_out, d_n, d_stats, st);
     if (rc) {
       (void)hipStreamSynchronize(st);
       return rc;
@@ -935,19 +863,16 @@ int bwagpu_chain2aln_submit(bwagpu_ctx_t* ctx, int slot, const bwagpu_batch_t* b
   // n_seeds slots the kernels fill)
   int32_t* h_off_dev = nullptr;
   bwagpu_alnreg_t* h_dense_dev = nullptr;
-  HIPC(hipHostGetDevicePointer((void**)&h_off_dev, s.h_off.p, 0), "hipHostGetDevicePointer");
-  HIPC(hipHostGetDevicePointer((void**)&h_dense_dev, s.h_dense.p, 0), "hipHostGetDevicePointer");
-  hipLaunchKernelGGL(dense_scan_kernel, dim3(1), dim3(kDenseScanBlock), 0, st, s.d_n.as<int32_t>(), b->n_reads,
-                     s.d_off.as<int32_t>(), h_off_dev);
+  HIPC(hipHostGetDevicePointer((void**)&h_off_dev, h_off, 0), "hipHostGetDevicePointer");
+  HIPC(hipHostGetDevicePointer((void**)&h_dense_dev, h_dense, 0), "hipHostGetDevicePointer");
+  hipLaunchKernelGGL(dense_scan_kernel, dim3(1), dim3(kDenseScanBlock), 0, st, d_n, b->n_reads, d_off, h_off_dev);
   if (b->n_reads)
-    hipLaunchKernelGGL(dense_copy_kernel, dim3((unsigned)((b->n_reads + 15) / 16)), dim3(256), 0, st,
-                       s.d_out.as<bwagpu_alnreg_t>(), s.d_n.as<int32_t>(), s.d_off.as<int32_t>(), db.read_chain_off,
-                       db.chain_seed_off, b->n_reads, h_dense_dev);
+    hipLaunchKernelGGL(dense_copy_kernel, dim3((unsigned)((b->n_reads + 15) / 16)), dim3(256), 0, st, d_out, d_n,
+                       d_off, db.read_chain_off, db.chain_seed_off, b->n_reads, h_dense_dev);
   HIPC(hipGetLastError(), "dense results launch");
   if (b->n_reads)
-    HIPC(hipMemcpyAsync(s.h_n.p, s.d_n.p, sizeof(int32_t) * (size_t)b->n_reads, hipMemcpyDeviceToHost, st),
-         "D2H counts");
-  HIPC(hipMemcpyAsync(s.h_stats.p, s.d_stats.p, sizeof(int64_t) * ST_N, hipMemcpyDeviceToHost, st), "D2H stats");
+    HIPC(hipMemcpyAsync(h_n, d_n, sizeof(int32_t) * (size_t)b->n_reads, hipMemcpyDeviceToHost, st), "D2H counts");
+  HIPC(hipMemcpyAsync(h_stats, d_stats, sizeof(int64_t) * ST_N, hipMemcpyDeviceToHost, st), "D2H stats");
   HIPC(hipEventRecord(s.ev3, st), "event");
   s.h2d = (int64_t)L.total;
   s.in_rco = L.rco;
@@ -1061,8 +986,9 @@ int bwagpu_chain2aln_results(bwagpu_ctx_t* ctx, int slot, const bwagpu_alnreg_t*
   if (s.busy) return fail(ctx, BWAGPU_E_INVAL, "slot's batch still in flight (wait first)");
   if (!s.has_results) return fail(ctx, BWAGPU_E_INVAL, "slot has no results");
   if (!s.slot_view) {  // the slot layout, built from the dense results once per batch
-    HIPC(s.h_out.ensure(sizeof(bwagpu_alnreg_t) * (size_t)std::max(s.n_seeds, 1)), "hipHostMalloc(out)");
-    if (s.n_seeds) expand_slots(s, s.h_out.as<bwagpu_alnreg_t>());
+    bwagpu_alnreg_t* h_out = nullptr;
+    HIPC(s.h_out.get(h_out, (size_t)s.n_seeds), "hipHostMalloc(out)");
+    if (s.n_seeds) expand_slots(s, h_out);
     s.slot_view = true;
   }
   *regs = s.h_out.as<const bwagpu_alnreg_t>();
@@ -1118,8 +1044,7 @@ int bwagpu_chain2aln_device(bwagpu_ctx_t* ctx, const bwagpu_batch_t* db_in, bwag
   db.seeds = db_in->seeds;
   int64_t* stats = dev_stats;
   if (!stats) {
-    HIPC(s.d_stats.ensure(sizeof(int64_t) * ST_N), "hipMalloc(stats)");
-    stats = s.d_stats.as<int64_t>();
+    HIPC(s.d_stats.get(stats, ST_N), "hipMalloc(stats)");
     HIPC(hipMemsetAsync(stats, 0, sizeof(int64_t) * ST_N, st), "memset stats");
   }
   return enqueue_chain2aln(ctx, s, db, lq_bound, dev_out, dev_n, stats, st);
@@ -1137,6 +1062,13 @@ int bwagpu_debug_fail_wait(bwagpu_ctx_t* ctx, int after_n_waits, int code) {
   if (!ctx || code <= 0) return BWAGPU_E_INVAL;
   ctx->fail_after = after_n_waits;
   ctx->fail_code = code;
+  return BWAGPU_OK;
+}
+
+int bwagpu_debug_live_buffers(int64_t* n, int64_t* bytes) {
+  if (!n || !bytes) return BWAGPU_E_INVAL;
+  *n = g_live_bufs.load(std::memory_order_relaxed);
+  *bytes = g_live_bytes.load(std::memory_order_relaxed);
   return BWAGPU_OK;
 }
 
@@ -1332,16 +1264,18 @@ extern "C" int bwagpu_set_bwt(bwagpu_ctx_t* ctx, const bwagpu_bwt_t* bwt) {
   ctx->bwt.seq_len = bwt->seq_len;
   ctx->bwt.bwt = ctx->bwt_words.as<uint32_t>();
   {  // the device occurrence layout (seed.hip: 64-position blocks)
-    HIPC(ctx->occ_d.ensure(2 * sizeof(uint4) * (size_t)occ64_blocks(bwt->seq_len)), "hipMalloc");
+    uint4* occ = nullptr;
+    uint64_t* sup = nullptr;
+    HIPC(ctx->occ_d.get(occ, 2 * (size_t)occ64_blocks(bwt->seq_len)), "hipMalloc");
     ctx->bwt.sup_shift = ctx->sup_shift;
-    HIPC(ctx->sup_d.ensure(4 * sizeof(uint64_t) * (size_t)occ64_supers(bwt->seq_len, ctx->sup_shift)), "hipMalloc");
-    HIPC(hipMemset(ctx->occ_d.p, 0, 2 * sizeof(uint4) * (size_t)occ64_blocks(bwt->seq_len)), "memset");
+    HIPC(ctx->sup_d.get(sup, 4 * (size_t)occ64_supers(bwt->seq_len, ctx->sup_shift)), "hipMalloc");
+    HIPC(hipMemset(occ, 0, 2 * sizeof(uint4) * (size_t)occ64_blocks(bwt->seq_len)), "memset");
     hipStream_t st = nullptr;
-  HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
-    HIPC(launch_build_occ64(ctx->bwt, ctx->occ_d.as<uint4>(), ctx->sup_d.as<uint64_t>(), st), "build_occ64 launch");
+    HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
+    HIPC(launch_build_occ64(ctx->bwt, occ, sup, st), "build_occ64 launch");
     HIPC(hipStreamSynchronize(st), "sync");
-    ctx->bwt.occ = ctx->occ_d.as<uint4>();
-    ctx->bwt.sup = ctx->sup_d.as<uint64_t>();
+    ctx->bwt.occ = occ;
+    ctx->bwt.sup = sup;
   }
   ctx->bwt.sa = nullptr;
   ctx->bwt.sa_mask = 0;
@@ -1352,9 +1286,10 @@ extern "C" int bwagpu_set_bwt(bwagpu_ctx_t* ctx, const bwagpu_bwt_t* bwt) {
     const int iv = bwt->sa_intv;
     if (iv < 1 || (iv & (iv - 1)) || bwt->n_sa < bwt->seq_len / (uint64_t)iv + 1)
       return fail(ctx, BWAGPU_E_INVAL, "suffix array sample interval / size inconsistent");
-    HIPC(ctx->sa_d.ensure(sizeof(uint64_t) * bwt->n_sa), "hipMalloc");
-    HIPC(hipMemcpy(ctx->sa_d.p, bwt->sa, sizeof(uint64_t) * bwt->n_sa, hipMemcpyHostToDevice), "H2D");
-    ctx->bwt.sa = ctx->sa_d.as<uint64_t>();
+    uint64_t* sa = nullptr;
+    HIPC(ctx->sa_d.get(sa, bwt->n_sa), "hipMalloc");
+    HIPC(hipMemcpy(sa, bwt->sa, sizeof(uint64_t) * bwt->n_sa, hipMemcpyHostToDevice), "H2D");
+    ctx->bwt.sa = sa;
     ctx->bwt.sa_mask = (uint64_t)iv - 1;
     while ((1 << ctx->bwt.sa_shift) < iv) ++ctx->bwt.sa_shift;
     // every row's entry in HBM (one load per bwt_sa instead of a walk of ~sa_intv
@@ -1392,11 +1327,12 @@ extern "C" int bwagpu_bwt_sa(bwagpu_ctx_t* ctx, int64_t n, const uint64_t* k, ui
   HIPC(hipSetDevice(ctx->device), "hipSetDevice");
   hipStream_t st = nullptr;
   HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
-  HIPC(ctx->sa_in.ensure(sizeof(uint64_t) * (size_t)n), "hipMalloc");
-  HIPC(ctx->sa_out.ensure(sizeof(uint64_t) * (size_t)n), "hipMalloc");
-  HIPC(hipMemcpyAsync(ctx->sa_in.p, k, sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, st), "H2D");
-  HIPC(launch_bwt_sa(ctx->bwt, n, ctx->sa_in.as<uint64_t>(), ctx->sa_out.as<uint64_t>(), st), "bwt_sa launch");
-  HIPC(hipMemcpyAsync(out, ctx->sa_out.p, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost, st), "D2H");
+  uint64_t *d_k = nullptr, *d_out = nullptr;
+  HIPC(ctx->sa_in.get(d_k, (size_t)n), "hipMalloc");
+  HIPC(ctx->sa_out.get(d_out, (size_t)n), "hipMalloc");
+  HIPC(hipMemcpyAsync(d_k, k, sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, st), "H2D");
+  HIPC(launch_bwt_sa(ctx->bwt, n, d_k, d_out, st), "bwt_sa launch");
+  HIPC(hipMemcpyAsync(out, d_out, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost, st), "D2H");
   HIPC(hipStreamSynchronize(st), "sync");
   return BWAGPU_OK;
 }
@@ -1486,11 +1422,12 @@ int seed_validate(bwagpu_ctx_t* ctx, const bwagpu_seedopt_t* opt, int32_t n_read
 int seed_enqueue(bwagpu_ctx_t* ctx, const bwagpu_seedopt_t* opt, int32_t n_reads, const int64_t* seq_off,
                  const uint8_t* seq, int64_t bases, int32_t max_per_read, bool upload, hipStream_t st, SeedArgs& a,
                  bool staged = false) {
-  HIPC(ctx->sd_off.ensure(sizeof(int64_t) * ((size_t)n_reads + 1)), "hipMalloc");
+  a = SeedArgs{};
+  HIPC(ctx->sd_off.get(a.seq_off, (size_t)n_reads + 1), "hipMalloc");
   HIPC(ctx->sd_seq.ensure((size_t)bases + 1), "hipMalloc");
-  HIPC(ctx->sd_out.ensure(sizeof(bwagpu_intv_t) * (size_t)n_reads * (size_t)max_per_read), "hipMalloc");
-  HIPC(ctx->sd_n.ensure(sizeof(int32_t) * (size_t)n_reads), "hipMalloc");
-  HIPC(ctx->sd_scratch.ensure(sizeof(bwagpu_intv_t) * (size_t)seed_scratch_entries(bases, n_reads)), "hipMalloc");
+  HIPC(ctx->sd_out.get(a.out, (size_t)n_reads * (size_t)max_per_read), "hipMalloc");
+  HIPC(ctx->sd_n.get(a.out_n, (size_t)n_reads), "hipMalloc");
+  HIPC(ctx->sd_scratch.get(a.scratch, (size_t)seed_scratch_entries(bases, n_reads)), "hipMalloc");
   if (upload) {  // through a pinned staging buffer filled on a few threads (a pageable H2D runs at a fraction)
     const size_t ob = sizeof(int64_t) * ((size_t)n_reads + 1);
     char* pin = ctx->sdh_in.as<char>();
@@ -1509,14 +1446,9 @@ int seed_enqueue(bwagpu_ctx_t* ctx, const bwagpu_seedopt_t* opt, int32_t n_reads
     if (bases) HIPC(hipMemcpyAsync(ctx->sd_seq.p, pin + ob, (size_t)bases, hipMemcpyHostToDevice, st), "H2D");
     HIPC(hipEventRecord(ctx->sdh_done, st), "hipEventRecord");
   }
-  a = SeedArgs{};
   a.n_reads = n_reads;
-  a.seq_off = ctx->sd_off.as<int64_t>();
   a.seq = ctx->sd_seq.as<uint8_t>();
   a.max_per_read = max_per_read;
-  a.out = ctx->sd_out.as<bwagpu_intv_t>();
-  a.out_n = ctx->sd_n.as<int32_t>();
-  a.scratch = ctx->sd_scratch.as<bwagpu_intv_t>();
   a.min_seed_len = opt->min_seed_len;
   a.split_width = opt->split_width;
   a.max_mem_intv = opt->max_mem_intv;
@@ -1528,9 +1460,8 @@ int seed_enqueue(bwagpu_ctx_t* ctx, const bwagpu_seedopt_t* opt, int32_t n_reads
   a.flags = a.heavy + n_reads;
   a.p3_n = a.flags + n_reads;
   if (getenv("BWAGPU_SEED_DBG")) {  // per-lane tier-1 stamps (tools_dev)
-    HIPC(ctx->sd_dbg.ensure(sizeof(int64_t) * 8 * (size_t)n_reads), "hipMalloc");
-    HIPC(hipMemsetAsync(ctx->sd_dbg.p, 0, sizeof(int64_t) * 8 * (size_t)n_reads, st), "memset");
-    a.dbg = ctx->sd_dbg.as<int64_t>();
+    HIPC(ctx->sd_dbg.get(a.dbg, 8 * (size_t)n_reads), "hipMalloc");
+    HIPC(hipMemsetAsync(a.dbg, 0, sizeof(int64_t) * 8 * (size_t)n_reads, st), "memset");
   }
   HIPC(launch_collect_intv(ctx->bwt, a, st), "collect_intv launch");
   return BWAGPU_OK;
@@ -1572,11 +1503,13 @@ extern "C" int bwagpu_collect_intv(bwagpu_ctx_t* ctx, const bwagpu_seedopt_t* op
   const int64_t total = off[(size_t)n_reads];
   if (total > out_cap) return fail(ctx, BWAGPU_E_UNSUPPORTED, "the batch has more than out_cap intervals");
   if (total == 0) return BWAGPU_OK;
-  HIPC(ctx->sd_poff.ensure(sizeof(int64_t) * off.size()), "hipMalloc");
-  HIPC(ctx->sd_pack.ensure(sizeof(bwagpu_intv_t) * (size_t)total), "hipMalloc");
-  HIPC(hipMemcpyAsync(ctx->sd_poff.p, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice, st), "H2D");
-  HIPC(launch_pack_intv(a, ctx->sd_poff.as<int64_t>(), ctx->sd_pack.as<bwagpu_intv_t>(), st), "pack launch");
-  HIPC(hipMemcpyAsync(out, ctx->sd_pack.p, sizeof(bwagpu_intv_t) * (size_t)total, hipMemcpyDeviceToHost, st), "D2H");
+  int64_t* d_off = nullptr;
+  bwagpu_intv_t* d_pack = nullptr;
+  HIPC(ctx->sd_poff.get(d_off, off.size()), "hipMalloc");
+  HIPC(ctx->sd_pack.get(d_pack, (size_t)total), "hipMalloc");
+  HIPC(hipMemcpyAsync(d_off, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice, st), "H2D");
+  HIPC(launch_pack_intv(a, d_off, d_pack, st), "pack launch");
+  HIPC(hipMemcpyAsync(out, d_pack, sizeof(bwagpu_intv_t) * (size_t)total, hipMemcpyDeviceToHost, st), "D2H");
   HIPC(hipStreamSynchronize(st), "sync");
   return BWAGPU_OK;
 }
@@ -1648,18 +1581,18 @@ int run_chaining(bwagpu_ctx_t* ctx, const bwagpu_seedopt_t* sopt, const bwagpu_c
   SeedArgs sa;
   if ((rc = seed_enqueue(ctx, sopt, n_reads, seq_off, seq, bases, mpr, true, st, sa, true))) return rc;
   const size_t nr = (size_t)n_reads;
-  HIPC(ctx->ch_npos.ensure(sizeof(int32_t) * nr), "hipMalloc");
-  HIPC(ctx->ch_posoff.ensure(sizeof(int64_t) * (nr + 1)), "hipMalloc");
-  HIPC(ctx->ch_frac.ensure(sizeof(float) * nr), "hipMalloc");
-  HIPC(ctx->ch_nout.ensure(sizeof(int32_t) * nr), "hipMalloc");
-  HIPC(ctx->ch_noseed.ensure(sizeof(int32_t) * nr), "hipMalloc");
-  HIPC(ctx->ch_nsw.ensure(sizeof(int32_t) * nr), "hipMalloc");
-  HIPC(ctx->ch_need.ensure(sizeof(int32_t)), "hipMalloc");
-  HIPC(ctx->ch_swtab.ensure(sizeof(int32_t) * tab.size()), "hipMalloc");
-  HIPC(ctx->chh_tot.ensure(sizeof(int64_t) * 8), "hipHostMalloc");
-  HIPC(hipMemcpyAsync(ctx->ch_swtab.p, tab.data(), sizeof(int32_t) * tab.size(), hipMemcpyHostToDevice, st), "H2D");
-  int64_t* tot = ctx->chh_tot.as<int64_t>();
   ChainArgs a{};
+  int64_t* tot = nullptr;
+  HIPC(ctx->ch_npos.get(a.n_pos, nr), "hipMalloc");
+  HIPC(ctx->ch_posoff.get(a.pos_off, nr + 1), "hipMalloc");
+  HIPC(ctx->ch_frac.get(a.frac_rep, nr), "hipMalloc");
+  HIPC(ctx->ch_nout.get(a.n_out, nr), "hipMalloc");
+  HIPC(ctx->ch_noseed.get(a.n_oseed, nr), "hipMalloc");
+  HIPC(ctx->ch_nsw.get(a.n_sw, nr), "hipMalloc");
+  HIPC(ctx->ch_need.get(a.need, 1), "hipMalloc");
+  HIPC(ctx->ch_swtab.get(a.sw_tab, tab.size()), "hipMalloc");
+  HIPC(ctx->chh_tot.get(tot, 8), "hipHostMalloc");
+  HIPC(hipMemcpyAsync(ctx->ch_swtab.p, tab.data(), sizeof(int32_t) * tab.size(), hipMemcpyHostToDevice, st), "H2D");
   a.n_reads = n_reads;
   a.seq_off = sa.seq_off;
   a.seq = sa.seq;
@@ -1679,14 +1612,6 @@ int run_chaining(bwagpu_ctx_t* ctx, const bwagpu_seedopt_t* sopt, const bwagpu_c
   a.ann_len = ctx->ref.ann_len;
   a.is_alt = ctx->has_alt ? ctx->ch_alt.as<uint8_t>() : nullptr;
   a.pac = ctx->ref.pac;
-  a.sw_tab = ctx->ch_swtab.as<int32_t>();
-  a.n_pos = ctx->ch_npos.as<int32_t>();
-  a.pos_off = ctx->ch_posoff.as<int64_t>();
-  a.frac_rep = ctx->ch_frac.as<float>();
-  a.n_out = ctx->ch_nout.as<int32_t>();
-  a.n_oseed = ctx->ch_noseed.as<int32_t>();
-  a.n_sw = ctx->ch_nsw.as<int32_t>();
-  a.need = ctx->ch_need.as<int32_t>();
   for (int pass = 0;; ++pass) {  // positions per read; a read out of interval slots reruns the search
     a.intv = sa.out;
     a.intv_n = sa.out_n;
@@ -1703,30 +1628,19 @@ int run_chaining(bwagpu_ctx_t* ctx, const bwagpu_seedopt_t* sopt, const bwagpu_c
     if ((rc = seed_enqueue(ctx, sopt, n_reads, seq_off, seq, bases, need, false, st, sa))) return rc;
   }
   const int64_t P = tot[0];
-  const size_t p1 = (size_t)std::max<int64_t>(P, 1);
-  HIPC(ctx->ch_kpos.ensure(sizeof(uint64_t) * p1), "hipMalloc");
-  HIPC(ctx->ch_rbeg.ensure(sizeof(uint64_t) * p1), "hipMalloc");
-  HIPC(ctx->ch_qinfo.ensure(sizeof(int2) * p1), "hipMalloc");
-  HIPC(ctx->ch_label.ensure(sizeof(int32_t) * p1), "hipMalloc");
-  HIPC(ctx->ch_score.ensure(sizeof(int32_t) * p1), "hipMalloc");
-  HIPC(ctx->ch_slist.ensure(sizeof(int32_t) * p1), "hipMalloc");
-  HIPC(ctx->ch_ord.ensure(sizeof(int32_t) * p1), "hipMalloc");
-  HIPC(ctx->ch_chains.ensure(sizeof(LChain) * p1), "hipMalloc");
-  HIPC(ctx->ch_nodes.ensure(sizeof(BNode32) * (size_t)node_total(P, n_reads)), "hipMalloc");
-  HIPC(ctx->ch_ochains.ensure(sizeof(DChain) * p1), "hipMalloc");
-  HIPC(ctx->ch_oslist.ensure(sizeof(int32_t) * p1), "hipMalloc");
+  const size_t np = (size_t)P;
+  HIPC(ctx->ch_kpos.get(a.kpos, np), "hipMalloc");
+  HIPC(ctx->ch_rbeg.get(a.rbeg, np), "hipMalloc");
+  HIPC(ctx->ch_qinfo.get(a.qinfo, np), "hipMalloc");
+  HIPC(ctx->ch_label.get(a.label, np), "hipMalloc");
+  HIPC(ctx->ch_score.get(a.score, np), "hipMalloc");
+  HIPC(ctx->ch_slist.get(a.slist, np), "hipMalloc");
+  HIPC(ctx->ch_ord.get(a.ord, np), "hipMalloc");
+  HIPC(ctx->ch_chains.get(a.lchains, np), "hipMalloc");
+  HIPC(ctx->ch_nodes.get(a.lnodes, (size_t)node_total(P, n_reads)), "hipMalloc");
+  HIPC(ctx->ch_ochains.get(a.ochains, np), "hipMalloc");
+  HIPC(ctx->ch_oslist.get(a.oslist, np), "hipMalloc");
   HIPC(ctx->ch_bins.ensure(sizeof(int32_t) * ((size_t)(kLdsBins + 1) * nr + kLdsBins + 1)), "hipMalloc");
-  a.kpos = ctx->ch_kpos.as<uint64_t>();
-  a.rbeg = ctx->ch_rbeg.as<uint64_t>();
-  a.qinfo = ctx->ch_qinfo.as<int2>();
-  a.label = ctx->ch_label.as<int32_t>();
-  a.score = ctx->ch_score.as<int32_t>();
-  a.slist = ctx->ch_slist.as<int32_t>();
-  a.ord = ctx->ch_ord.as<int32_t>();
-  a.lchains = ctx->ch_chains.as<LChain>();
-  a.lnodes = ctx->ch_nodes.as<BNode32>();
-  a.ochains = ctx->ch_ochains.as<DChain>();
-  a.oslist = ctx->ch_oslist.as<int32_t>();
   a.bin_count = ctx->ch_bins.as<int32_t>();
   a.bin_list = a.bin_count + kLdsBins + 1;
   HIPC(launch_chain_emit(a, st), "chain_emit launch");
@@ -1739,9 +1653,8 @@ int run_chaining(bwagpu_ctx_t* ctx, const bwagpu_seedopt_t* sopt, const bwagpu_c
   const char* dbg_env = getenv("BWAGPU_CHAIN_PHASES");
   const bool dbg_on = dbg_env && dbg_env[0] == '1';
   if (dbg_on) {
-    HIPC(ctx->ch_dbg.ensure(sizeof(uint64_t) * 8 * nr), "hipMalloc");
-    HIPC(hipMemsetAsync(ctx->ch_dbg.p, 0, sizeof(uint64_t) * 8 * nr, st), "memset");
-    a.dbg = ctx->ch_dbg.as<uint64_t>();
+    HIPC(ctx->ch_dbg.get(a.dbg, 8 * nr), "hipMalloc");
+    HIPC(hipMemsetAsync(a.dbg, 0, sizeof(uint64_t) * 8 * nr, st), "memset");
   }
   HIPC(launch_chain_build(a, st, ctx->ch_cs), "chain_build launch");
   if (dbg_on) {  // the slowest reads' phase times (100 MHz ticks) to stderr
@@ -1763,53 +1676,52 @@ int run_chaining(bwagpu_ctx_t* ctx, const bwagpu_seedopt_t* sopt, const bwagpu_c
     }
   }
   if (!raw && any_sw) {  // mem_flt_chained_seeds: every kept seed of a long read realigned
-    HIPC(ctx->ch_swoff.ensure(sizeof(int64_t) * (nr + 1)), "hipMalloc");
-    HIPC(launch_scan_i32(a.n_sw, ctx->ch_swoff.as<int64_t>(), n_reads, st), "scan launch");
-    HIPC(hipMemcpyAsync(tot + 2, ctx->ch_swoff.as<int64_t>() + n_reads, sizeof(int64_t), hipMemcpyDeviceToHost, st),
-         "D2H");
+    int64_t* sw_off = nullptr;
+    HIPC(ctx->ch_swoff.get(sw_off, nr + 1), "hipMalloc");
+    HIPC(launch_scan_i32(a.n_sw, sw_off, n_reads, st), "scan launch");
+    HIPC(hipMemcpyAsync(tot + 2, sw_off + n_reads, sizeof(int64_t), hipMemcpyDeviceToHost, st), "D2H");
     HIPC(hipStreamSynchronize(st), "sync");
     const int64_t T = tot[2];
     if (T > INT32_MAX / 2) return fail(ctx, BWAGPU_E_UNSUPPORTED, "too many seeds to realign");
     if (T) {
-      HIPC(ctx->ch_swtasks.ensure(sizeof(bwagpu_align2_task_t) * (size_t)T), "hipMalloc");
-      HIPC(ctx->ch_swt.ensure((size_t)kSwWin * (size_t)T), "hipMalloc");
-      HIPC(ctx->ch_swskip.ensure(sizeof(int32_t) * (size_t)T), "hipMalloc");
-      HIPC(ctx->ch_swres.ensure(sizeof(bwagpu_kswr_t) * (size_t)T), "hipMalloc");
+      ChainSw sw{};
+      bwagpu_kswr_t* res = nullptr;
+      sw.sw_off = sw_off;
+      HIPC(ctx->ch_swtasks.get(sw.tasks, (size_t)T), "hipMalloc");
+      HIPC(ctx->ch_swt.get(sw.tpool, (size_t)kSwWin * (size_t)T), "hipMalloc");
+      HIPC(ctx->ch_swskip.get(sw.skip, (size_t)T), "hipMalloc");
+      HIPC(ctx->ch_swres.get(res, (size_t)T), "hipMalloc");
       HIPC(ctx->ch_swscr.ensure(8 * ((size_t)kSwWin * (size_t)T + (size_t)T)), "hipMalloc");
-      ChainSw sw{ctx->ch_swoff.as<int64_t>(), ctx->ch_swtasks.as<bwagpu_align2_task_t>(), ctx->ch_swt.as<uint8_t>(),
-                 ctx->ch_swskip.as<int32_t>(), ctx->ch_swres.as<bwagpu_kswr_t>()};
+      sw.res = res;
       HIPC(launch_chain_sw_prep(a, sw, st), "chain_sw_prep launch");
-      if ((rc = bwagpu_align2_device(ctx, (int32_t)T, sw.tasks, sa.seq, sw.tpool, ctx->ch_swres.as<bwagpu_kswr_t>(),
-                                     ctx->ch_swscr.p, st)))
-        return rc;
+      if ((rc = bwagpu_align2_device(ctx, (int32_t)T, sw.tasks, sa.seq, sw.tpool, res, ctx->ch_swscr.p, st))) return rc;
       HIPC(launch_chain_sw_apply(a, sw, st), "chain_sw_apply launch");
     }
   }
-  HIPC(ctx->ch_ocoff.ensure(sizeof(int64_t) * (nr + 1)), "hipMalloc");
-  HIPC(ctx->ch_osoff.ensure(sizeof(int64_t) * (nr + 1)), "hipMalloc");
-  HIPC(launch_scan_i32(a.n_out, ctx->ch_ocoff.as<int64_t>(), n_reads, st), "scan launch");
-  HIPC(launch_scan_i32(a.n_oseed, ctx->ch_osoff.as<int64_t>(), n_reads, st), "scan launch");
-  HIPC(hipMemcpyAsync(tot + 3, ctx->ch_ocoff.as<int64_t>() + n_reads, sizeof(int64_t), hipMemcpyDeviceToHost, st),
-       "D2H");
-  HIPC(hipMemcpyAsync(tot + 4, ctx->ch_osoff.as<int64_t>() + n_reads, sizeof(int64_t), hipMemcpyDeviceToHost, st),
-       "D2H");
+  int64_t *oc_off = nullptr, *os_off = nullptr;
+  HIPC(ctx->ch_ocoff.get(oc_off, nr + 1), "hipMalloc");
+  HIPC(ctx->ch_osoff.get(os_off, nr + 1), "hipMalloc");
+  HIPC(launch_scan_i32(a.n_out, oc_off, n_reads, st), "scan launch");
+  HIPC(launch_scan_i32(a.n_oseed, os_off, n_reads, st), "scan launch");
+  HIPC(hipMemcpyAsync(tot + 3, oc_off + n_reads, sizeof(int64_t), hipMemcpyDeviceToHost, st), "D2H");
+  HIPC(hipMemcpyAsync(tot + 4, os_off + n_reads, sizeof(int64_t), hipMemcpyDeviceToHost, st), "D2H");
   HIPC(hipStreamSynchronize(st), "sync");
   const int64_t nc = tot[3], ns = tot[4];
   if (nc > INT32_MAX - 1 || ns > INT32_MAX - 1) return fail(ctx, BWAGPU_E_UNSUPPORTED, "batch has too many chains");
-  HIPC(ctx->ch_rco.ensure(sizeof(int32_t) * (nr + 1)), "hipMalloc");
-  HIPC(ctx->ch_cso.ensure(sizeof(int32_t) * ((size_t)nc + 1)), "hipMalloc");
-  HIPC(ctx->ch_rid.ensure(sizeof(int32_t) * (size_t)std::max<int64_t>(nc, 1)), "hipMalloc");
-  HIPC(ctx->ch_cfrac.ensure(sizeof(float) * (size_t)std::max<int64_t>(nc, 1)), "hipMalloc");
-  HIPC(ctx->ch_out.ensure(sizeof(bwagpu_chain_t) * (size_t)std::max<int64_t>(nc, 1)), "hipMalloc");
-  HIPC(ctx->ch_seeds.ensure(sizeof(bwagpu_seed_t) * (size_t)std::max<int64_t>(ns, 1)), "hipMalloc");
-  ChainPack pk{ctx->ch_ocoff.as<int64_t>(), ctx->ch_osoff.as<int64_t>(), ctx->ch_rco.as<int32_t>(),
-               ctx->ch_cso.as<int32_t>(), ctx->ch_rid.as<int32_t>(), ctx->ch_cfrac.as<float>(),
-               ctx->ch_out.as<bwagpu_chain_t>(), ctx->ch_seeds.as<bwagpu_seed_t>()};
+  ChainPack pk{};
+  pk.oc_off = oc_off;
+  pk.os_off = os_off;
+  HIPC(ctx->ch_rco.get(pk.read_chain_off, nr + 1), "hipMalloc");
+  HIPC(ctx->ch_cso.get(pk.chain_seed_off, (size_t)nc + 1), "hipMalloc");
+  HIPC(ctx->ch_rid.get(pk.chain_rid, (size_t)nc), "hipMalloc");
+  HIPC(ctx->ch_cfrac.get(pk.chain_frac, (size_t)nc), "hipMalloc");
+  HIPC(ctx->ch_out.get(pk.chains, (size_t)nc), "hipMalloc");
+  HIPC(ctx->ch_seeds.get(pk.seeds, (size_t)ns), "hipMalloc");
   if (to_host) {  // bwagpu_seqs2chains: the chains written over PCIe into its pinned results (no D2H step)
-    HIPC(ctx->chh_rco.ensure(sizeof(int32_t) * (nr + 1)), "hipHostMalloc");
-    HIPC(ctx->chh_cso.ensure(sizeof(int32_t) * ((size_t)nc + 1)), "hipHostMalloc");
-    HIPC(ctx->chh_chains.ensure(sizeof(bwagpu_chain_t) * (size_t)std::max<int64_t>(nc, 1)), "hipHostMalloc");
-    HIPC(ctx->chh_seeds.ensure(sizeof(bwagpu_seed_t) * (size_t)std::max<int64_t>(ns, 1)), "hipHostMalloc");
+    HIPC(ctx->chh_rco.get(pk.read_chain_off, nr + 1), "hipHostMalloc");  // the host's pointers, replaced below
+    HIPC(ctx->chh_cso.get(pk.chain_seed_off, (size_t)nc + 1), "hipHostMalloc");
+    HIPC(ctx->chh_chains.get(pk.chains, (size_t)nc), "hipHostMalloc");
+    HIPC(ctx->chh_seeds.get(pk.seeds, (size_t)ns), "hipHostMalloc");
     HIPC(hipHostGetDevicePointer((void**)&pk.read_chain_off, ctx->chh_rco.p, 0), "hipHostGetDevicePointer");
     HIPC(hipHostGetDevicePointer((void**)&pk.chain_seed_off, ctx->chh_cso.p, 0), "hipHostGetDevicePointer");
     HIPC(hipHostGetDevicePointer((void**)&pk.chains, ctx->chh_chains.p, 0), "hipHostGetDevicePointer");
@@ -1830,8 +1742,9 @@ extern "C" int bwagpu_set_alt(bwagpu_ctx_t* ctx, const uint8_t* is_alt) {
     return BWAGPU_OK;
   }
   HIPC(hipSetDevice(ctx->device), "hipSetDevice");
-  HIPC(ctx->ch_alt.ensure((size_t)std::max(ctx->ref.n_seqs, 1)), "hipMalloc");
-  HIPC(hipMemcpy(ctx->ch_alt.p, is_alt, (size_t)ctx->ref.n_seqs, hipMemcpyHostToDevice), "H2D");
+  uint8_t* alt = nullptr;
+  HIPC(ctx->ch_alt.get(alt, (size_t)ctx->ref.n_seqs), "hipMalloc");
+  HIPC(hipMemcpy(alt, is_alt, (size_t)ctx->ref.n_seqs, hipMemcpyHostToDevice), "H2D");
   ctx->has_alt = true;
   return BWAGPU_OK;
 }
@@ -1848,23 +1761,16 @@ extern "C" int bwagpu_seqs2chains(bwagpu_ctx_t* ctx, const bwagpu_seedopt_t* sop
   int rc = run_chaining(ctx, sopt, copt, n_reads, seq_off, seq, raw != 0, st, &nc, &ns, &lq, true);
   if (rc) return rc;
   const size_t nr = (size_t)n_reads;
-  HIPC(ctx->chh_rco.ensure(sizeof(int32_t) * (nr + 1)), "hipHostMalloc");
-  HIPC(ctx->chh_cso.ensure(sizeof(int32_t) * ((size_t)nc + 1)), "hipHostMalloc");
-  HIPC(ctx->chh_chains.ensure(sizeof(bwagpu_chain_t) * (size_t)std::max<int64_t>(nc, 1)), "hipHostMalloc");
-  HIPC(ctx->chh_seeds.ensure(sizeof(bwagpu_seed_t) * (size_t)std::max<int64_t>(ns, 1)), "hipHostMalloc");
-  if (n_reads) {
-    HIPC(hipStreamSynchronize(st), "sync");  // chain_pack wrote the results into the pinned buffers
-  } else {
-    ctx->chh_rco.as<int32_t>()[0] = 0;
-    ctx->chh_cso.as<int32_t>()[0] = 0;
-  }
-  out->n_reads = n_reads;
-  out->n_chains = (int32_t)nc;
-  out->n_seeds = ns;
-  out->read_chain_off = ctx->chh_rco.as<int32_t>();
-  out->chain_seed_off = ctx->chh_cso.as<int32_t>();
-  out->chains = ctx->chh_chains.as<bwagpu_chain_t>();
-  out->seeds = ctx->chh_seeds.as<bwagpu_seed_t>();
+  int32_t *rco = nullptr, *cso = nullptr;
+  bwagpu_chain_t* chains = nullptr;
+  bwagpu_seed_t* seeds = nullptr;
+  HIPC(ctx->chh_rco.get(rco, nr + 1), "hipHostMalloc");
+  HIPC(ctx->chh_cso.get(cso, (size_t)nc + 1), "hipHostMalloc");
+  HIPC(ctx->chh_chains.get(chains, (size_t)nc), "hipHostMalloc");
+  HIPC(ctx->chh_seeds.get(seeds, (size_t)ns), "hipHostMalloc");
+  if (n_reads) HIPC(hipStreamSynchronize(st), "sync");  // chain_pack wrote the results into the pinned buffers
+  else rco[0] = cso[0] = 0;
+  *out = bwagpu_chains_t{n_reads, (int32_t)nc, ns, rco, cso, chains, seeds};
   return BWAGPU_OK;
 }
 
@@ -1888,10 +1794,13 @@ extern "C" int bwagpu_seqs2regions(bwagpu_ctx_t* ctx, const bwagpu_seedopt_t* so
   if ((rc = check_lds(ctx, lq))) return rc;
   Slot& s = ctx->ch_slot;
   const size_t nr = (size_t)n_reads;
-  HIPC(s.d_out.ensure(sizeof(bwagpu_alnreg_t) * (size_t)std::max<int64_t>(ns, 1)), "hipMalloc(out)");
-  HIPC(s.d_n.ensure(sizeof(int32_t) * nr), "hipMalloc(out_n)");
-  HIPC(s.d_stats.ensure(sizeof(int64_t) * ST_N), "hipMalloc(stats)");
-  HIPC(hipMemsetAsync(s.d_stats.p, 0, sizeof(int64_t) * ST_N, st), "memset stats");
+  bwagpu_alnreg_t *d_out = nullptr, *d_regc = nullptr, *h_regs = nullptr;
+  int32_t* d_n = nullptr;
+  int64_t *d_stats = nullptr, *d_regoff = nullptr;
+  HIPC(s.d_out.get(d_out, (size_t)ns), "hipMalloc(out)");
+  HIPC(s.d_n.get(d_n, nr), "hipMalloc(out_n)");
+  HIPC(s.d_stats.get(d_stats, ST_N), "hipMalloc(stats)");
+  HIPC(hipMemsetAsync(d_stats, 0, sizeof(int64_t) * ST_N, st), "memset stats");
   DevBatch db;
   db.n_reads = n_reads;
   db.n_chains = (int32_t)nc;
@@ -1903,36 +1812,28 @@ extern "C" int bwagpu_seqs2regions(bwagpu_ctx_t* ctx, const bwagpu_seedopt_t* so
   db.chain_rid = ctx->ch_rid.as<int32_t>();
   db.chain_frac_rep = ctx->ch_cfrac.as<float>();
   db.seeds = ctx->ch_seeds.as<bwagpu_seed_t>();
-  if ((rc = enqueue_chain2aln(ctx, s, db, lq, s.d_out.as<bwagpu_alnreg_t>(), s.d_n.as<int32_t>(),
-                              s.d_stats.as<int64_t>(), st)))
-    return rc;
+  if ((rc = enqueue_chain2aln(ctx, s, db, lq, d_out, d_n, d_stats, st))) return rc;
   if (ctx->post_flags) {  // bwagpu_set_regs_post: before the counts are scanned and the regions compacted
     if ((rc = enqueue_regpost(ctx, ctx->post_opt, ctx->post_flags, ctx->post_id0, n_reads, db.seq_off, db.seq, nullptr,
-                              db.read_chain_off, db.chain_seed_off, s.d_out.as<bwagpu_alnreg_t>(),
-                              s.d_n.as<int32_t>(), s.d_stats.as<int64_t>(), st)))
+                              db.read_chain_off, db.chain_seed_off, d_out, d_n, d_stats, st)))
       return rc;
     ctx->post_id0 += n_reads;
   }
-  HIPC(ctx->ch_regoff.ensure(sizeof(int64_t) * (nr + 1)), "hipMalloc");
-  HIPC(launch_scan_i32(s.d_n.as<int32_t>(), ctx->ch_regoff.as<int64_t>(), n_reads, st), "scan launch");
+  HIPC(ctx->ch_regoff.get(d_regoff, nr + 1), "hipMalloc");
+  HIPC(launch_scan_i32(d_n, d_regoff, n_reads, st), "scan launch");
   int64_t* tot = ctx->chh_tot.as<int64_t>();
-  HIPC(hipMemcpyAsync(tot + 5, ctx->ch_regoff.as<int64_t>() + n_reads, sizeof(int64_t), hipMemcpyDeviceToHost, st),
-       "D2H");
-  HIPC(hipMemcpyAsync(tot + 6, s.d_stats.as<int64_t>() + ST_ERR, sizeof(int64_t), hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipMemcpyAsync(out_n, s.d_n.p, sizeof(int32_t) * nr, hipMemcpyDeviceToHost, st), "D2H");
+  HIPC(hipMemcpyAsync(tot + 5, d_regoff + n_reads, sizeof(int64_t), hipMemcpyDeviceToHost, st), "D2H");
+  HIPC(hipMemcpyAsync(tot + 6, d_stats + ST_ERR, sizeof(int64_t), hipMemcpyDeviceToHost, st), "D2H");
+  HIPC(hipMemcpyAsync(out_n, d_n, sizeof(int32_t) * nr, hipMemcpyDeviceToHost, st), "D2H");
   HIPC(hipStreamSynchronize(st), "sync");
   const int64_t nreg = tot[5];
-  HIPC(ctx->ch_regc.ensure(sizeof(bwagpu_alnreg_t) * (size_t)std::max<int64_t>(nreg, 1)), "hipMalloc");
-  HIPC(ctx->chh_regs.ensure(sizeof(bwagpu_alnreg_t) * (size_t)std::max<int64_t>(nreg, 1)), "hipHostMalloc");
-  HIPC(launch_reg_compact(n_reads, db.read_chain_off, db.chain_seed_off, s.d_out.as<bwagpu_alnreg_t>(),
-                          ctx->ch_regoff.as<int64_t>(), ctx->ch_regc.as<bwagpu_alnreg_t>(), st),
+  HIPC(ctx->ch_regc.get(d_regc, (size_t)nreg), "hipMalloc");
+  HIPC(ctx->chh_regs.get(h_regs, (size_t)nreg), "hipHostMalloc");
+  HIPC(launch_reg_compact(n_reads, db.read_chain_off, db.chain_seed_off, d_out, d_regoff, d_regc, st),
        "reg_compact launch");
-  if (nreg)
-    HIPC(hipMemcpyAsync(ctx->chh_regs.p, ctx->ch_regc.p, sizeof(bwagpu_alnreg_t) * (size_t)nreg, hipMemcpyDeviceToHost,
-                        st),
-         "D2H");
+  if (nreg) HIPC(hipMemcpyAsync(h_regs, d_regc, sizeof(bwagpu_alnreg_t) * (size_t)nreg, hipMemcpyDeviceToHost, st), "D2H");
   HIPC(hipStreamSynchronize(st), "sync");
-  *regs = ctx->chh_regs.as<const bwagpu_alnreg_t>();
+  *regs = h_regs;
   *n_regs = nreg;
   if (tot[6] & ERR_LEN) return fail(ctx, BWAGPU_E_UNSUPPORTED, "read longer than BWAGPU_MAX_READ_LEN");
   if (tot[6] & ERR_POST) return fail(ctx, BWAGPU_E_UNSUPPORTED, "a patch candidate's window exceeds 4096 bases");

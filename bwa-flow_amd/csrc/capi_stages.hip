@@ -88,17 +88,18 @@ extern "C" int bwagpu_regs_post(bwagpu_ctx_t* ctx, const bwagpu_postopt_t* popt,
   TRY(hc.begin());
   TRY(hc.up_spans(plan, nr, reg_off, regs, n));
   TRY(hc.up_seq(plan, nr, seq_off, seq));
-  HIPC(ctx->rp_stats.ensure(sizeof(int64_t) * ST_N), "hipMalloc");
-  HIPC(hipMemsetAsync(ctx->rp_stats.p, 0, sizeof(int64_t) * ST_N, hc.st), "memset");
+  int64_t* d_stats = nullptr;
+  HIPC(ctx->rp_stats.get(d_stats, ST_N), "hipMalloc");
+  HIPC(hipMemsetAsync(d_stats, 0, sizeof(int64_t) * ST_N, hc.st), "memset");
   TRY(hc.uploaded());
   TRY(hc.start());
   TRY(enqueue_regpost(ctx, *popt, flags, id0, n_reads, g.seq_off.as<int64_t>(), g.seq.as<uint8_t>(),
                       g.reg_off.as<int64_t>(), nullptr, nullptr, g.regs.as<bwagpu_alnreg_t>(), g.n.as<int32_t>(),
-                      ctx->rp_stats.as<int64_t>(), hc.st));
+                      d_stats, hc.st));
   TRY(hc.stop());
   TRY(hc.down(regs + plan.lo, g.regs, sizeof(bwagpu_alnreg_t) * span));
   TRY(hc.down(n, g.n, sizeof(int32_t) * nr));
-  HIPC(hipMemcpyAsync(hst, ctx->rp_stats.p, sizeof(hst), hipMemcpyDeviceToHost, hc.st), "D2H");
+  HIPC(hipMemcpyAsync(hst, d_stats, sizeof(hst), hipMemcpyDeviceToHost, hc.st), "D2H");
   TRY(hc.finish("regpost execution"));
   ctx->slot[0].last.ext_calls = hst[ST_CALLS];
   if (hst[ST_ERR] & ERR_POST) return fail(ctx, BWAGPU_E_UNSUPPORTED, "a patch candidate's window exceeds 4096 bases");
@@ -119,11 +120,9 @@ int enqueue_pestat(bwagpu_ctx_t* ctx, const bwagpu_pairopt_t& po, int32_t n_read
   a.reg_off = reg_off;
   a.regs = regs;
   a.n = n;
-  HIPC(ctx->pe_isize.ensure(sizeof(uint64_t) * 4 * (size_t)a.cap), "hipMalloc");
-  HIPC(ctx->pe_cnt.ensure(sizeof(int32_t) * 4), "hipMalloc");
-  HIPC(hipMemsetAsync(ctx->pe_cnt.p, 0, sizeof(int32_t) * 4, st), "memset");
-  a.isize = ctx->pe_isize.as<uint64_t>();
-  a.cnt = ctx->pe_cnt.as<int32_t>();
+  HIPC(ctx->pe_isize.get(a.isize, 4 * (size_t)a.cap), "hipMalloc");
+  HIPC(ctx->pe_cnt.get(a.cnt, 4), "hipMalloc");
+  HIPC(hipMemsetAsync(a.cnt, 0, sizeof(int32_t) * 4, st), "memset");
   a.pes = pes;
   HIPC(launch_pestat(ctx->opt, ctx->ref, a, st), "pestat launch");
   return BWAGPU_OK;
@@ -159,35 +158,33 @@ int enqueue_rescue(bwagpu_ctx_t* ctx, const bwagpu_pairopt_t& po, const bwagpu_p
   a.n_sw = n_sw;
   // per pair: pstate | nb0 | nslot | ntask | tbytes
   HIPC(ctx->rs_pair.ensure(sizeof(int32_t) * 5 * npz), "hipMalloc");
-  HIPC(ctx->rs_soff.ensure(sizeof(int64_t) * (npz + 1)), "hipMalloc");
-  HIPC(ctx->rs_toff.ensure(sizeof(int64_t) * (npz + 1)), "hipMalloc");
-  HIPC(ctx->rs_boff.ensure(sizeof(int64_t) * (npz + 1)), "hipMalloc");
+  int64_t *soff = nullptr, *toff = nullptr, *boff = nullptr, *tot = nullptr;  // the scans of nslot, ntask, tbytes
+  HIPC(ctx->rs_soff.get(soff, npz + 1), "hipMalloc");
+  HIPC(ctx->rs_toff.get(toff, npz + 1), "hipMalloc");
+  HIPC(ctx->rs_boff.get(boff, npz + 1), "hipMalloc");
   HIPC(ctx->rs_qpool.ensure(2 * (size_t)seq_bytes + 64), "hipMalloc");
-  HIPC(ctx->rs_ctr.ensure(sizeof(int32_t) * RC_WORDS), "hipMalloc");
-  HIPC(ctx->chh_tot.ensure(sizeof(int64_t) * 16), "hipHostMalloc");
+  HIPC(ctx->rs_ctr.get(a.ctr, RC_WORDS), "hipMalloc");
+  HIPC(ctx->chh_tot.get(tot, 16), "hipHostMalloc");
   a.pstate = ctx->rs_pair.as<int32_t>();
   a.nb0 = a.pstate + npz;
   a.nslot = a.nb0 + npz;
   a.ntask = a.nslot + npz;
   a.tbytes = a.ntask + npz;
-  a.slot_off = ctx->rs_soff.as<int64_t>();
-  a.task_off = ctx->rs_toff.as<int64_t>();
-  a.tb_off = ctx->rs_boff.as<int64_t>();
+  a.slot_off = soff;
+  a.task_off = toff;
+  a.tb_off = boff;
   a.qpool = ctx->rs_qpool.as<uint8_t>();
   a.rc_base = seq_bytes;
-  a.ctr = ctx->rs_ctr.as<int32_t>();
-  int64_t* tot = ctx->chh_tot.as<int64_t>();
   ctx->rs_ev_rounds = 0;
   ctx->rs_ev_stream = st;
   HIPC(launch_rescue_pool(a, st), "rescue_pool launch");
   HIPC(launch_rescue_init(ctx->opt, a, st), "rescue_init launch");
-  HIPC(launch_scan_i32(a.nslot, ctx->rs_soff.as<int64_t>(), np, st), "scan launch");
-  HIPC(hipMemcpyAsync(tot + 8, ctx->rs_soff.as<int64_t>() + np, sizeof(int64_t), hipMemcpyDeviceToHost, st), "D2H");
+  HIPC(launch_scan_i32(a.nslot, soff, np, st), "scan launch");
+  HIPC(hipMemcpyAsync(tot + 8, soff + np, sizeof(int64_t), hipMemcpyDeviceToHost, st), "D2H");
   HIPC(hipStreamSynchronize(st), "sync");
   const int64_t S = tot[8];
-  HIPC(ctx->rs_tab.ensure(sizeof(int32_t) * (size_t)std::max<int64_t>(S, 1)), "hipMalloc");
-  HIPC(hipMemsetAsync(ctx->rs_tab.p, 0xff, sizeof(int32_t) * (size_t)std::max<int64_t>(S, 1), st), "memset");  // RS_NONE
-  a.tab = ctx->rs_tab.as<int32_t>();
+  HIPC(ctx->rs_tab.get(a.tab, (size_t)S), "hipMalloc");
+  HIPC(hipMemsetAsync(a.tab, 0xff, sizeof(int32_t) * (size_t)std::max<int64_t>(S, 1), st), "memset");  // RS_NONE
   HIPC(hipMemsetAsync(a.ctr, 0, sizeof(int32_t) * RC_WORDS, st), "memset");
   for (int round = 0; round < po.max_rounds; ++round) {
     a.round = round;
@@ -198,26 +195,24 @@ int enqueue_rescue(bwagpu_ctx_t* ctx, const bwagpu_pairopt_t& po, const bwagpu_p
       if (!ev[k]) HIPC(hipEventCreate(&ev[k]), "hipEventCreate");
     HIPC(hipEventRecord(ev[0], st), "event");
     HIPC(launch_rescue_plan(ctx->opt, ctx->ref, a, false, st), "rescue_plan launch");
-    HIPC(launch_scan_i32(a.ntask, ctx->rs_toff.as<int64_t>(), np, st), "scan launch");
-    HIPC(launch_scan_i32(a.tbytes, ctx->rs_boff.as<int64_t>(), np, st), "scan launch");
-    HIPC(hipMemcpyAsync(tot + 9, ctx->rs_toff.as<int64_t>() + np, sizeof(int64_t), hipMemcpyDeviceToHost, st), "D2H");
-    HIPC(hipMemcpyAsync(tot + 10, ctx->rs_boff.as<int64_t>() + np, sizeof(int64_t), hipMemcpyDeviceToHost, st), "D2H");
+    HIPC(launch_scan_i32(a.ntask, toff, np, st), "scan launch");
+    HIPC(launch_scan_i32(a.tbytes, boff, np, st), "scan launch");
+    HIPC(hipMemcpyAsync(tot + 9, toff + np, sizeof(int64_t), hipMemcpyDeviceToHost, st), "D2H");
+    HIPC(hipMemcpyAsync(tot + 10, boff + np, sizeof(int64_t), hipMemcpyDeviceToHost, st), "D2H");
     HIPC(hipStreamSynchronize(st), "sync");
     const int64_t T = tot[9], B = tot[10];
     if (T >= (int64_t)1 << kRescueIdxBits) return fail(ctx, BWAGPU_E_UNSUPPORTED, "too many rescue alignments in one batch");
     if (T) {
-      HIPC(ctx->rs_tasks[round].ensure(sizeof(bwagpu_align2_task_t) * (size_t)T), "hipMalloc");
+      bwagpu_kswr_t* res = nullptr;
+      HIPC(ctx->rs_tasks[round].get(a.tasks, (size_t)T), "hipMalloc");
       HIPC(ctx->rs_tpool[round].ensure((size_t)B + 64), "hipMalloc");
-      HIPC(ctx->rs_res[round].ensure(sizeof(bwagpu_kswr_t) * (size_t)T), "hipMalloc");
+      HIPC(ctx->rs_res[round].get(res, (size_t)T), "hipMalloc");
       HIPC(ctx->rs_scr.ensure(8 * ((size_t)B + (size_t)T)), "hipMalloc");
-      a.tasks = ctx->rs_tasks[round].as<bwagpu_align2_task_t>();
       a.tpool = ctx->rs_tpool[round].as<uint8_t>();
-      a.res[round] = ctx->rs_res[round].as<bwagpu_kswr_t>();
+      a.res[round] = res;
       HIPC(launch_rescue_plan(ctx->opt, ctx->ref, a, true, st), "rescue_plan launch");
       HIPC(hipEventRecord(ev[1], st), "event");
-      if (int rc = bwagpu_align2_device(ctx, (int32_t)T, a.tasks, a.qpool, a.tpool, ctx->rs_res[round].as<bwagpu_kswr_t>(),
-                                        ctx->rs_scr.p, st))
-        return rc;
+      if (int rc = bwagpu_align2_device(ctx, (int32_t)T, a.tasks, a.qpool, a.tpool, res, ctx->rs_scr.p, st)) return rc;
       run->tasks += T;
     } else {
       HIPC(hipEventRecord(ev[1], st), "event");
@@ -384,8 +379,8 @@ int sel_tmp(const bwagpu_ctx_t* ctx) {  // bwamem.c:505-507
 
 int enqueue_mark(bwagpu_ctx_t* ctx, const bwagpu_selopt_t& so, int64_t id0, int32_t n_reads, const int64_t* reg_off,
                  bwagpu_alnreg_t* regs, const int32_t* n, int32_t* n_pri, int32_t* status, hipStream_t st) {
-  HIPC(ctx->ps_scratch.ensure(sizeof(bwagpu_alnreg_t) * (size_t)kSelCap * kSelMaxBlocks), "hipMalloc");
   MarkArgs a{};
+  HIPC(ctx->ps_scratch.get(a.scratch, (size_t)kSelCap * kSelMaxBlocks), "hipMalloc");
   a.n_reads = n_reads;
   a.tmp = sel_tmp(ctx);
   a.mask_level = so.mask_level;
@@ -395,7 +390,6 @@ int enqueue_mark(bwagpu_ctx_t* ctx, const bwagpu_selopt_t& so, int64_t id0, int3
   a.n = n;
   a.n_pri = n_pri;
   a.status = status;
-  a.scratch = ctx->ps_scratch.as<bwagpu_alnreg_t>();
   HIPC(launch_mark_primary(a, st), "mark_primary launch");
   return BWAGPU_OK;
 }
@@ -409,25 +403,27 @@ int enqueue_pairsel(bwagpu_ctx_t* ctx, const bwagpu_selopt_t& so, const bwagpu_p
   if (!ctx->ps_log_ready) {
     std::vector<double> lg((size_t)kSelLogN);
     fill_log_table(lg.data(), kSelLogN);
-    HIPC(ctx->ps_log.ensure(sizeof(double) * (size_t)kSelLogN), "hipMalloc");
-    HIPC(hipMemcpyAsync(ctx->ps_log.p, lg.data(), sizeof(double) * (size_t)kSelLogN, hipMemcpyHostToDevice, st), "H2D");
+    double* d_lg = nullptr;
+    HIPC(ctx->ps_log.get(d_lg, (size_t)kSelLogN), "hipMalloc");
+    HIPC(hipMemcpyAsync(d_lg, lg.data(), sizeof(double) * (size_t)kSelLogN, hipMemcpyHostToDevice, st), "H2D");
     HIPC(hipStreamSynchronize(st), "H2D");
     ctx->ps_log_ready = true;
   }
   int64_t len[4], total = 0;
   for (int r = 0; r < 4; ++r) total += len[r] = erfc_table_len(hpes[r]);
-  std::vector<double> tab((size_t)std::max<int64_t>(total, 1));
-  HIPC(ctx->ps_erfc.ensure(sizeof(double) * tab.size()), "hipMalloc");
+  std::vector<double> tab((size_t)total);
+  double* d_erfc = nullptr;
+  HIPC(ctx->ps_erfc.get(d_erfc, tab.size()), "hipMalloc");
   PairSelArgs a{};
   int64_t at = 0;
   for (int r = 0; r < 4; ++r) {
     a.pes[r] = hpes[r];
-    a.erfc_tab[r] = ctx->ps_erfc.as<double>() + at;
+    a.erfc_tab[r] = d_erfc + at;
     if (len[r]) fill_erfc_table(hpes[r], tab.data() + at);
     at += len[r];
   }
   if (total) {
-    HIPC(hipMemcpyAsync(ctx->ps_erfc.p, tab.data(), sizeof(double) * (size_t)total, hipMemcpyHostToDevice, st), "H2D");
+    HIPC(hipMemcpyAsync(d_erfc, tab.data(), sizeof(double) * (size_t)total, hipMemcpyHostToDevice, st), "H2D");
     HIPC(hipStreamSynchronize(st), "H2D");
   }
   a.n_pairs = n_reads >> 1;

@@ -75,27 +75,28 @@ int bwagpu_extend_batch(bwagpu_ctx_t* ctx, int32_t n, const bwagpu_ext_task_t* t
   TRY(h.up(ctx->ex_tasks, tasks, sizeof(bwagpu_ext_task_t) * n));
   TRY(h.up(ctx->ex_q, qpool, (size_t)qpool_len, 1));
   TRY(h.up(ctx->ex_t, tpool, (size_t)tpool_len, 1));
-  TRY(h.reserve(ctx->ex_list, sizeof(int32_t) * n));
-  TRY(h.reserve(ctx->ex_res, sizeof(bwagpu_ext_result_t) * n));
-  TRY(h.reserve(ctx->ex_stats, sizeof(int64_t) * ST_N));
-  HIPC(hipMemcpyAsync(ctx->ex_list.p, plan.all.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, st), "H2D");
-  HIPC(hipMemsetAsync(ctx->ex_stats.p, 0, sizeof(int64_t) * ST_N, st), "memset");
+  int32_t* lists = nullptr;
+  bwagpu_ext_result_t* res = nullptr;
+  int64_t* stats = nullptr;
+  TRY(h.reserve(ctx->ex_list, lists, (size_t)n));
+  TRY(h.reserve(ctx->ex_res, res, (size_t)n));
+  TRY(h.reserve(ctx->ex_stats, stats, ST_N));
+  HIPC(hipMemcpyAsync(lists, plan.all.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, st), "H2D");
+  HIPC(hipMemsetAsync(stats, 0, sizeof(int64_t) * ST_N, st), "memset");
   TRY(h.start());
+  const bwagpu_ext_task_t* d_tasks = ctx->ex_tasks.as<bwagpu_ext_task_t>();
+  const uint8_t *d_q = ctx->ex_q.as<uint8_t>(), *d_t = ctx->ex_t.as<uint8_t>();
   for (int v = 0; v < kExtLists; ++v) {
     if (!plan.count[v]) continue;
-    const int32_t* list = ctx->ex_list.as<int32_t>() + plan.off[v];
+    const int32_t* list = lists + plan.off[v];
     HIPC(v < kNumExtVariants
-             ? launch_extend(v, plan.t5, ctx->opt, n, ctx->ex_tasks.as<bwagpu_ext_task_t>(), list, plan.count[v],
-                             ctx->ex_q.as<uint8_t>(), ctx->ex_t.as<uint8_t>(), plan.tb[v],
-                             ctx->ex_res.as<bwagpu_ext_result_t>(), ctx->ex_stats.as<int64_t>(), st)
-             : launch_extend4(ctx->opt, ctx->ex_tasks.as<bwagpu_ext_task_t>(), list, plan.count[v],
-                              ctx->ex_q.as<uint8_t>(), ctx->ex_t.as<uint8_t>(), plan.tb[v],
-                              ctx->ex_res.as<bwagpu_ext_result_t>(), ctx->ex_stats.as<int64_t>(), st),
+             ? launch_extend(v, plan.t5, ctx->opt, n, d_tasks, list, plan.count[v], d_q, d_t, plan.tb[v], res, stats, st)
+             : launch_extend4(ctx->opt, d_tasks, list, plan.count[v], d_q, d_t, plan.tb[v], res, stats, st),
          "extend launch");
   }
   TRY(h.stop());
   TRY(h.down(results, ctx->ex_res, sizeof(bwagpu_ext_result_t) * n));
-  return h.finish("extend batch", ctx->ex_stats.as<int64_t>());
+  return h.finish("extend batch", stats);
 }
 
 int bwagpu_reg2aln_batch(bwagpu_ctx_t* ctx, int32_t n, const bwagpu_reg2aln_task_t* tasks, const uint8_t* qpool,
@@ -163,13 +164,16 @@ int bwagpu_reg2aln_batch(bwagpu_ctx_t* ctx, int32_t n, const bwagpu_reg2aln_task
   HIPC(hipSetDevice(ctx->device), "hipSetDevice");
   hipStream_t st = nullptr;
   HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
-  HIPC(ctx->r2_tasks.ensure(sizeof(bwagpu_reg2aln_task_t) * n), "hipMalloc");
+  R2AArgs base{};  // what the launches of all bins share
+  int32_t* lists = nullptr;
+  HIPC(ctx->r2_tasks.get(base.tasks, (size_t)n), "hipMalloc");
   HIPC(ctx->r2_q.ensure((size_t)qpool_len + 1), "hipMalloc");
-  HIPC(ctx->r2_out.ensure(sizeof(bwagpu_aln_t) * n), "hipMalloc");
-  HIPC(ctx->r2_cig.ensure(sizeof(uint32_t) * (size_t)n * max_ops), "hipMalloc");
-  HIPC(ctx->r2_md.ensure((size_t)n * max_md), "hipMalloc");
-  HIPC(ctx->r2_lists.ensure(sizeof(int32_t) * n), "hipMalloc");
-  HIPC(ctx->r2_stats.ensure(sizeof(int64_t) * ST_N), "hipMalloc");
+  HIPC(ctx->r2_out.get(base.out, (size_t)n), "hipMalloc");
+  HIPC(ctx->r2_cig.get(base.cigar, (size_t)n * max_ops), "hipMalloc");
+  HIPC(ctx->r2_md.get(base.md, (size_t)n * max_md), "hipMalloc");
+  HIPC(ctx->r2_lists.get(lists, (size_t)n), "hipMalloc");
+  HIPC(ctx->r2_stats.get(base.stats, ST_N), "hipMalloc");
+  base.qpool = ctx->r2_q.as<uint8_t>(), base.max_ops = max_ops, base.max_md = max_md;
   std::vector<int32_t> all;
   all.reserve((size_t)n);
   for (auto& row : bins)
@@ -202,11 +206,8 @@ int bwagpu_reg2aln_batch(bwagpu_ctx_t* ctx, int32_t n, const bwagpu_reg2aln_task
   TRY(side_fork(ctx, st, launches.size(), &used));
   auto make_args = [&](const Launch& L, int& wpb) {
     const Bin& b = bins[L.bk][L.cls];
-    R2AArgs a{};
-    a.tasks = ctx->r2_tasks.as<bwagpu_reg2aln_task_t>(), a.qpool = ctx->r2_q.as<uint8_t>();
-    a.list = ctx->r2_lists.as<int32_t>() + L.off, a.n = (int)b.ids.size(), a.max_ops = max_ops, a.max_md = max_md;
-    a.out = ctx->r2_out.as<bwagpu_aln_t>(), a.cigar = ctx->r2_cig.as<uint32_t>(), a.md = ctx->r2_md.as<char>();
-    a.stats = ctx->r2_stats.as<int64_t>();
+    R2AArgs a = base;
+    a.list = lists + L.off, a.n = (int)b.ids.size();
     a.qcap = (b.qmax + 16) & ~15;
     a.rcap = (b.rmax + 16) & ~15;
     a.ocap = a.qcap + a.rcap + 4;
@@ -231,7 +232,8 @@ int bwagpu_reg2aln_batch(bwagpu_ctx_t* ctx, int32_t n, const bwagpu_reg2aln_task
     }
     L.work = waves;
   }
-  HIPC(ctx->r2_z.ensure(std::max<size_t>(zoff, 256)), "hipMalloc(reg2aln matrices)");
+  uint8_t* z = nullptr;
+  HIPC(ctx->r2_z.get(z, std::max<size_t>(zoff, 256)), "hipMalloc(reg2aln matrices)");
   zoff = 0;
   for (size_t li = 0; li < launches.size(); ++li) {
     const Launch& L = launches[li];
@@ -239,7 +241,7 @@ int bwagpu_reg2aln_batch(bwagpu_ctx_t* ctx, int32_t n, const bwagpu_reg2aln_task
     R2AArgs a = make_args(L, wpb);
     const int nb = a.n, waves = (int)L.work;
     if (L.cls == 2) {
-      a.zglob = ctx->r2_z.as<uint8_t>() + zoff;
+      a.zglob = z + zoff;
       zoff += (size_t)a.zstride * waves;
     }
     const int blocks = std::max(1, std::min((nb + wpb - 1) / wpb, waves / wpb));
@@ -286,17 +288,17 @@ int bwagpu_reg2aln_device(bwagpu_ctx_t* ctx, int32_t n_cap, const int32_t* dev_n
                            tab_bytes > ctx->r2d_tab.cap))
     HIPC(hipEventSynchronize(ctx->r2d_done), "event sync");
   if (ctx->r2d_pending) HIPC(hipStreamWaitEvent(st, ctx->r2d_done, 0), "stream wait");
-  HIPC(ctx->r2d_keys.ensure(list_bytes), "hipMalloc");
-  HIPC(ctx->r2d_lists.ensure(list_bytes), "hipMalloc");
+  int32_t *keys = nullptr, *lists = nullptr, *htab = nullptr;
+  HIPC(ctx->r2d_keys.get(keys, (size_t)n_cap), "hipMalloc");
+  HIPC(ctx->r2d_lists.get(lists, (size_t)n_cap), "hipMalloc");
   HIPC(ctx->r2d_tab.ensure(tab_bytes), "hipMalloc");  // table | scatter cursors
-  HIPC(ctx->r2d_htab.ensure(sizeof(int32_t) * kR2TabWords), "hipHostMalloc");
+  HIPC(ctx->r2d_htab.get(htab, kR2TabWords), "hipHostMalloc");
   if (!ctx->r2d_done) HIPC(hipEventCreateWithFlags(&ctx->r2d_done, hipEventDisableTiming), "event");
   if (timing)
     for (hipEvent_t& e : ctx->r2d_ev)
       if (!e) HIPC(hipEventCreate(&e), "event");
   int32_t* const d_tab = ctx->r2d_tab.as<int32_t>();
-  int32_t* const keys = ctx->r2d_keys.as<int32_t>();
-  const int32_t* const h = ctx->r2d_htab.as<int32_t>();
+  const int32_t* const h = htab;
   ctx->r2d_timed = false;
   // every way out from here on leaves the event behind what this call enqueued
   struct Done {
@@ -307,7 +309,7 @@ int bwagpu_reg2aln_device(bwagpu_ctx_t* ctx, int32_t n_cap, const int32_t* dev_n
   HIPC(hipMemsetAsync(d_tab, 0, sizeof(int32_t) * (kR2TabWords + kKeys), st), "memset");
   HIPC(launch_reg2aln_classify(o, ctx->ref.l_pac, qpool_len, n_cap, dev_n_tasks, dev_tasks, keys, dev_out, d_tab, st),
        "reg2aln classify launch");
-  HIPC(hipMemcpyAsync(ctx->r2d_htab.p, d_tab, sizeof(int32_t) * kR2TabWords, hipMemcpyDeviceToHost, st), "D2H");
+  HIPC(hipMemcpyAsync(htab, d_tab, sizeof(int32_t) * kR2TabWords, hipMemcpyDeviceToHost, st), "D2H");
   const auto t_wait = std::chrono::steady_clock::now();
   // the stream waited for the previous device-form call first, so that call has finished too
   HIPC(hipStreamSynchronize(st), "reg2aln classification");
@@ -336,7 +338,7 @@ int bwagpu_reg2aln_device(bwagpu_ctx_t* ctx, int32_t n_cap, const int32_t* dev_n
     const int b = L.bk * 3 + L.cls;
     R2AArgs& a = L.a;
     a = R2AArgs{};
-    a.tasks = dev_tasks, a.qpool = dev_qpool, a.list = ctx->r2d_lists.as<int32_t>() + L.off, a.n = L.n;
+    a.tasks = dev_tasks, a.qpool = dev_qpool, a.list = lists + L.off, a.n = L.n;
     a.max_ops = max_ops, a.max_md = max_md, a.out = dev_out, a.cigar = dev_cigar, a.md = dev_md;
     // the issue of this field: a producer's count that stays on the device.  Here it is the table word
     // the host has just read into a.n, so min(a.n, *dev_n) = a.n; but the running bins now read the
@@ -356,9 +358,9 @@ int bwagpu_reg2aln_device(bwagpu_ctx_t* ctx, int32_t n_cap, const int32_t* dev_n
       zoff += (size_t)a.zstride * L.waves;
     }
   }
-  HIPC(ctx->r2d_z.ensure(std::max<size_t>(zoff, 256)), "hipMalloc(reg2aln matrices)");  // idle: see the wait above
-  if (at) HIPC(launch_reg2aln_scatter(n_cap, keys, off, d_tab + kR2TabWords, ctx->r2d_lists.as<int32_t>(), st),
-               "reg2aln scatter launch");
+  uint8_t* z = nullptr;
+  HIPC(ctx->r2d_z.get(z, std::max<size_t>(zoff, 256)), "hipMalloc(reg2aln matrices)");  // idle: see the wait above
+  if (at) HIPC(launch_reg2aln_scatter(n_cap, keys, off, d_tab + kR2TabWords, lists, st), "reg2aln scatter launch");
   if (timing) HIPC(hipEventRecord(ctx->r2d_ev[0], st), "event");
   if (!launches.empty()) {
     int used = 0;
@@ -367,7 +369,7 @@ int bwagpu_reg2aln_device(bwagpu_ctx_t* ctx, int32_t n_cap, const int32_t* dev_n
     for (size_t li = 0; li < launches.size(); ++li) {
       Launch& L = launches[li];
       if (L.cls == 2) {
-        L.a.zglob = ctx->r2d_z.as<uint8_t>() + zoff;
+        L.a.zglob = z + zoff;
         zoff += (size_t)L.a.zstride * L.waves;
       }
       const int blocks = std::max(1, std::min((L.n + L.wpb - 1) / L.wpb, L.waves / L.wpb));
@@ -414,13 +416,14 @@ int bwagpu_reg2aln_jobs_device(bwagpu_ctx_t* ctx, int32_t n_reads, const int64_t
     HIPC(hipMemsetAsync(dev_n_jobs, 0, 2 * sizeof(int32_t), st), "memset");
     return BWAGPU_OK;
   }
-  const size_t sum_bytes = sizeof(int32_t) * (((size_t)n_reads + 255) / 256);
+  const size_t n_sums = ((size_t)n_reads + 255) / 256, sum_bytes = sizeof(int32_t) * n_sums;
   if (!ctx->r2d_done) HIPC(hipEventCreateWithFlags(&ctx->r2d_done, hipEventDisableTiming), "event");
   if (ctx->r2d_pending && sum_bytes > ctx->r2d_sums.cap) HIPC(hipEventSynchronize(ctx->r2d_done), "event sync");
   if (ctx->r2d_pending) HIPC(hipStreamWaitEvent(st, ctx->r2d_done, 0), "stream wait");
-  HIPC(ctx->r2d_sums.ensure(sum_bytes), "hipMalloc");
+  int32_t* sums = nullptr;
+  HIPC(ctx->r2d_sums.get(sums, n_sums), "hipMalloc");
   const hipError_t e = launch_reg2aln_jobs(n_reads, dev_reg_off, dev_regs, dev_n, dev_select, dev_seq_off, job_cap,
-                                           dev_tasks, dev_job_of, dev_n_jobs, ctx->r2d_sums.as<int32_t>(), st);
+                                           dev_tasks, dev_job_of, dev_n_jobs, sums, st);
   if (hipEventRecord(ctx->r2d_done, st) == hipSuccess) ctx->r2d_pending = true;
   HIPC(e, "reg2aln jobs launch");
   return BWAGPU_OK;
@@ -464,22 +467,25 @@ int bwagpu_align2_batch(bwagpu_ctx_t* ctx, int32_t n, const bwagpu_align2_task_t
   TRY(h.up(ctx->a2_tasks, tasks, sizeof(bwagpu_align2_task_t) * n));
   TRY(h.up(ctx->a2_q, qpool, (size_t)qpool_len, 1));
   TRY(h.up(ctx->a2_t, tpool, (size_t)tpool_len, 1));
-  TRY(h.reserve(ctx->a2_out, sizeof(bwagpu_kswr_t) * n));
-  TRY(h.reserve(ctx->a2_scratch, sizeof(int2) * (size_t)plan.scratch));
-  TRY(h.reserve(ctx->a2_lists, sizeof(int32_t) * n));
+  bwagpu_kswr_t* out = nullptr;
+  int2* scratch = nullptr;
+  int32_t* lists = nullptr;
+  int64_t* boff = nullptr;
+  TRY(h.reserve(ctx->a2_out, out, (size_t)n));
+  TRY(h.reserve(ctx->a2_scratch, scratch, (size_t)plan.scratch));
+  TRY(h.reserve(ctx->a2_lists, lists, (size_t)n));
   // counts[kA2Bins] | cursors[kA2Bins] | stats[ST_N]
   TRY(h.reserve(ctx->a2_counts, sizeof(int32_t) * 2 * kA2Bins + sizeof(int64_t) * ST_N));
-  TRY(h.reserve(ctx->a2_boff, sizeof(int64_t) * n));
+  TRY(h.reserve(ctx->a2_boff, boff, (size_t)n));
   int32_t* d_counts = ctx->a2_counts.as<int32_t>();
   int64_t* d_stats = (int64_t*)(d_counts + 2 * kA2Bins);
-  HIPC(hipMemcpyAsync(ctx->a2_lists.p, plan.all.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, st), "H2D");
+  HIPC(hipMemcpyAsync(lists, plan.all.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, st), "H2D");
   HIPC(hipMemcpyAsync(d_counts, plan.counts, sizeof plan.counts, hipMemcpyHostToDevice, st), "H2D");  // + zero cursors
   HIPC(hipMemsetAsync(d_stats, 0, sizeof(int64_t) * ST_N, st), "memset");
-  HIPC(hipMemcpyAsync(ctx->a2_boff.p, plan.boff.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice, st), "H2D");
+  HIPC(hipMemcpyAsync(boff, plan.boff.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice, st), "H2D");
   TRY(h.start());
-  const A2Args base{ctx->a2_tasks.as<bwagpu_align2_task_t>(), ctx->a2_q.as<uint8_t>(), ctx->a2_t.as<uint8_t>(),
-                    ctx->a2_out.as<bwagpu_kswr_t>(), ctx->a2_scratch.as<int2>(), ctx->a2_boff.as<int64_t>(),
-                    ctx->a2_lists.as<int32_t>(), nullptr, nullptr, d_stats};
+  const A2Args base{ctx->a2_tasks.as<bwagpu_align2_task_t>(), ctx->a2_q.as<uint8_t>(), ctx->a2_t.as<uint8_t>(), out,
+                    scratch, boff, lists, nullptr, nullptr, d_stats};
   TRY(launch_align2_concurrent(ctx, st, plan.bins, base, plan.list_off, plan.counts, d_counts, d_counts + kA2Bins, 0));
   TRY(h.stop());
   TRY(h.down(results, ctx->a2_out, sizeof(bwagpu_kswr_t) * n));
@@ -494,8 +500,10 @@ int bwagpu_align2_device(bwagpu_ctx_t* ctx, int32_t n, const bwagpu_align2_task_
   if (const char* why = align2_opt_unsupported(ctx->opt)) return fail(ctx, BWAGPU_E_UNSUPPORTED, why);
   hipStream_t st = nullptr;
   if (int rc = entry_stream(ctx, stream, &st)) return rc;
-  HIPC(ctx->a2_lists.ensure(sizeof(int32_t) * (size_t)kA2Bins * n), "hipMalloc");
-  HIPC(ctx->a2_boff.ensure(sizeof(int64_t) * n), "hipMalloc");
+  int32_t* lists = nullptr;
+  int64_t* boff = nullptr;
+  HIPC(ctx->a2_lists.get(lists, (size_t)kA2Bins * n), "hipMalloc");
+  HIPC(ctx->a2_boff.get(boff, (size_t)n), "hipMalloc");
   // counts[kA2Bins] | cursors[kA2Bins] | scratch cursor (u64) | stats[ST_N]
   const size_t cbytes = sizeof(int32_t) * 2 * kA2Bins + sizeof(int64_t) * (1 + ST_N);
   HIPC(ctx->a2_counts.ensure(cbytes), "hipMalloc");
@@ -503,14 +511,12 @@ int bwagpu_align2_device(bwagpu_ctx_t* ctx, int32_t n, const bwagpu_align2_task_
   unsigned long long* cursor = (unsigned long long*)(d_counts + 2 * kA2Bins);
   int64_t* d_stats = (int64_t*)(cursor + 1);
   HIPC(hipMemsetAsync(d_counts, 0, cbytes, st), "memset");
-  HIPC(launch_align2_bins(ctx->opt, dev_tasks, n, ctx->a2_lists.as<int32_t>(), d_counts, ctx->a2_boff.as<int64_t>(),
-                          cursor, dev_results, d_stats, st),
+  HIPC(launch_align2_bins(ctx->opt, dev_tasks, n, lists, d_counts, boff, cursor, dev_results, d_stats, st),
        "align2 bin launch");
   // counts are on the device only: every bin's kernel is launched with a
   // resident-capacity grid; an empty bin's waves exit on their first claim
   const std::vector<int> bins{2, 3, 10, 11, 1, 9, 0, 8, 4, 12, 5, 13, 6, 14, 7, 15};
-  A2Args base{dev_tasks, dev_qpool, dev_tpool, dev_results, (int2*)dev_scratch, ctx->a2_boff.as<int64_t>(),
-              ctx->a2_lists.as<int32_t>(), nullptr, nullptr, d_stats};
+  A2Args base{dev_tasks, dev_qpool, dev_tpool, dev_results, (int2*)dev_scratch, boff, lists, nullptr, nullptr, d_stats};
   return launch_align2_concurrent(ctx, st, bins, base, nullptr, nullptr, d_counts, d_counts + kA2Bins, (size_t)n);
 }
 
@@ -538,21 +544,19 @@ int bwagpu_sw_stream(bwagpu_ctx_t* ctx, const int32_t* i_buf, int64_t i_words, i
   hipStream_t st = h.st;
   const size_t cap = (size_t)std::max(o_cap_tasks, 1), nr = plan.starts.size();
   TRY(h.up(ctx->st_buf, i_buf, sizeof(int32_t) * (size_t)i_words));
-  TRY(h.reserve(ctx->st_start, sizeof(int64_t) * nr));
-  TRY(h.reserve(ctx->st_q, 8 * (size_t)i_words));
-  TRY(h.reserve(ctx->st_tasks, sizeof(StreamTask) * cap));
-  TRY(h.reserve(ctx->st_lists, sizeof(int32_t) * kSpecBins * cap));
-  TRY(h.reserve(ctx->st_seen, sizeof(int32_t) * cap));
-  TRY(h.reserve(ctx->st_ctr, sizeof(int32_t) * kStrCtrWords));
-  TRY(h.reserve(ctx->st_out, sizeof(int32_t) * 5 * cap));
-  HIPC(hipMemcpyAsync(ctx->st_start.p, plan.starts.data(), sizeof(int64_t) * nr, hipMemcpyHostToDevice, st), "H2D");
-  HIPC(hipMemsetAsync(ctx->st_seen.p, 0, sizeof(int32_t) * cap, st), "memset");
-  HIPC(hipMemsetAsync(ctx->st_ctr.p, 0, sizeof(int32_t) * kStrCtrWords, st), "memset");
   StreamArgs a{};
-  a.buf = ctx->st_buf.as<int32_t>(), a.rstart = ctx->st_start.as<int64_t>(), a.n_reads = (int32_t)nr;
+  TRY(h.reserve(ctx->st_start, a.rstart, nr));
+  TRY(h.reserve(ctx->st_q, a.qpool, 8 * (size_t)i_words));
+  TRY(h.reserve(ctx->st_tasks, a.tasks, cap));
+  TRY(h.reserve(ctx->st_lists, a.lists, kSpecBins * cap));
+  TRY(h.reserve(ctx->st_seen, a.seen, cap));
+  TRY(h.reserve(ctx->st_ctr, a.ctr, kStrCtrWords));
+  TRY(h.reserve(ctx->st_out, a.out, 5 * cap));
+  HIPC(hipMemcpyAsync(ctx->st_start.p, plan.starts.data(), sizeof(int64_t) * nr, hipMemcpyHostToDevice, st), "H2D");
+  HIPC(hipMemsetAsync(a.seen, 0, sizeof(int32_t) * cap, st), "memset");
+  HIPC(hipMemsetAsync(a.ctr, 0, sizeof(int32_t) * kStrCtrWords, st), "memset");
+  a.buf = ctx->st_buf.as<int32_t>(), a.n_reads = (int32_t)nr;
   a.cap = o_cap_tasks, a.l_pac = ctx->ref.l_pac;  // cap 0: every task index is then out of range
-  a.qpool = ctx->st_q.as<uint8_t>(), a.tasks = ctx->st_tasks.as<StreamTask>(), a.lists = ctx->st_lists.as<int32_t>();
-  a.seen = ctx->st_seen.as<int32_t>(), a.ctr = ctx->st_ctr.as<int32_t>(), a.out = ctx->st_out.as<int32_t>();
   TRY(h.start());
   HIPC(launch_sw_stream(ctx->opt, ctx->ref, a, tb, st), "sw_stream launch");
   TRY(h.stop());

@@ -7,9 +7,11 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "bwagpu.h"
@@ -22,21 +24,46 @@
 
 namespace bwagpu {
 
+// live GrowBuf allocations of the process and their bytes (bwagpu_debug_live_buffers)
+inline std::atomic<int64_t> g_live_bufs{0}, g_live_bytes{0};
+
+// Grow-only device buffer, or pinned host buffer.  It owns its memory: whoever holds one
+// (the context, a Slot, Staging) frees it by going away, so nothing lists buffers to free.
 template <bool kPinned>
-struct GrowBuf {  // grow-only device buffer, or pinned host buffer
+struct GrowBuf {
   void* p = nullptr;
   size_t cap = 0;
+  GrowBuf() = default;
+  GrowBuf(const GrowBuf&) = delete;
+  GrowBuf& operator=(const GrowBuf&) = delete;
+  ~GrowBuf() { release(); }
   hipError_t ensure(size_t n) {
     if (n <= cap) return hipSuccess;
     release();
     const size_t want = std::max<size_t>(n + n / 4, 4096);
     const hipError_t e = kPinned ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want);
-    if (e == hipSuccess) cap = want;
-    else p = nullptr;
+    if (e != hipSuccess) {
+      p = nullptr;
+      return e;
+    }
+    cap = want;
+    g_live_bufs.fetch_add(1, std::memory_order_relaxed);
+    g_live_bytes.fetch_add((int64_t)want, std::memory_order_relaxed);
+    return e;
+  }
+  // room for n elements of T, at least one so that a kernel always gets a pointer -> out (null on failure)
+  template <class T>
+  hipError_t get(T*& out, size_t n) {
+    const hipError_t e = ensure(sizeof(T) * std::max<size_t>(n, 1));
+    out = e == hipSuccess ? (T*)p : nullptr;
     return e;
   }
   void release() {
-    if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p));
+    if (p) {
+      (void)(kPinned ? hipHostFree(p) : hipFree(p));
+      g_live_bufs.fetch_sub(1, std::memory_order_relaxed);
+      g_live_bytes.fetch_sub((int64_t)cap, std::memory_order_relaxed);
+    }
     p = nullptr;
     cap = 0;
   }
@@ -45,6 +72,7 @@ struct GrowBuf {  // grow-only device buffer, or pinned host buffer
 };
 using DevBuf = GrowBuf<false>;
 using HostBuf = GrowBuf<true>;
+static_assert(!std::is_copy_constructible<DevBuf>::value, "a copy would free the buffer twice");
 
 struct Slot {
   // created on first use (lazy_stream): the device entry runs on the caller's
@@ -60,22 +88,6 @@ struct Slot {
   DevBuf d_schain, d_hinfo, d_mat, d_cov, d_hflag, d_colent, d_qh, d_longc, d_sorth, d_stasks, d_ftask, d_ftaskR;
   SpecStreams spec;  // created on first use (choose_side)
   bool side_chosen = false;
-  void release_scratch() {
-    d_win.release(); d_srt.release(); d_prog.release(); d_desc.release(); d_lists.release(); d_counts.release();
-    d_cread.release(); d_ext.release(); d_tasks.release(); d_ctr.release(); d_regpos.release(); d_skipf.release();
-    d_heavy.release(); d_redo.release(); d_rbits.release(); d_schain.release(); d_hinfo.release(); d_mat.release(); d_cov.release(); d_hflag.release(); d_colent.release(); d_longc.release();
-    d_qh.release();
-    d_sorth.release();
-    d_stasks.release();
-    d_ftask.release();
-    d_ftaskR.release();
-    if (spec.side) (void)hipStreamSynchronize(spec.side);
-    if (spec.side) (void)hipStreamDestroy(spec.side);
-    if (spec.fork) (void)hipEventDestroy(spec.fork);
-    if (spec.join) (void)hipEventDestroy(spec.join);
-    spec = SpecStreams{};
-    side_chosen = false;
-  }
   HostBuf h_in, h_out, h_n, h_stats;
   // the submit/wait path's results: regions written densely (read r's at
   // h_dense[h_off[r] ..]) by dense_copy_kernel straight into pinned memory;
@@ -98,6 +110,16 @@ struct Slot {
   std::chrono::steady_clock::time_point t_submit;
   bwagpu_stats_t last{};
   int64_t h2d = 0, d2h = 0;
+  // what the slot itself created, drained first; its buffers free themselves afterwards
+  ~Slot() {
+    for (hipStream_t x : {stream, spec.side})
+      if (x) {
+        (void)hipStreamSynchronize(x);
+        (void)hipStreamDestroy(x);
+      }
+    for (hipEvent_t e : {ev0, ev1, ev2, ev3, spec.fork, spec.join})
+      if (e) (void)hipEventDestroy(e);
+  }
 };
 
 inline hipError_t lazy_stream(Slot& s, hipStream_t* st) {
@@ -120,11 +142,6 @@ struct Staging {
   DevBuf seq_off, reg_off, out_off;  // offsets, relative to what is copied
   DevBuf n, out_n, n_pri, status, n_sw, mapq, sel;  // per read, per pair or per region
   DevBuf pes;                        // the four bwagpu_pestat_t
-  void release() {
-    for (DevBuf* b : {&regs, &out_regs, &seq, &seq_off, &reg_off, &out_off, &n, &out_n, &n_pri, &status, &n_sw, &mapq,
-                      &sel, &pes})
-      b->release();
-  }
 };
 
 }  // namespace bwagpu
@@ -358,6 +375,8 @@ struct HostCall {
   int done(hipError_t e, const char* what) { return e == hipSuccess ? BWAGPU_OK : hip_fail(ctx, e, what); }
   // at least one element, so that the kernels get a pointer
   int reserve(DevBuf& b, size_t bytes) { return done(b.ensure(std::max<size_t>(bytes, 1)), "hipMalloc"); }
+  template <class T>
+  int reserve(DevBuf& b, T*& out, size_t n) { return done(b.get(out, n), "hipMalloc"); }  // n elements of T -> out
   int up(DevBuf& b, const void* src, size_t bytes, size_t slack = 0) {  // slack: bytes a kernel may read past the end
     if (int rc = reserve(b, bytes + slack)) return rc;
     if (bytes) HIPC(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st), "H2D");

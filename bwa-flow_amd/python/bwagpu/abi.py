@@ -216,6 +216,7 @@ PROTOS = {
     "bwagpu_debug_set_trace": (C.c_int, [_VP, _VP]),
     "bwagpu_prof_start": (C.c_int, [_VP, C.c_int]),
     "bwagpu_debug_fail_wait": (C.c_int, [_VP, C.c_int, C.c_int]),
+    "bwagpu_debug_live_buffers": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "bwagpu_debug_spec_counters": (C.c_int, [_VP, _VP, _VP]),
     "bwagpu_debug_occupancy": (C.c_int, [_VP, _VP, _VP]),
     "bwagpu_debug_spec_ext": (C.c_int, [_VP, _VP, _VP, C.c_int32]),

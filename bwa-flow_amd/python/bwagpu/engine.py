@@ -623,6 +623,15 @@ class Engine:
         """tests: the first round's plan of later mate_rescue calls leaves every k-th task out (0 = off)"""
         self._check(self.lib.bwagpu_debug_rescue_drop(self.ctx, int(k)), "debug_rescue_drop")
 
+    @staticmethod
+    def debug_live_buffers() -> tuple[int, int]:
+        """-> (buffers, bytes) that all contexts of this process hold at the moment"""
+        n, b = C.c_int64(), C.c_int64()
+        rc = abi.load().bwagpu_debug_live_buffers(C.byref(n), C.byref(b))
+        if rc != abi.OK:
+            raise BwaGpuError(rc, "debug_live_buffers")
+        return n.value, b.value
+
     def debug_rescue_times(self) -> dict:
         """the last mate_rescue* call by HIP events, summed over its rounds (waits for it)"""
         out = np.zeros(4, np.float64)

@@ -44,6 +44,13 @@ int bwagpu_debug_set_trace(bwagpu_ctx_t *ctx, void *dev_ptr);
    bwagpu_chain2aln_wait calls, the next one returns `code` (e.g.
    BWAGPU_E_HANG, as a watchdog expiry does) with its batch left in flight */
 int bwagpu_debug_fail_wait(bwagpu_ctx_t *ctx, int after_n_waits, int code);
+/* tests of the contexts' lifetime: the grow-only device and pinned host buffers
+   that all contexts of this process hold at the moment (*n) and their
+   capacities' sum (*bytes).  Every such buffer belongs to a context, so a
+   bwagpu_destroy brings both back to what they were before its bwagpu_create
+   — without reading the device's free memory, which other processes change.
+   The resident reference (pac, contig table) is not counted. */
+int bwagpu_debug_live_buffers(int64_t *n, int64_t *bytes);
 
 /* kernel timing (bench.py's roofline): after bwagpu_prof_start(ctx, n) the
    next n launches of the dominant extension kernel (the first length bin's
