@@ -1,4 +1,10 @@
-// capi.hip — implementation of the C ABI declared in include/bwagpu.h.
+// capi.hip — the core of the C ABI declared in include/bwagpu.h: the context's
+// lifecycle, the side-stream probe and choice, mem_chain2aln's entries (submit /
+// wait / stage / results / device) with their dense-result kernels, and the
+// debug and profiling entries.  The stages after mem_chain2aln are in
+// capi_stages.hip, the task-list entries in capi_tasks.hip, seeding and
+// chaining in capi_seed.hip; a batch's host-side checks and staging copy are
+// plain C++ in batch_host.h.
 //
 // One context = one device.  It owns the HBM-resident reference (pac +
 // contig table), the scoring options, and BWAGPU_NUM_SLOTS independent
@@ -11,9 +17,6 @@
 
 #include <algorithm>
 #include <chrono>
-#include <condition_variable>
-#include <deque>
-#include <functional>
 #include <cstdio>
 #include <mutex>
 #include <new>
@@ -21,108 +24,15 @@
 #include <thread>
 #include <vector>
 
-#include "regpost.h"
-#include "seed.h"
-#include "chain.h"
+#include "batch_host.h"
 #include "ctx.h"
 #include "engine.h"
+#include "regpost.h"
 
 using namespace bwagpu;
 
 namespace {
 
-// A persistent pool for the host-side passes over a batch (the staging copy
-// and check of bwagpu_chain2aln_submit, seeding's validation and staging):
-// creating threads per call cost 20-50 us each, and far more when several
-// stage workers submit at once.  host_parallel(nt, f) runs f(1..nt-1) on the
-// pool and f(0) on the caller, and returns when all are done; pool tasks never
-// wait on the pool, so concurrent callers cannot deadlock.
-class PassPool {
- public:
-  static PassPool& get() {
-    static PassPool p(7);
-    return p;
-  }
-  void post(std::function<void()> f) {
-    {
-      std::lock_guard<std::mutex> g(mu_);
-      q_.push_back(std::move(f));
-    }
-    cv_.notify_one();
-  }
-  ~PassPool() {
-    {
-      std::lock_guard<std::mutex> g(mu_);
-      stop_ = true;
-    }
-    cv_.notify_all();
-    for (auto& t : th_) t.join();
-  }
-
- private:
-  explicit PassPool(int n) {
-    for (int i = 0; i < n; ++i) th_.emplace_back([this] { loop(); });
-  }
-  void loop() {
-    for (;;) {
-      std::function<void()> f;
-      {
-        std::unique_lock<std::mutex> g(mu_);
-        cv_.wait(g, [this] { return stop_ || !q_.empty(); });
-        if (q_.empty()) return;
-        f = std::move(q_.front());
-        q_.pop_front();
-      }
-      f();
-    }
-  }
-  std::mutex mu_;
-  std::condition_variable cv_;
-  std::deque<std::function<void()>> q_;
-  std::vector<std::thread> th_;
-  bool stop_ = false;
-};
-
-template <typename F>
-void host_parallel(int nt, F f) {
-  if (nt <= 1) {
-    f(0);
-    return;
-  }
-  int left = nt - 1;  // decremented under m: the caller cannot unwind before the last task released it
-  std::mutex m;
-  std::condition_variable done;
-  for (int t = 1; t < nt; ++t)
-    PassPool::get().post([&, t] {
-      f(t);
-      std::lock_guard<std::mutex> g(m);
-      if (--left == 0) done.notify_all();
-    });
-  f(0);
-  std::unique_lock<std::mutex> g(m);
-  done.wait(g, [&] { return left == 0; });
-}
-
-// layout of one batch inside a slot's single input allocation
-struct InLayout {
-  size_t seq_off, seq, rco, cso, rid, frac, seeds, total;
-  void make(const bwagpu_batch_t& b) {
-    size_t o = 0;
-    auto take = [&](size_t n) {
-      size_t at = o;
-      o += (n + 255) & ~(size_t)255;
-      return at;
-    };
-    seq_off = take(sizeof(int64_t) * (size_t)(b.n_reads + 1));
-    rco = take(sizeof(int32_t) * (size_t)(b.n_reads + 1));
-    cso = take(sizeof(int32_t) * (size_t)(b.n_chains + 1));
-    rid = take(sizeof(int32_t) * (size_t)b.n_chains);
-    frac = take(sizeof(float) * (size_t)b.n_chains);
-    seeds = take(sizeof(bwagpu_seed_t) * (size_t)b.n_seeds);
-    seq = take((size_t)b.seq_bytes);
-    total = o;
-  }
-};
 
 // Side-stream probes.  HIP maps every stream of the process onto one of
 // GPU_MAX_HW_QUEUES hardware queues (4 on the pool's boxes), and work on two
@@ -337,161 +247,6 @@ void destroy_ctx(bwagpu_ctx_t* ctx) {
   delete ctx;
 }
 
-// validate the flattened batch on the host (cheap O(n) checks so that a
-// malformed batch is an E_INVAL here, never an out-of-bounds access on device);
-// one pass over reads -> chains -> seeds, which also yields the longest read
-// the batch's dimensions and array pointers (O(1)): what the staging copy relies on
-int check_batch_header(bwagpu_ctx_t* ctx, const bwagpu_batch_t* b) {
-  if (!b) return fail(ctx, BWAGPU_E_INVAL, "batch is NULL");
-  if (b->n_reads < 0 || b->n_chains < 0 || b->n_seeds < 0 || b->seq_bytes < 0)
-    return fail(ctx, BWAGPU_E_INVAL, "negative batch dimension");
-  if (b->n_reads == 0) return BWAGPU_OK;
-  if (!b->seq_off || !b->read_chain_off || !b->chain_seed_off)
-    return fail(ctx, BWAGPU_E_INVAL, "NULL offset array");
-  if (b->seq_off[0] != 0 || b->seq_off[b->n_reads] != b->seq_bytes)
-    return fail(ctx, BWAGPU_E_INVAL, "seq_off does not span seq_bytes");
-  if (b->read_chain_off[0] != 0 || b->read_chain_off[b->n_reads] != b->n_chains)
-    return fail(ctx, BWAGPU_E_INVAL, "read_chain_off does not span n_chains");
-  if (b->chain_seed_off[0] != 0 || b->chain_seed_off[b->n_chains] != b->n_seeds)
-    return fail(ctx, BWAGPU_E_INVAL, "chain_seed_off does not span n_seeds");
-  if (b->n_chains && (!b->chain_rid || !b->chain_frac_rep)) return fail(ctx, BWAGPU_E_INVAL, "NULL chain array");
-  if (b->n_seeds && !b->seeds) return fail(ctx, BWAGPU_E_INVAL, "NULL seeds");
-  if (b->seq_bytes && !b->seq) return fail(ctx, BWAGPU_E_INVAL, "NULL seq");
-  return BWAGPU_OK;
-}
-
-// reads [r0, r1) of a header-checked batch: seq_off and the offsets monotone,
-// every read at most BWAGPU_MAX_READ_LEN (*bad_read), every seed inside its
-// read and inside [0, 2*l_pac).  -> 0 ok, 1 seq_off, 2 read too long, 3 rco,
-// 4 cso, 5 seed; *lmax = the longest read.
-int check_reads(const bwagpu_batch_t* b, int64_t l_pac, int r0, int r1, int64_t* lmax, int* bad_read) {
-  const int64_t two = l_pac << 1;
-  const int64_t* so = b->seq_off;
-  const int32_t* rco = b->read_chain_off;
-  const int32_t* cso = b->chain_seed_off;
-  const bwagpu_seed_t* sd = b->seeds;
-  int64_t lm = 0;
-  for (int r = r0; r < r1; ++r) {
-    const int64_t l = so[r + 1] - so[r];
-    if (l < 0) return 1;
-    if (l > BWAGPU_MAX_READ_LEN) {
-      *bad_read = r;
-      return 2;
-    }
-    lm = std::max(lm, l);
-    // every offset is range-checked BEFORE it indexes: a range may start
-    // anywhere, and a later read's failing check must not come after an
-    // earlier read walked past the caller's arrays
-    const int c0 = rco[r], c1 = rco[r + 1];
-    if (c0 < 0 || c1 < c0 || c1 > b->n_chains) return 3;
-    bool bad_seed = false;
-    for (int c = c0; c < c1; ++c) {
-      const int k0 = cso[c], k1 = cso[c + 1];
-      if (k0 < 0 || k1 < k0 || k1 > b->n_seeds) return 4;
-      for (int k = k0; k < k1; ++k) {  // branch-free accumulation: one test per read
-        const bwagpu_seed_t& s = sd[k];
-        bad_seed |= (s.qbeg < 0) | (s.len <= 0) | ((int64_t)s.qbeg + s.len > l) | (s.rbeg < 0) | (s.rbeg + s.len > two);
-      }
-    }
-    if (bad_seed) return 5;
-  }
-  *lmax = lm;
-  return 0;
-}
-
-// the first failing range's code as one sequential pass would report it
-int check_report(bwagpu_ctx_t* ctx, const bwagpu_batch_t* b, const int* code, const int* bad_read, int nt) {
-  for (int t = 0; t < nt; ++t) {
-    switch (code[t]) {
-      case 1: return fail(ctx, BWAGPU_E_INVAL, "seq_off not monotone");
-      case 2: {
-        char m[128];
-        snprintf(m, sizeof m, "read %d has length %lld > %d", bad_read[t],
-                 (long long)(b->seq_off[bad_read[t] + 1] - b->seq_off[bad_read[t]]), BWAGPU_MAX_READ_LEN);
-        return fail(ctx, BWAGPU_E_UNSUPPORTED, m);
-      }
-      case 3: return fail(ctx, BWAGPU_E_INVAL, "read_chain_off not monotone");
-      case 4: return fail(ctx, BWAGPU_E_INVAL, "chain_seed_off not monotone");
-      case 5: return fail(ctx, BWAGPU_E_INVAL, "seed outside its read or the reference");
-      default: break;
-    }
-  }
-  return BWAGPU_OK;
-}
-
-// every read, chain and seed (O(n), after check_batch_header): the longest read -> *lq_max_out
-int check_batch_seeds(bwagpu_ctx_t* ctx, const bwagpu_batch_t* b, int* lq_max_out) {
-  *lq_max_out = 0;
-  if (b->n_reads == 0) return BWAGPU_OK;
-  const int nt = b->n_seeds >= (1 << 16) ? 4 : 1;
-  int code[4] = {0, 0, 0, 0}, bad_read[4] = {0, 0, 0, 0};
-  int64_t lmaxs[4] = {0, 0, 0, 0};
-  host_parallel(nt, [&](int t) {
-    code[t] = check_reads(b, ctx->ref.l_pac, (int)((int64_t)b->n_reads * t / nt),
-                          (int)((int64_t)b->n_reads * (t + 1) / nt), &lmaxs[t], &bad_read[t]);
-  });
-  if (int rc = check_report(ctx, b, code, bad_read, nt)) return rc;
-  *lq_max_out = (int)std::max(std::max(lmaxs[0], lmaxs[1]), std::max(lmaxs[2], lmaxs[3]));
-  return BWAGPU_OK;
-}
-
-// The staging copy and the check in one pass (bwagpu_chain2aln_submit): nt
-// threads, each a read range in blocks of 1024 reads — a block's arrays are
-// copied into the pinned staging buffer h (layout L), then checked while still
-// in cache.  A block's copy ranges come from its boundary offsets, which are
-// range-checked first, so a malformed batch never makes the copy leave the
-// caller's arrays (sizes from the header); it is refused after the pass.
-int stage_and_check(bwagpu_ctx_t* ctx, const bwagpu_batch_t* b, char* h, const InLayout& L, int* lq_max_out) {
-  *lq_max_out = 0;
-  const int nr = b->n_reads;
-  if (nr == 0) return BWAGPU_OK;
-  constexpr int kBlk = 1024, kMaxT = 8;
-  const int nt = b->n_seeds >= (1 << 16) ? kMaxT : 1;
-  const int nblk = (nr + kBlk - 1) / kBlk;
-  int code[kMaxT] = {}, bad_read[kMaxT] = {};
-  int64_t lmaxs[kMaxT] = {};
-  auto work = [&](int t) {
-    // this thread's blocks: [nblk*t/nt, nblk*(t+1)/nt), in order
-    for (int k = (int)((int64_t)nblk * t / nt), ke = (int)((int64_t)nblk * (t + 1) / nt); k < ke; ++k) {
-      const int r0 = k * kBlk, r1 = std::min(nr, r0 + kBlk);
-      const int64_t b0 = b->seq_off[r0], b1 = b->seq_off[r1];
-      const int c0 = b->read_chain_off[r0], c1 = b->read_chain_off[r1];
-      if (b0 < 0 || b1 < b0 || b1 > b->seq_bytes) {
-        code[t] = 1;
-        return;
-      }
-      if (c0 < 0 || c1 < c0 || c1 > b->n_chains) {
-        code[t] = 3;
-        return;
-      }
-      const int k0 = b->chain_seed_off[c0], k1 = b->chain_seed_off[c1];
-      if (k0 < 0 || k1 < k0 || k1 > b->n_seeds) {
-        code[t] = 4;
-        return;
-      }
-      const int re = r1 == nr ? r1 + 1 : r1, ce = c1 == b->n_chains ? c1 + 1 : c1;  // the last block: the end offsets
-      memcpy(h + L.seq_off + sizeof(int64_t) * r0, b->seq_off + r0, sizeof(int64_t) * (size_t)(re - r0));
-      memcpy(h + L.rco + sizeof(int32_t) * r0, b->read_chain_off + r0, sizeof(int32_t) * (size_t)(re - r0));
-      memcpy(h + L.cso + sizeof(int32_t) * c0, b->chain_seed_off + c0, sizeof(int32_t) * (size_t)(ce - c0));
-      if (c1 > c0) {
-        memcpy(h + L.rid + sizeof(int32_t) * c0, b->chain_rid + c0, sizeof(int32_t) * (size_t)(c1 - c0));
-        memcpy(h + L.frac + sizeof(float) * c0, b->chain_frac_rep + c0, sizeof(float) * (size_t)(c1 - c0));
-      }
-      if (k1 > k0) memcpy(h + L.seeds + sizeof(bwagpu_seed_t) * k0, b->seeds + k0, sizeof(bwagpu_seed_t) * (size_t)(k1 - k0));
-      if (b1 > b0) memcpy(h + L.seq + b0, b->seq + b0, (size_t)(b1 - b0));
-      int64_t lm = 0;
-      if ((code[t] = check_reads(b, ctx->ref.l_pac, r0, r1, &lm, &bad_read[t]))) return;
-      lmaxs[t] = std::max(lmaxs[t], lm);
-    }
-  };
-  host_parallel(nt, work);
-  if (int rc = check_report(ctx, b, code, bad_read, nt)) return rc;
-  int64_t lm = 0;
-  for (int t = 0; t < nt; ++t) lm = std::max(lm, lmaxs[t]);
-  *lq_max_out = (int)lm;
-  return BWAGPU_OK;
-}
-
 // BWAGPU_C2A_PATH=fast: the wave-per-read kernels (chain2aln_fast_kernel /
 // chain2aln_kernel, DESIGN.md §3 "per-read kernels"); default: the speculative
 // path (extension tasks + selection passes)
@@ -508,10 +263,12 @@ size_t variant_lds(const DevOpt& o, int v, int lq_max) {
   return vk.kind == VK_FAST ? (size_t)(kBlock / 64) * fast_wave_lds(tb) : (size_t)tb * (kBlock / vk.G);
 }
 
+}  // namespace
+
 // Options that need more LDS per workgroup than a launch may take are refused
 // BEFORE anything is enqueued (a refusal after the H2D would leave a DMA
 // reading the slot's pinned staging buffer while the caller reuses the slot).
-int check_lds(bwagpu_ctx_t* ctx, int lq_max) {
+int bwagpu::check_lds(bwagpu_ctx_t* ctx, int lq_max) {
   if (!use_read_kernels()) {
     if (spec_redo_cap(tb_bytes_for(ctx->opt, std::max(lq_max, 1))) < 64)
       return fail(ctx, BWAGPU_E_UNSUPPORTED, "LDS row buffer too large for these options (w, pen_clip, read length)");
@@ -523,6 +280,8 @@ int check_lds(bwagpu_ctx_t* ctx, int lq_max) {
   }
   return BWAGPU_OK;
 }
+
+namespace {
 
 // The caller stream st of a spec-path batch: a side stream for its heavy
 // selection kernels on a hardware queue that none of this context's caller
@@ -654,10 +413,12 @@ int enqueue_spec(bwagpu_ctx_t* ctx, Slot& s, const DevBatch& db, int lq_max, bwa
   return BWAGPU_OK;
 }
 
+}  // namespace
+
 // enqueue prep + binning + the per-variant kernels for a batch whose arrays
 // are already in device memory (check_lds has passed for lq_max)
-int enqueue_chain2aln(bwagpu_ctx_t* ctx, Slot& s, const DevBatch& db, int lq_max, bwagpu_alnreg_t* d_out,
-                      int32_t* d_n, int64_t* d_stats, hipStream_t st) {
+int bwagpu::enqueue_chain2aln(bwagpu_ctx_t* ctx, Slot& s, const DevBatch& db, int lq_max, bwagpu_alnreg_t* d_out,
+                              int32_t* d_n, int64_t* d_stats, hipStream_t st) {
   if (!use_read_kernels()) return enqueue_spec(ctx, s, db, lq_max, d_out, d_n, d_stats, st);
   ChainWin* win = nullptr;
   bwagpu_seed_t* prog = nullptr;
@@ -691,8 +452,6 @@ int enqueue_chain2aln(bwagpu_ctx_t* ctx, Slot& s, const DevBatch& db, int lq_max
   }
   return BWAGPU_OK;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -783,8 +542,9 @@ int bwagpu_chain2aln_submit(bwagpu_ctx_t* ctx, int slot, const bwagpu_batch_t* b
   s.kept = false;
   s.slot_view = false;
   int lq_max = 0;
-  int rc = check_batch_header(ctx, b);
-  if (rc) return rc;
+  std::string why;
+  int rc = check_batch_header(b, &why);
+  if (rc) return fail(ctx, rc, why);
   HIPC(hipSetDevice(ctx->device), "hipSetDevice");
   s.t_submit = std::chrono::steady_clock::now();
   InLayout L;
@@ -815,12 +575,12 @@ int bwagpu_chain2aln_submit(bwagpu_ctx_t* ctx, int slot, const bwagpu_batch_t* b
   // enqueued before both are done, so a refused batch leaves no DMA reading
   // the staging buffer
   if (!staged && b->n_reads) {
-    rc = stage_and_check(ctx, b, h, L, &lq_max);
+    rc = stage_and_check(b, ctx->ref.l_pac, h, L, &lq_max, &why);
   } else {
     if (!staged) memcpy(h + L.cso, b->chain_seed_off, sizeof(int32_t) * (size_t)(b->n_chains + 1));
-    rc = check_batch_seeds(ctx, b, &lq_max);
+    rc = check_batch_seeds(b, ctx->ref.l_pac, &lq_max, &why);
   }
-  if (rc) return rc;
+  if (rc) return fail(ctx, rc, why);
   if ((rc = check_lds(ctx, lq_max))) return rc;
 
   hipStream_t st = nullptr;
@@ -1050,6 +810,12 @@ int bwagpu_chain2aln_device(bwagpu_ctx_t* ctx, const bwagpu_batch_t* db_in, bwag
   return enqueue_chain2aln(ctx, s, db, lq_bound, dev_out, dev_n, stats, st);
 }
 
+int bwagpu_set_device_read_len(bwagpu_ctx_t* ctx, int32_t max_len) {
+  if (!ctx || max_len < 1 || max_len > BWAGPU_MAX_READ_LEN) return BWAGPU_E_INVAL;
+  ctx->dev_read_len = max_len;
+  return BWAGPU_OK;
+}
+
 int bwagpu_debug_set_trace(bwagpu_ctx_t* ctx, void* dev_ptr) {
   if (!ctx) return BWAGPU_E_INVAL;
   HIPC(hipSetDevice(ctx->device), "hipSetDevice");
@@ -1249,595 +1015,3 @@ int bwagpu_last_stats(const bwagpu_ctx_t* ctx, int slot, bwagpu_stats_t* out) {
 }
 
 }  // extern "C"
-
-// ------------------------------------------------------------------ seeding
-extern "C" int bwagpu_set_bwt(bwagpu_ctx_t* ctx, const bwagpu_bwt_t* bwt) {
-  if (!ctx || !bwt || !bwt->bwt || bwt->bwt_size == 0) return BWAGPU_E_INVAL;
-  // the occurrence array covers every position: 16 words per 128 positions
-  if (bwt->bwt_size < ((bwt->seq_len + 127) >> 7) * 16 || bwt->L2[4] != bwt->seq_len || bwt->primary > bwt->seq_len)
-    return fail(ctx, BWAGPU_E_INVAL, "bwt header inconsistent with its occurrence array");
-  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
-  HIPC(ctx->bwt_words.ensure(sizeof(uint32_t) * bwt->bwt_size + 64), "hipMalloc");
-  HIPC(hipMemcpy(ctx->bwt_words.p, bwt->bwt, sizeof(uint32_t) * bwt->bwt_size, hipMemcpyHostToDevice), "H2D");
-  ctx->bwt.primary = bwt->primary;
-  for (int i = 0; i < 5; ++i) ctx->bwt.L2[i] = bwt->L2[i];
-  ctx->bwt.seq_len = bwt->seq_len;
-  ctx->bwt.bwt = ctx->bwt_words.as<uint32_t>();
-  {  // the device occurrence layout (seed.hip: 64-position blocks)
-    uint4* occ = nullptr;
-    uint64_t* sup = nullptr;
-    HIPC(ctx->occ_d.get(occ, 2 * (size_t)occ64_blocks(bwt->seq_len)), "hipMalloc");
-    ctx->bwt.sup_shift = ctx->sup_shift;
-    HIPC(ctx->sup_d.get(sup, 4 * (size_t)occ64_supers(bwt->seq_len, ctx->sup_shift)), "hipMalloc");
-    HIPC(hipMemset(occ, 0, 2 * sizeof(uint4) * (size_t)occ64_blocks(bwt->seq_len)), "memset");
-    hipStream_t st = nullptr;
-    HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
-    HIPC(launch_build_occ64(ctx->bwt, occ, sup, st), "build_occ64 launch");
-    HIPC(hipStreamSynchronize(st), "sync");
-    ctx->bwt.occ = occ;
-    ctx->bwt.sup = sup;
-  }
-  ctx->bwt.sa = nullptr;
-  ctx->bwt.sa_mask = 0;
-  ctx->bwt.sa_shift = 0;
-  ctx->bwt.sa_full32 = nullptr;
-  ctx->bwt.sa_full64 = nullptr;
-  if (bwt->sa) {
-    const int iv = bwt->sa_intv;
-    if (iv < 1 || (iv & (iv - 1)) || bwt->n_sa < bwt->seq_len / (uint64_t)iv + 1)
-      return fail(ctx, BWAGPU_E_INVAL, "suffix array sample interval / size inconsistent");
-    uint64_t* sa = nullptr;
-    HIPC(ctx->sa_d.get(sa, bwt->n_sa), "hipMalloc");
-    HIPC(hipMemcpy(sa, bwt->sa, sizeof(uint64_t) * bwt->n_sa, hipMemcpyHostToDevice), "H2D");
-    ctx->bwt.sa = sa;
-    ctx->bwt.sa_mask = (uint64_t)iv - 1;
-    while ((1 << ctx->bwt.sa_shift) < iv) ++ctx->bwt.sa_shift;
-    // every row's entry in HBM (one load per bwt_sa instead of a walk of ~sa_intv
-    // dependent occurrence lookups): 32-bit entries below 2^32 rows (chr21: 0.37
-    // GB), 64-bit above (GRCh38: 50 GB of the 288), within 64 GB and a quarter
-    // of the free memory; BWAGPU_SA_FULL=0 keeps the sampled walk, =64 forces
-    // 64-bit entries (tests)
-    const char* fe = getenv("BWAGPU_SA_FULL");
-    const bool narrow = bwt->seq_len < 0xffffffffull && !(fe && strcmp(fe, "64") == 0);
-    const uint64_t bytes = (bwt->seq_len + 1) * (narrow ? 4 : 8);
-    size_t free_b = 0, total_b = 0;
-    if (!(fe && strcmp(fe, "0") == 0) && iv > 1 && hipMemGetInfo(&free_b, &total_b) == hipSuccess &&
-        bytes <= ((uint64_t)64 << 30) && bytes <= free_b / 4) {
-      HIPC(ctx->sa_full.ensure((size_t)bytes), "hipMalloc");
-      hipStream_t st = nullptr;
-      HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
-      HIPC(launch_sa_expand(ctx->bwt, narrow ? ctx->sa_full.as<uint32_t>() : nullptr,
-                            narrow ? nullptr : ctx->sa_full.as<uint64_t>(), st),
-           "sa_expand launch");
-      HIPC(hipStreamSynchronize(st), "sync");
-      if (narrow) ctx->bwt.sa_full32 = ctx->sa_full.as<uint32_t>();
-      else ctx->bwt.sa_full64 = ctx->sa_full.as<uint64_t>();
-    }
-  }
-  ctx->has_bwt = true;
-  return BWAGPU_OK;
-}
-
-extern "C" int bwagpu_bwt_sa(bwagpu_ctx_t* ctx, int64_t n, const uint64_t* k, uint64_t* out) {
-  if (!ctx || n < 0 || (n && (!k || !out))) return BWAGPU_E_INVAL;
-  if (!ctx->has_bwt || !ctx->bwt.sa) return fail(ctx, BWAGPU_E_INVAL, "no suffix array: pass it to bwagpu_set_bwt");
-  for (int64_t i = 0; i < n; ++i)
-    if (k[i] > ctx->bwt.seq_len) return fail(ctx, BWAGPU_E_INVAL, "BWT position past seq_len");
-  if (n == 0) return BWAGPU_OK;
-  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
-  hipStream_t st = nullptr;
-  HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
-  uint64_t *d_k = nullptr, *d_out = nullptr;
-  HIPC(ctx->sa_in.get(d_k, (size_t)n), "hipMalloc");
-  HIPC(ctx->sa_out.get(d_out, (size_t)n), "hipMalloc");
-  HIPC(hipMemcpyAsync(d_k, k, sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, st), "H2D");
-  HIPC(launch_bwt_sa(ctx->bwt, n, d_k, d_out, st), "bwt_sa launch");
-  HIPC(hipMemcpyAsync(out, d_out, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipStreamSynchronize(st), "sync");
-  return BWAGPU_OK;
-}
-
-namespace {
-
-// the checks of bwagpu_collect_intv's arguments; *bases = the batch's bases
-// The pinned staging buffer of seeding's reads (seq_off, then the bases),
-// once the previous call's H2D out of it is done (a caller that returned
-// early on an error never synchronized its stream)
-int seed_pin(bwagpu_ctx_t* ctx, int32_t n_reads, int64_t nb, char** pin) {
-  if (ctx->sdh_done) HIPC(hipEventSynchronize(ctx->sdh_done), "hipEventSynchronize");
-  else HIPC(hipEventCreateWithFlags(&ctx->sdh_done, hipEventDisableTiming), "hipEventCreate");
-  HIPC(ctx->sdh_in.ensure(sizeof(int64_t) * ((size_t)n_reads + 1) + (size_t)nb), "hipHostMalloc");
-  *pin = ctx->sdh_in.as<char>();
-  return BWAGPU_OK;
-}
-
-// Checks a seeding batch: the read lengths and every base (nt4: 0..4), on up
-// to 8 threads for a batch of megabases.  stage: the same pass also copies
-// the reads into the pinned staging buffer (seed_pin; seed_enqueue then skips
-// its copy).  *lq_max (optional) = the longest read.
-int seed_validate(bwagpu_ctx_t* ctx, const bwagpu_seedopt_t* opt, int32_t n_reads, const int64_t* seq_off,
-                  const uint8_t* seq, int64_t* bases, bool stage = false, int* lq_max = nullptr) {
-  if (!ctx->has_bwt) return fail(ctx, BWAGPU_E_INVAL, "no FM-index: call bwagpu_set_bwt first");
-  if (opt->min_seed_len < 1 || opt->split_width < 0) return fail(ctx, BWAGPU_E_INVAL, "bad seeding options");
-  *bases = 0;
-  if (lq_max) *lq_max = 0;
-  if (n_reads == 0) return BWAGPU_OK;
-  const int64_t nb = seq_off[n_reads] - seq_off[0];
-  if (seq_off[0] != 0 || nb < 0 || (nb && !seq)) return fail(ctx, BWAGPU_E_INVAL, "seq_off must start at 0");
-  char* pin = nullptr;
-  if (stage) {
-    int rc = seed_pin(ctx, n_reads, nb, &pin);
-    if (rc) return rc;
-  }
-  const size_t ob = sizeof(int64_t) * ((size_t)n_reads + 1);
-  // one thread takes ~1 ms per 10 Mbases
-  const int nt = nb >= (1 << 22) ? 8 : 1;
-  int len_bad[8] = {}, base_bad[8] = {};
-  int64_t lms[8] = {};
-  auto part = [&](int t) {
-    int64_t lm = 0;
-    for (int32_t r = (int32_t)((int64_t)n_reads * t / nt); r < (int32_t)((int64_t)n_reads * (t + 1) / nt); ++r) {
-      const int64_t l = seq_off[r + 1] - seq_off[r];
-      if (l < 0) len_bad[t] |= 1;
-      if (l > BWAGPU_MAX_SEED_READ) len_bad[t] |= 2;
-      lm = std::max(lm, l);
-    }
-    lms[t] = lm;
-    if (pin && t == 0) memcpy(pin, seq_off, ob);
-    // eight bytes at a time: (b & 0x7f) + 0x7b carries into bit 7 iff b > 4
-    int64_t i = (nb * t / nt) & ~(int64_t)7;
-    const int64_t e = t == nt - 1 ? nb : (nb * (t + 1) / nt) & ~(int64_t)7;
-    uint64_t bad = 0;
-    char* const dst = pin ? pin + ob : nullptr;
-    for (; i + 8 <= e; i += 8) {
-      uint64_t w;
-      memcpy(&w, seq + i, 8);
-      bad |= (((w & 0x7f7f7f7f7f7f7f7fULL) + 0x7b7b7b7b7b7b7b7bULL) | w) & 0x8080808080808080ULL;
-      if (dst) memcpy(dst + i, &w, 8);
-    }
-    for (; i < e; ++i) {
-      bad |= seq[i] > 4;
-      if (dst) dst[i] = (char)seq[i];
-    }
-    base_bad[t] = bad != 0;
-  };
-  host_parallel(nt, part);
-  int lb = 0, bb = 0;
-  int64_t lm = 0;
-  for (int t = 0; t < nt; ++t) {
-    lb |= len_bad[t];
-    bb |= base_bad[t];
-    lm = std::max(lm, lms[t]);
-  }
-  if (lb & 1) return fail(ctx, BWAGPU_E_INVAL, "seq_off not monotone");
-  if (lb & 2) return fail(ctx, BWAGPU_E_UNSUPPORTED, "read longer than BWAGPU_MAX_SEED_READ");
-  if (bb) return fail(ctx, BWAGPU_E_INVAL, "read base > 4 (bases are nt4)");
-  *bases = nb;
-  if (lq_max) *lq_max = (int)lm;
-  return BWAGPU_OK;
-}
-
-// H2D of the reads (when upload) and mem_collect_intv into per-read slots of
-// max_per_read intervals (ctx->sd_*), enqueued on st
-int seed_enqueue(bwagpu_ctx_t* ctx, const bwagpu_seedopt_t* opt, int32_t n_reads, const int64_t* seq_off,
-                 const uint8_t* seq, int64_t bases, int32_t max_per_read, bool upload, hipStream_t st, SeedArgs& a,
-                 bool staged = false) {
-  a = SeedArgs{};
-  HIPC(ctx->sd_off.get(a.seq_off, (size_t)n_reads + 1), "hipMalloc");
-  HIPC(ctx->sd_seq.ensure((size_t)bases + 1), "hipMalloc");
-  HIPC(ctx->sd_out.get(a.out, (size_t)n_reads * (size_t)max_per_read), "hipMalloc");
-  HIPC(ctx->sd_n.get(a.out_n, (size_t)n_reads), "hipMalloc");
-  HIPC(ctx->sd_scratch.get(a.scratch, (size_t)seed_scratch_entries(bases, n_reads)), "hipMalloc");
-  if (upload) {  // through a pinned staging buffer filled on a few threads (a pageable H2D runs at a fraction)
-    const size_t ob = sizeof(int64_t) * ((size_t)n_reads + 1);
-    char* pin = ctx->sdh_in.as<char>();
-    if (!staged) {  // else seed_validate's pass filled it
-      int rc = seed_pin(ctx, n_reads, bases, &pin);
-      if (rc) return rc;
-      const int nt = bases >= (1 << 22) ? 8 : 1;
-      auto part = [&](int t) {
-        const size_t b0 = (size_t)bases * t / nt, b1 = (size_t)bases * (t + 1) / nt;
-        memcpy(pin + ob + b0, seq + b0, b1 - b0);
-        if (t == 0) memcpy(pin, seq_off, ob);
-      };
-      host_parallel(nt, part);
-    }
-    HIPC(hipMemcpyAsync(ctx->sd_off.p, pin, ob, hipMemcpyHostToDevice, st), "H2D");
-    if (bases) HIPC(hipMemcpyAsync(ctx->sd_seq.p, pin + ob, (size_t)bases, hipMemcpyHostToDevice, st), "H2D");
-    HIPC(hipEventRecord(ctx->sdh_done, st), "hipEventRecord");
-  }
-  a.n_reads = n_reads;
-  a.seq = ctx->sd_seq.as<uint8_t>();
-  a.max_per_read = max_per_read;
-  a.min_seed_len = opt->min_seed_len;
-  a.split_width = opt->split_width;
-  a.max_mem_intv = opt->max_mem_intv;
-  a.split_len = (int)(opt->min_seed_len * opt->split_factor + .499);  // bwamem.c:124
-  HIPC(ctx->sd_heavy.ensure(sizeof(int32_t) * (3 * (size_t)n_reads + 1)), "hipMalloc");
-  a.budget = ctx->seed_budget;
-  a.heavy = ctx->sd_heavy.as<int32_t>() + 1;
-  a.n_heavy = ctx->sd_heavy.as<int32_t>();
-  a.flags = a.heavy + n_reads;
-  a.p3_n = a.flags + n_reads;
-  if (getenv("BWAGPU_SEED_DBG")) {  // per-lane tier-1 stamps (tools_dev)
-    HIPC(ctx->sd_dbg.get(a.dbg, 8 * (size_t)n_reads), "hipMalloc");
-    HIPC(hipMemsetAsync(a.dbg, 0, sizeof(int64_t) * 8 * (size_t)n_reads, st), "memset");
-  }
-  HIPC(launch_collect_intv(ctx->bwt, a, st), "collect_intv launch");
-  return BWAGPU_OK;
-}
-
-}  // namespace
-
-extern "C" int bwagpu_collect_intv(bwagpu_ctx_t* ctx, const bwagpu_seedopt_t* opt, int32_t n_reads,
-                                   const int64_t* seq_off, const uint8_t* seq, int32_t max_per_read,
-                                   bwagpu_intv_t* out, int64_t out_cap, int32_t* out_n) {
-  if (!ctx || !opt || n_reads < 0 || max_per_read < 1 || out_cap < 0 || (n_reads && (!seq_off || !out_n)) ||
-      (out_cap && !out))
-    return BWAGPU_E_INVAL;
-  int64_t bases = 0;
-  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
-  int rc = seed_validate(ctx, opt, n_reads, seq_off, seq, &bases, true);
-  if (rc) return rc;
-  if (n_reads == 0) return BWAGPU_OK;
-  hipStream_t st = nullptr;
-  HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
-  SeedArgs a;
-  if ((rc = seed_enqueue(ctx, opt, n_reads, seq_off, seq, bases, max_per_read, true, st, a, true))) return rc;
-  HIPC(hipMemcpyAsync(out_n, ctx->sd_n.p, sizeof(int32_t) * (size_t)n_reads, hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipStreamSynchronize(st), "sync");
-  if (const char* dp = getenv("BWAGPU_SEED_DBG")) {
-    std::vector<int64_t> d(8 * (size_t)n_reads);
-    HIPC(hipMemcpy(d.data(), ctx->sd_dbg.p, sizeof(int64_t) * d.size(), hipMemcpyDeviceToHost), "D2H");
-    if (FILE* f = fopen(dp, "ab")) {
-      fwrite(d.data(), sizeof(int64_t), d.size(), f);
-      fclose(f);
-    }
-  }
-  // pack the per-read slots back to back (read order) and copy only those
-  std::vector<int64_t> off((size_t)n_reads + 1, 0);
-  for (int32_t r = 0; r < n_reads; ++r) {
-    if (out_n[r] < 0) return fail(ctx, BWAGPU_E_UNSUPPORTED, "a read has more than max_per_read intervals");
-    off[(size_t)r + 1] = off[(size_t)r] + out_n[r];
-  }
-  const int64_t total = off[(size_t)n_reads];
-  if (total > out_cap) return fail(ctx, BWAGPU_E_UNSUPPORTED, "the batch has more than out_cap intervals");
-  if (total == 0) return BWAGPU_OK;
-  int64_t* d_off = nullptr;
-  bwagpu_intv_t* d_pack = nullptr;
-  HIPC(ctx->sd_poff.get(d_off, off.size()), "hipMalloc");
-  HIPC(ctx->sd_pack.get(d_pack, (size_t)total), "hipMalloc");
-  HIPC(hipMemcpyAsync(d_off, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice, st), "H2D");
-  HIPC(launch_pack_intv(a, d_off, d_pack, st), "pack launch");
-  HIPC(hipMemcpyAsync(out, d_pack, sizeof(bwagpu_intv_t) * (size_t)total, hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipStreamSynchronize(st), "sync");
-  return BWAGPU_OK;
-}
-
-extern "C" int bwagpu_debug_seed_budget(bwagpu_ctx_t* ctx, int32_t budget) {
-  if (!ctx || budget < 0) return BWAGPU_E_INVAL;
-  ctx->seed_budget = budget;
-  return BWAGPU_OK;
-}
-
-extern "C" int bwagpu_set_device_read_len(bwagpu_ctx_t* ctx, int32_t max_len) {
-  if (!ctx || max_len < 1 || max_len > BWAGPU_MAX_READ_LEN) return BWAGPU_E_INVAL;
-  ctx->dev_read_len = max_len;
-  return BWAGPU_OK;
-}
-
-extern "C" int bwagpu_debug_sup_shift(bwagpu_ctx_t* ctx, int32_t shift) {
-  if (!ctx || shift < 7 || shift > 32) return BWAGPU_E_INVAL;  // a superblock is whole 128-position bwa blocks
-  ctx->sup_shift = shift;
-  return BWAGPU_OK;
-}
-
-// ------------------------------------------------------------------ chaining
-// SeqsToChains on the device (chain.h): mem_collect_intv, mem_chain's body,
-// mem_chain_flt and mem_flt_chained_seeds, with three host round trips for
-// sizes (positions, mem_seed_sw tasks when a read is long enough for them,
-// chains out).
-namespace {
-
-int run_chaining(bwagpu_ctx_t* ctx, const bwagpu_seedopt_t* sopt, const bwagpu_chainopt_t* copt, int32_t n_reads,
-                 const int64_t* seq_off, const uint8_t* seq, bool raw, hipStream_t st, int64_t* n_chains,
-                 int64_t* n_seeds, int* lq_max_out, bool to_host = false) {
-  *n_chains = *n_seeds = 0;
-  if (copt->max_occ < 1 || copt->max_chain_gap < 0 || copt->max_chain_extend < 0 || !(copt->mask_level >= 0) ||
-      !(copt->drop_ratio >= 0))
-    return fail(ctx, BWAGPU_E_INVAL, "bad chaining options");
-  if (!ctx->bwt.sa) return fail(ctx, BWAGPU_E_INVAL, "no suffix array: pass it to bwagpu_set_bwt");
-  {  // the largest LDS bin's arena (chain.h) needs gfx950's 160 KB per workgroup
-    int lds_max = 0;
-    HIPC(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device), "attribute");
-    if ((size_t)lds_max < lds_arena(kBinCap[kLdsBins - 1]))
-      return fail(ctx, BWAGPU_E_UNSUPPORTED, "device LDS per workgroup is smaller than the chaining arena");
-  }
-  int64_t bases = 0;
-  int lq_max = 0;
-  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
-  int rc = seed_validate(ctx, sopt, n_reads, seq_off, seq, &bases, true, &lq_max);  // + the staging copy
-  if (rc) return rc;
-  *lq_max_out = lq_max;
-  if (n_reads == 0) return BWAGPU_OK;
-  // mem_flt_chained_seeds' gate and min_HSP_score per read length
-  // (bwamem.c:609-611), in the host's double arithmetic
-  std::vector<int32_t> tab((size_t)lq_max + 1, -1);
-  bool any_sw = false;
-  {
-    std::vector<char> has((size_t)lq_max + 1, 0);
-    for (int32_t r = 0; r < n_reads; ++r) has[(size_t)(seq_off[r + 1] - seq_off[r])] = 1;
-    for (int l = 1; l <= lq_max; ++l) {
-      const double min_l = copt->min_chain_weight ? 1.1f * copt->min_chain_weight : 5.5f * log((double)l);
-      if (min_l > 0.05f * l) continue;
-      tab[(size_t)l] = (int)(ctx->opt.a * min_l + .499);
-      any_sw = any_sw || (has[(size_t)l] && l >= sopt->min_seed_len);
-    }
-  }
-  if (!raw && any_sw)
-    if (const char* why = align2_opt_unsupported(ctx->opt)) return fail(ctx, BWAGPU_E_UNSUPPORTED, why);
-  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
-  int32_t mpr = std::max(64, 2 * lq_max + 64);  // interval slots per read (grown on overflow)
-  SeedArgs sa;
-  if ((rc = seed_enqueue(ctx, sopt, n_reads, seq_off, seq, bases, mpr, true, st, sa, true))) return rc;
-  const size_t nr = (size_t)n_reads;
-  ChainArgs a{};
-  int64_t* tot = nullptr;
-  HIPC(ctx->ch_npos.get(a.n_pos, nr), "hipMalloc");
-  HIPC(ctx->ch_posoff.get(a.pos_off, nr + 1), "hipMalloc");
-  HIPC(ctx->ch_frac.get(a.frac_rep, nr), "hipMalloc");
-  HIPC(ctx->ch_nout.get(a.n_out, nr), "hipMalloc");
-  HIPC(ctx->ch_noseed.get(a.n_oseed, nr), "hipMalloc");
-  HIPC(ctx->ch_nsw.get(a.n_sw, nr), "hipMalloc");
-  HIPC(ctx->ch_need.get(a.need, 1), "hipMalloc");
-  HIPC(ctx->ch_swtab.get(a.sw_tab, tab.size()), "hipMalloc");
-  HIPC(ctx->chh_tot.get(tot, 8), "hipHostMalloc");
-  HIPC(hipMemcpyAsync(ctx->ch_swtab.p, tab.data(), sizeof(int32_t) * tab.size(), hipMemcpyHostToDevice, st), "H2D");
-  a.n_reads = n_reads;
-  a.seq_off = sa.seq_off;
-  a.seq = sa.seq;
-  a.max_occ = copt->max_occ;
-  a.max_chain_gap = copt->max_chain_gap;
-  a.min_chain_weight = copt->min_chain_weight;
-  a.max_chain_extend = copt->max_chain_extend;
-  a.mask_level = copt->mask_level;
-  a.drop_ratio = copt->drop_ratio;
-  a.min_seed_len = sopt->min_seed_len;
-  a.w = ctx->opt.w;
-  a.a = ctx->opt.a;
-  a.raw = raw ? 1 : 0;
-  a.l_pac = ctx->ref.l_pac;
-  a.n_seqs = ctx->ref.n_seqs;
-  a.ann_off = ctx->ref.ann_offset;
-  a.ann_len = ctx->ref.ann_len;
-  a.is_alt = ctx->has_alt ? ctx->ch_alt.as<uint8_t>() : nullptr;
-  a.pac = ctx->ref.pac;
-  for (int pass = 0;; ++pass) {  // positions per read; a read out of interval slots reruns the search
-    a.intv = sa.out;
-    a.intv_n = sa.out_n;
-    a.max_per_read = sa.max_per_read;
-    HIPC(hipMemsetAsync(a.need, 0, sizeof(int32_t), st), "memset");
-    HIPC(launch_chain_count(a, st), "chain_count launch");
-    HIPC(launch_scan_i32(a.n_pos, a.pos_off, n_reads, st), "scan launch");
-    HIPC(hipMemcpyAsync(tot, a.pos_off + n_reads, sizeof(int64_t), hipMemcpyDeviceToHost, st), "D2H");
-    HIPC(hipMemcpyAsync(tot + 1, a.need, sizeof(int32_t), hipMemcpyDeviceToHost, st), "D2H");
-    HIPC(hipStreamSynchronize(st), "sync");
-    const int32_t need = (int32_t)(uint32_t)tot[1];
-    if (need <= 0) break;
-    if (pass) return fail(ctx, BWAGPU_E_DEVICE, "interval slots still overflow");
-    if ((rc = seed_enqueue(ctx, sopt, n_reads, seq_off, seq, bases, need, false, st, sa))) return rc;
-  }
-  const int64_t P = tot[0];
-  const size_t np = (size_t)P;
-  HIPC(ctx->ch_kpos.get(a.kpos, np), "hipMalloc");
-  HIPC(ctx->ch_rbeg.get(a.rbeg, np), "hipMalloc");
-  HIPC(ctx->ch_qinfo.get(a.qinfo, np), "hipMalloc");
-  HIPC(ctx->ch_label.get(a.label, np), "hipMalloc");
-  HIPC(ctx->ch_score.get(a.score, np), "hipMalloc");
-  HIPC(ctx->ch_slist.get(a.slist, np), "hipMalloc");
-  HIPC(ctx->ch_ord.get(a.ord, np), "hipMalloc");
-  HIPC(ctx->ch_chains.get(a.lchains, np), "hipMalloc");
-  HIPC(ctx->ch_nodes.get(a.lnodes, (size_t)node_total(P, n_reads)), "hipMalloc");
-  HIPC(ctx->ch_ochains.get(a.ochains, np), "hipMalloc");
-  HIPC(ctx->ch_oslist.get(a.oslist, np), "hipMalloc");
-  HIPC(ctx->ch_bins.ensure(sizeof(int32_t) * ((size_t)(kLdsBins + 1) * nr + kLdsBins + 1)), "hipMalloc");
-  a.bin_count = ctx->ch_bins.as<int32_t>();
-  a.bin_list = a.bin_count + kLdsBins + 1;
-  HIPC(launch_chain_emit(a, st), "chain_emit launch");
-  if (P) HIPC(launch_bwt_sa(ctx->bwt, P, a.kpos, a.rbeg, st), "bwt_sa launch");
-  if (!ctx->ch_cs.fork) {
-    HIPC(hipStreamCreateWithFlags(&ctx->ch_cs.side[0], hipStreamNonBlocking), "hipStreamCreate");
-    HIPC(hipEventCreateWithFlags(&ctx->ch_cs.join[0], hipEventDisableTiming), "hipEventCreate");
-    HIPC(hipEventCreateWithFlags(&ctx->ch_cs.fork, hipEventDisableTiming), "hipEventCreate");
-  }
-  const char* dbg_env = getenv("BWAGPU_CHAIN_PHASES");
-  const bool dbg_on = dbg_env && dbg_env[0] == '1';
-  if (dbg_on) {
-    HIPC(ctx->ch_dbg.get(a.dbg, 8 * nr), "hipMalloc");
-    HIPC(hipMemsetAsync(a.dbg, 0, sizeof(uint64_t) * 8 * nr, st), "memset");
-  }
-  HIPC(launch_chain_build(a, st, ctx->ch_cs), "chain_build launch");
-  if (dbg_on) {  // the slowest reads' phase times (100 MHz ticks) to stderr
-    std::vector<uint64_t> d(8 * nr);
-    HIPC(hipMemcpyAsync(d.data(), ctx->ch_dbg.p, sizeof(uint64_t) * 8 * nr, hipMemcpyDeviceToHost, st), "D2H");
-    HIPC(hipStreamSynchronize(st), "sync");
-    std::vector<int> idx;
-    for (int r = 0; r < n_reads; ++r)
-      if (d[8 * (size_t)r + 6]) idx.push_back(r);
-    std::sort(idx.begin(), idx.end(), [&](int x, int y) {
-      return d[8 * (size_t)x + 6] - d[8 * (size_t)x] > d[8 * (size_t)y + 6] - d[8 * (size_t)y];
-    });
-    for (size_t k = 0; k < idx.size() && k < 8; ++k) {
-      const uint64_t* q = &d[8 * (size_t)idx[k]];
-      fprintf(stderr, "[chain phases] read %d pos %u chains %u: loop %.1f trav %.1f prep %.1f sort %.1f flt %.1f out %.1f us\n",
-              idx[k], (unsigned)(q[7] & 0xffffffff), (unsigned)(q[7] >> 32), (q[1] - q[0]) / 100.0,
-              (q[2] - q[1]) / 100.0, (q[3] ? q[3] - q[2] : 0) / 100.0, (q[4] ? q[4] - q[3] : 0) / 100.0,
-              (q[5] - (q[4] ? q[4] : q[2])) / 100.0, (q[6] - q[5]) / 100.0);
-    }
-  }
-  if (!raw && any_sw) {  // mem_flt_chained_seeds: every kept seed of a long read realigned
-    int64_t* sw_off = nullptr;
-    HIPC(ctx->ch_swoff.get(sw_off, nr + 1), "hipMalloc");
-    HIPC(launch_scan_i32(a.n_sw, sw_off, n_reads, st), "scan launch");
-    HIPC(hipMemcpyAsync(tot + 2, sw_off + n_reads, sizeof(int64_t), hipMemcpyDeviceToHost, st), "D2H");
-    HIPC(hipStreamSynchronize(st), "sync");
-    const int64_t T = tot[2];
-    if (T > INT32_MAX / 2) return fail(ctx, BWAGPU_E_UNSUPPORTED, "too many seeds to realign");
-    if (T) {
-      ChainSw sw{};
-      bwagpu_kswr_t* res = nullptr;
-      sw.sw_off = sw_off;
-      HIPC(ctx->ch_swtasks.get(sw.tasks, (size_t)T), "hipMalloc");
-      HIPC(ctx->ch_swt.get(sw.tpool, (size_t)kSwWin * (size_t)T), "hipMalloc");
-      HIPC(ctx->ch_swskip.get(sw.skip, (size_t)T), "hipMalloc");
-      HIPC(ctx->ch_swres.get(res, (size_t)T), "hipMalloc");
-      HIPC(ctx->ch_swscr.ensure(8 * ((size_t)kSwWin * (size_t)T + (size_t)T)), "hipMalloc");
-      sw.res = res;
-      HIPC(launch_chain_sw_prep(a, sw, st), "chain_sw_prep launch");
-      if ((rc = bwagpu_align2_device(ctx, (int32_t)T, sw.tasks, sa.seq, sw.tpool, res, ctx->ch_swscr.p, st))) return rc;
-      HIPC(launch_chain_sw_apply(a, sw, st), "chain_sw_apply launch");
-    }
-  }
-  int64_t *oc_off = nullptr, *os_off = nullptr;
-  HIPC(ctx->ch_ocoff.get(oc_off, nr + 1), "hipMalloc");
-  HIPC(ctx->ch_osoff.get(os_off, nr + 1), "hipMalloc");
-  HIPC(launch_scan_i32(a.n_out, oc_off, n_reads, st), "scan launch");
-  HIPC(launch_scan_i32(a.n_oseed, os_off, n_reads, st), "scan launch");
-  HIPC(hipMemcpyAsync(tot + 3, oc_off + n_reads, sizeof(int64_t), hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipMemcpyAsync(tot + 4, os_off + n_reads, sizeof(int64_t), hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipStreamSynchronize(st), "sync");
-  const int64_t nc = tot[3], ns = tot[4];
-  if (nc > INT32_MAX - 1 || ns > INT32_MAX - 1) return fail(ctx, BWAGPU_E_UNSUPPORTED, "batch has too many chains");
-  ChainPack pk{};
-  pk.oc_off = oc_off;
-  pk.os_off = os_off;
-  HIPC(ctx->ch_rco.get(pk.read_chain_off, nr + 1), "hipMalloc");
-  HIPC(ctx->ch_cso.get(pk.chain_seed_off, (size_t)nc + 1), "hipMalloc");
-  HIPC(ctx->ch_rid.get(pk.chain_rid, (size_t)nc), "hipMalloc");
-  HIPC(ctx->ch_cfrac.get(pk.chain_frac, (size_t)nc), "hipMalloc");
-  HIPC(ctx->ch_out.get(pk.chains, (size_t)nc), "hipMalloc");
-  HIPC(ctx->ch_seeds.get(pk.seeds, (size_t)ns), "hipMalloc");
-  if (to_host) {  // bwagpu_seqs2chains: the chains written over PCIe into its pinned results (no D2H step)
-    HIPC(ctx->chh_rco.get(pk.read_chain_off, nr + 1), "hipHostMalloc");  // the host's pointers, replaced below
-    HIPC(ctx->chh_cso.get(pk.chain_seed_off, (size_t)nc + 1), "hipHostMalloc");
-    HIPC(ctx->chh_chains.get(pk.chains, (size_t)nc), "hipHostMalloc");
-    HIPC(ctx->chh_seeds.get(pk.seeds, (size_t)ns), "hipHostMalloc");
-    HIPC(hipHostGetDevicePointer((void**)&pk.read_chain_off, ctx->chh_rco.p, 0), "hipHostGetDevicePointer");
-    HIPC(hipHostGetDevicePointer((void**)&pk.chain_seed_off, ctx->chh_cso.p, 0), "hipHostGetDevicePointer");
-    HIPC(hipHostGetDevicePointer((void**)&pk.chains, ctx->chh_chains.p, 0), "hipHostGetDevicePointer");
-    HIPC(hipHostGetDevicePointer((void**)&pk.seeds, ctx->chh_seeds.p, 0), "hipHostGetDevicePointer");
-  }
-  HIPC(launch_chain_pack(a, pk, st), "chain_pack launch");
-  *n_chains = nc;
-  *n_seeds = ns;
-  return BWAGPU_OK;
-}
-
-}  // namespace
-
-extern "C" int bwagpu_set_alt(bwagpu_ctx_t* ctx, const uint8_t* is_alt) {
-  if (!ctx) return BWAGPU_E_INVAL;
-  if (!is_alt) {
-    ctx->has_alt = false;
-    return BWAGPU_OK;
-  }
-  HIPC(hipSetDevice(ctx->device), "hipSetDevice");
-  uint8_t* alt = nullptr;
-  HIPC(ctx->ch_alt.get(alt, (size_t)ctx->ref.n_seqs), "hipMalloc");
-  HIPC(hipMemcpy(alt, is_alt, (size_t)ctx->ref.n_seqs, hipMemcpyHostToDevice), "H2D");
-  ctx->has_alt = true;
-  return BWAGPU_OK;
-}
-
-extern "C" int bwagpu_seqs2chains(bwagpu_ctx_t* ctx, const bwagpu_seedopt_t* sopt, const bwagpu_chainopt_t* copt,
-                                  int32_t n_reads, const int64_t* seq_off, const uint8_t* seq, int32_t raw,
-                                  bwagpu_chains_t* out) {
-  if (!ctx || !sopt || !copt || !out || n_reads < 0 || (n_reads && !seq_off)) return BWAGPU_E_INVAL;
-  *out = bwagpu_chains_t{};
-  hipStream_t st = nullptr;
-  HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
-  int64_t nc = 0, ns = 0;
-  int lq = 0;
-  int rc = run_chaining(ctx, sopt, copt, n_reads, seq_off, seq, raw != 0, st, &nc, &ns, &lq, true);
-  if (rc) return rc;
-  const size_t nr = (size_t)n_reads;
-  int32_t *rco = nullptr, *cso = nullptr;
-  bwagpu_chain_t* chains = nullptr;
-  bwagpu_seed_t* seeds = nullptr;
-  HIPC(ctx->chh_rco.get(rco, nr + 1), "hipHostMalloc");
-  HIPC(ctx->chh_cso.get(cso, (size_t)nc + 1), "hipHostMalloc");
-  HIPC(ctx->chh_chains.get(chains, (size_t)nc), "hipHostMalloc");
-  HIPC(ctx->chh_seeds.get(seeds, (size_t)ns), "hipHostMalloc");
-  if (n_reads) HIPC(hipStreamSynchronize(st), "sync");  // chain_pack wrote the results into the pinned buffers
-  else rco[0] = cso[0] = 0;
-  *out = bwagpu_chains_t{n_reads, (int32_t)nc, ns, rco, cso, chains, seeds};
-  return BWAGPU_OK;
-}
-
-extern "C" int bwagpu_seqs2regions(bwagpu_ctx_t* ctx, const bwagpu_seedopt_t* sopt, const bwagpu_chainopt_t* copt,
-                                   int32_t n_reads, const int64_t* seq_off, const uint8_t* seq, int32_t* out_n,
-                                   const bwagpu_alnreg_t** regs, int64_t* n_regs) {
-  if (!ctx || !sopt || !copt || !regs || !n_regs || n_reads < 0 || (n_reads && (!seq_off || !out_n)))
-    return BWAGPU_E_INVAL;
-  *regs = nullptr;
-  *n_regs = 0;
-  for (int32_t r = 0; r < n_reads; ++r)
-    if (seq_off[r + 1] - seq_off[r] > BWAGPU_MAX_READ_LEN)
-      return fail(ctx, BWAGPU_E_UNSUPPORTED, "read longer than BWAGPU_MAX_READ_LEN");
-  hipStream_t st = nullptr;
-  HIPC(lazy_stream(ctx->slot[0], &st), "hipStreamCreate");
-  int64_t nc = 0, ns = 0;
-  int lq = 0;
-  int rc = run_chaining(ctx, sopt, copt, n_reads, seq_off, seq, false, st, &nc, &ns, &lq);
-  if (rc) return rc;
-  if (n_reads == 0) return BWAGPU_OK;
-  if ((rc = check_lds(ctx, lq))) return rc;
-  Slot& s = ctx->ch_slot;
-  const size_t nr = (size_t)n_reads;
-  bwagpu_alnreg_t *d_out = nullptr, *d_regc = nullptr, *h_regs = nullptr;
-  int32_t* d_n = nullptr;
-  int64_t *d_stats = nullptr, *d_regoff = nullptr;
-  HIPC(s.d_out.get(d_out, (size_t)ns), "hipMalloc(out)");
-  HIPC(s.d_n.get(d_n, nr), "hipMalloc(out_n)");
-  HIPC(s.d_stats.get(d_stats, ST_N), "hipMalloc(stats)");
-  HIPC(hipMemsetAsync(d_stats, 0, sizeof(int64_t) * ST_N, st), "memset stats");
-  DevBatch db;
-  db.n_reads = n_reads;
-  db.n_chains = (int32_t)nc;
-  db.n_seeds = (int32_t)ns;
-  db.seq_off = ctx->sd_off.as<int64_t>();
-  db.seq = ctx->sd_seq.as<uint8_t>();
-  db.read_chain_off = ctx->ch_rco.as<int32_t>();
-  db.chain_seed_off = ctx->ch_cso.as<int32_t>();
-  db.chain_rid = ctx->ch_rid.as<int32_t>();
-  db.chain_frac_rep = ctx->ch_cfrac.as<float>();
-  db.seeds = ctx->ch_seeds.as<bwagpu_seed_t>();
-  if ((rc = enqueue_chain2aln(ctx, s, db, lq, d_out, d_n, d_stats, st))) return rc;
-  if (ctx->post_flags) {  // bwagpu_set_regs_post: before the counts are scanned and the regions compacted
-    if ((rc = enqueue_regpost(ctx, ctx->post_opt, ctx->post_flags, ctx->post_id0, n_reads, db.seq_off, db.seq, nullptr,
-                              db.read_chain_off, db.chain_seed_off, d_out, d_n, d_stats, st)))
-      return rc;
-    ctx->post_id0 += n_reads;
-  }
-  HIPC(ctx->ch_regoff.get(d_regoff, nr + 1), "hipMalloc");
-  HIPC(launch_scan_i32(d_n, d_regoff, n_reads, st), "scan launch");
-  int64_t* tot = ctx->chh_tot.as<int64_t>();
-  HIPC(hipMemcpyAsync(tot + 5, d_regoff + n_reads, sizeof(int64_t), hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipMemcpyAsync(tot + 6, d_stats + ST_ERR, sizeof(int64_t), hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipMemcpyAsync(out_n, d_n, sizeof(int32_t) * nr, hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipStreamSynchronize(st), "sync");
-  const int64_t nreg = tot[5];
-  HIPC(ctx->ch_regc.get(d_regc, (size_t)nreg), "hipMalloc");
-  HIPC(ctx->chh_regs.get(h_regs, (size_t)nreg), "hipHostMalloc");
-  HIPC(launch_reg_compact(n_reads, db.read_chain_off, db.chain_seed_off, d_out, d_regoff, d_regc, st),
-       "reg_compact launch");
-  if (nreg) HIPC(hipMemcpyAsync(h_regs, d_regc, sizeof(bwagpu_alnreg_t) * (size_t)nreg, hipMemcpyDeviceToHost, st), "D2H");
-  HIPC(hipStreamSynchronize(st), "sync");
-  *regs = h_regs;
-  *n_regs = nreg;
-  if (tot[6] & ERR_LEN) return fail(ctx, BWAGPU_E_UNSUPPORTED, "read longer than BWAGPU_MAX_READ_LEN");
-  if (tot[6] & ERR_POST) return fail(ctx, BWAGPU_E_UNSUPPORTED, "a patch candidate's window exceeds 4096 bases");
-  if (tot[6] & ERR_RID)
-    return fail(ctx, BWAGPU_E_RESULTS, "a chain's first seed is not inside contig chain_rid (bwamem.c:669 assert)");
-  return BWAGPU_OK;
-}

@@ -1,6 +1,8 @@
 // ctx.h — what the translation units of the C ABI share (capi.hip,
-// capi_stages.hip, capi_tasks.hip): the context and its slots, grow-only
-// buffers, the error path, and the scaffold of a blocking host-buffer entry.
+// capi_seed.hip, capi_stages.hip, capi_tasks.hip): the context and its slots,
+// grow-only buffers, the error path, the chain2aln and post-processing passes
+// that more than one of them enqueues, and the scaffold of a blocking
+// host-buffer entry.
 // Internal: nothing here is part of include/bwagpu.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -196,8 +198,8 @@ struct bwagpu_ctx {
   static constexpr int kA2Streams = 4;
   hipStream_t a2_st[kA2Streams] = {};
   hipEvent_t a2_fork = nullptr, a2_join[kA2Streams] = {};
-  // seeding (bwagpu_set_bwt / bwagpu_collect_intv): the resident FM-index and
-  // the batch buffers
+  // seeding (capi_seed.hip: bwagpu_set_bwt / bwagpu_collect_intv): the resident
+  // FM-index and the batch buffers
   DevBuf bwt_words, sa_d, sa_in, sa_out, occ_d, sup_d, sa_full;
   bwagpu::DevBwt bwt{};
   bool has_bwt = false;
@@ -341,6 +343,12 @@ struct EventPair {
 int enqueue_regpost(bwagpu_ctx_t* ctx, const bwagpu_postopt_t& po, int32_t flags, int64_t id0, int32_t n_reads,
                     const int64_t* seq_off, const uint8_t* seq, const int64_t* reg_off, const int32_t* rco,
                     const int32_t* cso, bwagpu_alnreg_t* regs, int32_t* n, int64_t* stats, hipStream_t st);
+
+// mem_chain2aln over a batch in device memory (capi.hip): check_lds refuses options whose LDS row
+// buffers do not fit, before anything is enqueued; enqueue_chain2aln then fills d_out / d_n on st
+int check_lds(bwagpu_ctx_t* ctx, int lq_max);
+int enqueue_chain2aln(bwagpu_ctx_t* ctx, Slot& s, const DevBatch& db, int lq_max, bwagpu_alnreg_t* d_out,
+                      int32_t* d_n, int64_t* d_stats, hipStream_t st);
 
 // One blocking host-buffer entry of a stage, on slot[0]'s stream:
 //   begin();  up(...) / up_spans(...) / reserve(...);  uploaded();
