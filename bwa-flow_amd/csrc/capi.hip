@@ -181,6 +181,7 @@ int create_common(int device, const bwagpu_opt_t* opt, const bwagpu_bns_t* bns, 
   ctx->ext_short = ext_short_default();
   ctx->ext_short_fill = ext_short_fill_default();
   ctx->light_pack = light_pack_default();
+  ctx->ungapped = ungapped_default();
   *made = ctx;
   HIPC(hipSetDevice(device), "hipSetDevice");
   HIPC(hipMalloc(&ctx->d_ann_off, sizeof(int64_t) * bns->n_seqs), "hipMalloc(ann_offset)");
@@ -373,6 +374,9 @@ int enqueue_spec(bwagpu_ctx_t* ctx, Slot& s, const DevBatch& db, int lq_max, bwa
   HIPC(s.d_stasks.get(a.stasks, n_tasks), "hipMalloc(stasks)");
   HIPC(s.d_ftask.get(a.ftask, n_tasks), "hipMalloc(ftask)");
   HIPC(s.d_ftaskR.get(a.ftaskR, n_tasks), "hipMalloc(ftaskR)");
+  // the certificate only moves work out of the DP, as the row bound does: it acts under that switch
+  a.ung = nullptr;
+  if (ctx->ungapped && ctx->opt.row_bound) HIPC(s.d_ung.get(a.ung, n_tasks), "hipMalloc(ung)");
   // pair matrices of heavy reads: sum over them of 2 * ns * ceil(ns / 64) words,
   // <= 2 * ns_total * (1 + ns_max / 64); reads that do not fit take the per-seed kernel
   HIPC(s.d_mat.get(a.mat, (size_t)std::max<int64_t>(1 << 20, 16 * (int64_t)ns)), "hipMalloc(mat)");
@@ -946,6 +950,35 @@ int bwagpu_debug_spec_short(bwagpu_ctx_t* ctx, void* stream, int64_t* out) {
     out[2 + 4 * r] = c[SPC_LLONG + l];
     out[3 + 4 * r] = c[SPC_RCNT + l];
     out[4 + 4 * r] = c[SPC_RLONG + l];
+  }
+  return BWAGPU_OK;
+}
+
+int bwagpu_ctx_ungapped(bwagpu_ctx_t* ctx, int on) {
+  if (!ctx) return BWAGPU_E_INVAL;
+  const int prev = ctx->ungapped;
+  if (on >= 0) ctx->ungapped = on ? 1 : 0;
+  return prev;
+}
+
+int bwagpu_debug_spec_ungapped(bwagpu_ctx_t* ctx, void* stream, int64_t* out) {
+  if (!ctx || !out) return BWAGPU_E_INVAL;
+  hipStream_t st = nullptr;
+  if (int rc = entry_stream(ctx, stream, &st)) return rc;
+  int k = 0;
+  while (k < BWAGPU_NUM_SLOTS && ctx->dev_stream[k] != st) ++k;
+  if (k == BWAGPU_NUM_SLOTS || !ctx->dev_scratch[k].d_ctr.p) return fail(ctx, BWAGPU_E_INVAL, "no device-entry batch on this stream");
+  HIPC(hipStreamSynchronize(st), "hipStreamSynchronize");
+  int32_t c[SPC_WORDS];
+  HIPC(hipMemcpy(c, ctx->dev_scratch[k].d_ctr.p, sizeof c, hipMemcpyDeviceToHost), "hipMemcpy(ctr)");
+  for (int r = 0; r < kSpecRounds; ++r) {
+    out[4 * r + 0] = c[SPC_UNG_N + r];
+    out[4 * r + 1] = c[SPC_UNG_Q + r];
+    out[4 * r + 2] = out[4 * r + 3] = 0;
+    for (int bin = 0; bin < kSpecBins; ++bin) {  // the sides left on the lists (0 for a bin that is not phased)
+      out[4 * r + 2] += c[SPC_LCNT + r * kSpecBins + bin];
+      out[4 * r + 3] += c[SPC_RCNT + r * kSpecBins + bin];
+    }
   }
   return BWAGPU_OK;
 }

@@ -8,6 +8,7 @@
 #include "bwagpu_debug.h"
 #include "pure.h"
 #include "spec_plan.h"
+#include "ungapped.h"
 
 namespace bwagpu {
 
@@ -139,6 +140,8 @@ enum {
   SPC_LLONG = 84,     // [list] phased extension, short phase on: left sides with a query longer than short_q
   SPC_RLONG = 93,     // [list] ... right sides (the first position of the list's short run)
   SPC_SHORT_N = 102,  // sides run in the short phase, sixteen per wave (diagnostic)
+  SPC_UNG_N = 103,    // [round] sides the ungapped certificate settled at sort time (diagnostic)
+  SPC_UNG_Q = 106,    // [round] ... and the sum of their query lengths (the DP rows they would have run)
   SPC_WORDS = 128
 };
 // sharded queue heads of the extension task lists (SpecArgs::qh, zeroed per
@@ -175,6 +178,17 @@ struct FatTask {
 };
 static_assert(sizeof(FatTask) == 32, "FatTask layout");
 static_assert(BWAGPU_MAX_READ_LEN < 1024, "FatTask packs qbeg / len / lq in 10 bits each");
+// The ungapped certificate's stored decision for one task of a phased list
+// (spec_ungapped_kernel writes it ahead of the sort; spec_sort2_count and
+// spec_sort2_scatter read the same record): which sides need no DP, and what
+// each of those leaves (ungapped.h)
+struct UngRec {
+  struct Side {
+    int32_t ok;  // the side exists and holds the certificate
+    UngappedSide s;
+  } side[2];  // left, right
+};
+static_assert(sizeof(UngRec) == 32, "UngRec layout");
 struct SpecArgs {
   int lq_bound;               // reads longer than this set ERR_LEN and are skipped
   ChainWin* win;              // per chain
@@ -204,6 +218,7 @@ struct SpecArgs {
   FatTask* ftask;             // the same lists as FatTask records (the packed kernels); the phased
                               // extension: the tasks with a left side, by that side's length
   FatTask* ftaskR;            // the phased extension: the tasks with a right side, by its length
+  UngRec* ung;                // per task of a phased list (same offsets as tasks); null: the certificate is off
   int risky_first;            // spec_select_light<SEL_FINAL>: reads with a round-B task first (BWAGPU_LIGHT_RISKY_FIRST)
   int emu_strict;             // spec_select_light<SEL_EMULATE>: round-B tasks for uncertain skips too (BWAGPU_EMU_STRICT)
   int light_pack;             // spec_select_light: narrow reads eight per wave (bwagpu_ctx_light_pack)
@@ -233,6 +248,8 @@ struct SpecStreams {
   // sixteen-per-wave slots (bwagpu_ctx_ext_short_fill)
   int short_fill = 0;
 };
+// the ungapped certificate new contexts start with (BWAGPU_UNGAPPED, else on)
+int ungapped_default();
 // the form new contexts start with (bwagpu_debug_ext_form; process-wide default)
 int set_ext_form(int form);
 // the short-side threshold new contexts start with (BWAGPU_EXT_SHORT_Q, else

@@ -2348,6 +2348,15 @@ int ext_short_default() {
 #ifndef BWAGPU_EXT_SHORT_FILL_DEFAULT
 #define BWAGPU_EXT_SHORT_FILL_DEFAULT 150
 #endif
+// The ungapped certificate (bwagpu_ctx_ungapped).
+// BWAGPU_UNGAPPED=0 starts contexts with it off.
+int ungapped_default() {
+  static const int on = [] {
+    const char* e = getenv("BWAGPU_UNGAPPED");
+    return !(e && e[0] == '0');
+  }();
+  return on;
+}
 int ext_short_fill_default() {
   static const int f = [] {
     const char* e = getenv("BWAGPU_EXT_SHORT_FILL");
@@ -2358,8 +2367,8 @@ int ext_short_fill_default() {
 
 
 // a bin's list sorted as its kernel takes it, and its launch
-static void launch_sort(const ExtBin& k, const ExtRound& r, int bin0, int nbins, int short_q) {
-  if (k.phased) launch_side_sort(r, bin0, nbins, short_q);
+static void launch_sort(const ExtBin& k, const ExtRound& r, int bin0, int nbins, int short_q, int short_fill) {
+  if (k.phased) launch_side_sort(r, bin0, nbins, short_q, short_fill);
   else launch_task_sort(r, bin0, nbins);
 }
 static void launch_ext_bin(const ExtBin& k, const ExtRound& r, int list, const ExtPlan& p, int short_fill) {
@@ -2380,10 +2389,10 @@ static void launch_ext_round(const DevOpt& o, const DevRef& ref, const DevBatch&
   const ExtPlan plan = ext_plan(o, ss.form, tb_bytes, ss.short_q);
   const ExtRound r{o, ref, b, a, round, tb_bytes, st};
   if (!bin1 || plan.bin[0].phased == plan.bin[1].phased) {
-    launch_sort(plan.bin[0], r, 0, bin1 ? 2 : 1, plan.short_q);
+    launch_sort(plan.bin[0], r, 0, bin1 ? 2 : 1, plan.short_q, ss.short_fill);
   } else {
-    launch_sort(plan.bin[0], r, 0, 1, plan.short_q);
-    launch_sort(plan.bin[1], r, 1, 1, 0);
+    launch_sort(plan.bin[0], r, 0, 1, plan.short_q, ss.short_fill);
+    launch_sort(plan.bin[1], r, 1, 1, 0, ss.short_fill);
   }
   const bool prof = ss.pool && *ss.pool_used + 2 <= ss.pool_n;
   if (prof) (void)hipEventRecord(ss.pool[*ss.pool_used], st);

@@ -216,7 +216,7 @@ int ext2_grid(int nb, bool packed);
 // the phased pair SIDE4 (spec_side.hip): a bin's lists, one per side in its
 // query length order (spec_sort2_*), and its two launches as ext_plan
 // (spec_plan.h) names the kernel `k`
-void launch_side_sort(const ExtRound& r, int bin0, int nbins, int short_q);
+void launch_side_sort(const ExtRound& r, int bin0, int nbins, int short_q, int short_fill);
 void launch_side_bin(const ExtBin& k, const ExtRound& r, int list, const ExtPlan& p, int short_fill);
 constexpr int ext_key(int family, int g, int pmax, bool k8) { return ((family * 64 + g) * 32 + pmax) * 2 + (k8 ? 1 : 0); }
 

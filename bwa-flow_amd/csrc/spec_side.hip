@@ -18,6 +18,179 @@ namespace bwagpu {
 // whole-read seed (neither side) is written by the scatter itself.
 __device__ __forceinline__ int side_key(int qlen) { return 255 - min(qlen, 255); }  // descending
 
+
+// ------------------------------------------- the ungapped certificate (§24)
+// A side whose diagonal loses less than the cheapest gap open needs no DP
+// (ungapped.h).  spec_ungapped_kernel decides that once per side, ahead of the
+// sort, and stores the decision with what the side leaves; the count and the
+// scatter read the stored record, so both see the same lists.  One thread per
+// (task, side).  The query bytes come from the read (a left side runs down
+// from the seed), the target bases from the pac at the 2-strand coordinates
+// that fill_side_run reads, sixteen of each per pass from two loads; P never
+// falls, so a pass is abandoned at its end.
+// keep_short > 0 (the first bin's lists with bwagpu_ctx_ext_short_fill at 0:
+// every side up to the short threshold takes the short phase) leaves those
+// sides to the lists.
+struct UngSide {
+  const uint8_t* rd;  // the read; the side's query base j is rd[p0 + d j]
+  int64_t x0;         // ... against the 2-strand coordinate x0 + d j
+  int p0, d, qlen, lq;
+};
+// one pass: the side's bases [base, last].  Sixteen bases are sixteen bytes of
+// the read and at most five of the pac: one unaligned load of each (fast), from
+// a window pushed back inside the read / the pac where the sixteen would leave
+// it.  A read under 16 bases, a pac under 8 bytes or a pass over both strands
+// (a chain window never is) takes the bases one by one.
+struct UngPass {
+  uint64_t qw[2], tw;
+  int64_t fa, b0;
+  int base, last, ws;
+  bool fast, rev;
+};
+__device__ __forceinline__ UngPass ung_load(const UngSide& s, const DevRef& ref, int base) {
+  UngPass p;
+  p.base = base;
+  p.last = min(base + 15, s.qlen - 1);  // rows j < qlen <= tlen lie in the chain's window
+  p.fast = false;
+  if (base >= s.qlen) return p;
+  const int64_t two1 = (ref.l_pac << 1) - 1, pac_bytes = (ref.l_pac >> 2) + 1;  // bwa.c:281-282
+  const int64_t xa = s.x0 + (int64_t)s.d * base, xb = s.x0 + (int64_t)s.d * p.last;
+  p.rev = xa >= ref.l_pac;
+  p.fa = p.rev ? two1 - xa : xa;
+  const int64_t fb = p.rev ? two1 - xb : xb;
+  p.fast = s.lq >= 16 && pac_bytes >= 8 && (xb >= ref.l_pac) == p.rev;
+  if (p.fast) {
+    p.ws = min(max(min(s.p0 + s.d * base, s.p0 + s.d * (base + 15)), 0), s.lq - 16);
+    p.b0 = min(min(p.fa, fb) >> 2, pac_bytes - 8);
+    __builtin_memcpy(p.qw, s.rd + p.ws, 16);
+    __builtin_memcpy(&p.tw, ref.pac + p.b0, 8);
+  }
+  return p;
+}
+__device__ __forceinline__ void ung_eat(const UngSide& s, const DevRef& ref, const UngPass& p, const int8_t* mat,
+                                        int max_mat, UngappedScan& sc) {
+  if (p.base >= s.qlen) return;
+  if (p.fast) {
+#pragma unroll
+    for (int m = 0; m < 16; ++m)
+      if (p.base + m <= p.last) {
+        const int k = s.p0 + s.d * (p.base + m) - p.ws;  // 0 .. 15
+        const int qv = (int)(p.qw[k >> 3] >> ((k & 7) * 8)) & 255;
+        const int64_t fm = p.fa + (p.rev ? -s.d : s.d) * m;
+        const int byte = (int)(p.tw >> (((fm >> 2) - p.b0) * 8)) & 255;
+        const int bse = (byte >> ((~fm & 3) << 1)) & 3;
+        sc.step(p.base + m, mat[(p.rev ? 3 - bse : bse) * 5 + min(qv, 4)], max_mat);
+      }
+  } else {
+    for (int j = p.base; j <= p.last; ++j)
+      sc.step(j, mat[pac_base2(ref.pac, ref.l_pac, s.x0 + (int64_t)s.d * j) * 5 + min((int)s.rd[s.p0 + s.d * j], 4)],
+              max_mat);
+  }
+}
+
+__global__ void __launch_bounds__(256) spec_ungapped_kernel(DevOpt o, DevRef ref, DevBatch b, SpecArgs a, int round,
+                                                            int bin0, int keep_short) {
+  sel_prio();
+  __shared__ int8_t mat[25];  // the scores by (target, query) base: a lookup per base, kept out of global memory
+  if (threadIdx.x < 25) mat[threadIdx.x] = o.mat[threadIdx.x];
+  __syncthreads();
+  const int bin = bin0 + (int)blockIdx.y;
+  const int list = round * kSpecBins + bin;
+  const int n = __hip_atomic_load(&a.ctr[SPC_CNT + list], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const size_t off = spec_list_off(list, b.n_chains, b.n_seeds);
+  const int2* tl = a.tasks + off;
+  const int oe_min = ungapped_oe_min(o.o_del, o.e_del, o.o_ins, o.e_ins);
+  const int keep = bin == 0 ? keep_short : 0;
+  const int chunk = (n + (int)gridDim.x - 1) / (int)gridDim.x;
+  const int i0 = (int)blockIdx.x * chunk, i1 = min(n, i0 + chunk);
+  for (int k = 2 * i0 + (int)threadIdx.x; k < 2 * i1; k += 256) {
+    const int i = k >> 1, right = k & 1;
+    const FatTask f = fat_task(b, a, tl[i]);
+    const int qb = (int)(f.qls & 1023u), ln = (int)((f.qls >> 10) & 1023u), lq = (int)(f.qls >> 20);
+    const int64_t xr = f.rbeg + ln;
+    const int qlen = right ? lq - qb - ln : qb;
+    const int tlen = right ? (int)(f.rbeg + f.dhi - xr) : f.dlo;
+    UngRec::Side rec{0, {0, 0, 0}};
+    // a right side starts from the left score, which is at least the seed's (ln * a)
+    if (qlen > keep && ungapped_band_ok(o.w) &&
+        ungapped_call_ok(qlen, tlen, ln * o.a, o.w, o.zdrop, o.max_mat, oe_min)) {
+      UngSide sd;
+      sd.rd = b.seq + f.qoff;
+      sd.p0 = right ? qb + ln : qb - 1;
+      sd.d = right ? 1 : -1;
+      sd.x0 = right ? xr : f.rbeg - 1;
+      sd.qlen = qlen;
+      sd.lq = lq;
+      UngappedScan sc;
+      for (int base = 0; base < qlen && !sc.dead(oe_min); base += 16)
+        ung_eat(sd, ref, ung_load(sd, ref, base), mat, o.max_mat, sc);
+      if (!sc.dead(oe_min)) rec = UngRec::Side{1, sc.side()};
+    }
+    a.ung[off + i].side[right] = rec;
+  }
+}
+
+// the stored decision of the task at `slot` of its list: which of its sides
+// (query lengths qb, qr) are settled here (cl, cr) and which enter a list.  A
+// certified right side behind a left side that needs the DP stays on the
+// right list: its h0 is the left call's score.
+struct SideLists {
+  bool cl, cr, in_l, in_r;
+};
+__device__ __forceinline__ SideLists side_lists(const SpecArgs& a, size_t slot, int qb, int qr) {
+  SideLists s{false, false, qb > 0, qr > 0};
+  if (a.ung) {
+    s.cl = qb > 0 && a.ung[slot].side[0].ok;
+    s.in_l = qb > 0 && !s.cl;
+    s.cr = qr > 0 && a.ung[slot].side[1].ok && !s.in_l;
+    s.in_r = qr > 0 && !s.cr;
+  }
+  return s;
+}
+
+// The SeedExt of a task whose left side is absent or certified, as the side
+// launches would leave it (side_start / side_advance with x = ungapped_result,
+// one call per side, no rows, no cells, no band retry: max_off = 0).  right:
+// the right side is certified too.  Final if the task has no right side or
+// `right`; else the partial slot the right launch goes on from.
+__device__ __forceinline__ SeedExt settle_sides(const DevOpt& o, const FatTask& f, const UngRec& u, bool right) {
+  const int qb = (int)(f.qls & 1023u), ln = (int)((f.qls >> 10) & 1023u), lq = (int)(f.qls >> 20);
+  const int qr = lq - qb - ln;
+  SeedExt e;
+  int calls = 0;
+  e.rb = f.rbeg;
+  e.qb = 0;
+  e.score = e.truesc = ln * o.a;  // bwamem.c:753
+  if (qb > 0) {
+    const UngappedOut x = ungapped_result(ln * o.a, qb, u.side[0].s);
+    const bool local = x.gscore <= 0 || x.gscore <= x.score - o.pen_clip5;
+    e.rb = f.rbeg - (local ? x.tle : x.gtle);
+    e.qb = local ? qb - x.qle : 0;
+    e.score = x.score;
+    e.truesc = local ? x.score : x.gscore;
+    ++calls;
+  }
+  e.re = f.rbeg + ln;
+  e.qe = lq;
+  if (right) {
+    const int h0 = e.score;  // sc0 (bwamem.c:761)
+    const UngappedOut x = ungapped_result(h0, qr, u.side[1].s);
+    const bool local = x.gscore <= 0 || x.gscore <= x.score - o.pen_clip3;
+    e.qe = local ? qb + ln + x.qle : lq;
+    e.re = f.rbeg + ln + (local ? x.tle : x.gtle);
+    e.score = x.score;
+    e.truesc += (local ? x.score : x.gscore) - h0;
+    ++calls;
+  } else if (qr > 0) {
+    e.re = 0;
+    e.qe = 0;
+  }
+  e.w = o.w;
+  e.cells = e.rows = 0;
+  e.calls = calls + (right || qr == 0 ? 1 : 0);  // + 1 on a final slot: a computed slot is never all-zero
+  return e;
+}
+
 __global__ void __launch_bounds__(256) spec_sort2_count(DevBatch b, SpecArgs a, int round, int bin0) {
   sel_prio();
   __shared__ int hist[2][256];
@@ -30,15 +203,17 @@ __global__ void __launch_bounds__(256) spec_sort2_count(DevBatch b, SpecArgs a, 
   if (threadIdx.x < 2) tot[threadIdx.x] = 0;
   __syncthreads();
   const int n = __hip_atomic_load(&a.ctr[SPC_CNT + list], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const int2* tl = a.tasks + spec_list_off(list, b.n_chains, b.n_seeds);
+  const size_t off = spec_list_off(list, b.n_chains, b.n_seeds);
+  const int2* tl = a.tasks + off;
   const int chunk = (n + (int)gridDim.x - 1) / (int)gridDim.x;
   const int i0 = (int)blockIdx.x * chunk, i1 = min(n, i0 + chunk);
   for (int i = i0 + (int)threadIdx.x; i < i1; i += 256) {
     const FatTask f = fat_task(b, a, tl[i]);
     const int qb = (int)(f.qls & 1023u), ln = (int)((f.qls >> 10) & 1023u), lq = (int)(f.qls >> 20);
     const int qr = lq - qb - ln;
-    if (qb > 0) atomicAdd(&hist[0][side_key(qb)], 1);
-    if (qr > 0) atomicAdd(&hist[1][side_key(qr)], 1);
+    const SideLists sl = side_lists(a, off + i, qb, qr);
+    if (sl.in_l) atomicAdd(&hist[0][side_key(qb)], 1);
+    if (sl.in_r) atomicAdd(&hist[1][side_key(qr)], 1);
   }
   __syncthreads();
   for (int k = threadIdx.x; k < 2 * 256; k += 256) {
@@ -82,11 +257,13 @@ __global__ void __launch_bounds__(256) spec_sort2_scan(SpecArgs a, int round, in
 __global__ void __launch_bounds__(256) spec_sort2_scatter(DevOpt o, DevBatch b, SpecArgs a, int round, int bin0) {
   sel_prio();
   __shared__ int cnt[2][256];
+  __shared__ int ung[2];  // sides settled here, their query lengths
   const int bin = bin0 + (int)blockIdx.y;
   const int list = round * kSpecBins + bin;
   int32_t* ghL = a.sorth + (round * 2 + bin) * kSortKeys;
   int32_t* ghR = ghL + kSortWordsR;
   for (int k = threadIdx.x; k < 2 * 256; k += 256) cnt[k >> 8][k & 255] = 0;
+  if (threadIdx.x < 2) ung[threadIdx.x] = 0;
   __syncthreads();
   const int n = __hip_atomic_load(&a.ctr[SPC_CNT + list], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const size_t off = spec_list_off(list, b.n_chains, b.n_seeds);
@@ -107,25 +284,24 @@ __global__ void __launch_bounds__(256) spec_sort2_scatter(DevOpt o, DevBatch b, 
         ft[m] = fat_task(b, a, tl[i]);
         const int qb = (int)(ft[m].qls & 1023u), ln = (int)((ft[m].qls >> 10) & 1023u), lq = (int)(ft[m].qls >> 20);
         const int qr = lq - qb - ln;
-        if (qb > 0) {
+        const SideLists sl = side_lists(a, off + i, qb, qr);
+        if (sl.in_l) {
           kl[m] = side_key(qb);
           rl[m] = atomicAdd(&cnt[0][kl[m]], 1);
         }
-        if (qr > 0) {
+        if (sl.in_r) {
           kr[m] = side_key(qr);
           rr[m] = atomicAdd(&cnt[1][kr[m]], 1);
         }
-        if (qb == 0 && qr == 0) {  // a whole-read seed (bwamem.c:753, 781): no ksw_extend2 call
-          SeedExt e;
-          e.rb = ft[m].rbeg;
-          e.re = ft[m].rbeg + ln;
-          e.qb = 0;
-          e.qe = lq;
-          e.score = e.truesc = ln * o.a;
-          e.w = o.w;
-          e.cells = e.rows = 0;
-          e.calls = 1;
-          a.ext[ft[m].pos] = e;
+        if (!sl.in_l) {
+          // no left call to run: a whole-read seed (bwamem.c:753, 781: no ksw_extend2 call), or sides the
+          // certificate settles; with a right side on its list, the slot that launch goes on from
+          if (qb > 0 || !sl.in_r)
+            a.ext[ft[m].pos] = settle_sides(o, ft[m], sl.cl || sl.cr ? a.ung[off + i] : UngRec{}, sl.cr);
+          if (sl.cl || sl.cr) {
+            atomicAdd(&ung[0], (sl.cl ? 1 : 0) + (sl.cr ? 1 : 0));
+            atomicAdd(&ung[1], (sl.cl ? qb : 0) + (sl.cr ? qr : 0));
+          }
         }
       }
     }
@@ -144,6 +320,8 @@ __global__ void __launch_bounds__(256) spec_sort2_scatter(DevOpt o, DevBatch b, 
     for (int k = threadIdx.x; k < 2 * 256; k += 256) cnt[k >> 8][k & 255] = 0;
     __syncthreads();
   }
+  if (threadIdx.x < 2 && ung[threadIdx.x])
+    atomicAdd(&a.ctr[(threadIdx.x ? SPC_UNG_Q : SPC_UNG_N) + round], ung[threadIdx.x]);
 }
 
 // One side of a task in flight (LDS, per sub-slot, between its calls).
@@ -509,7 +687,10 @@ __global__ void __launch_bounds__(kBlock) spec_side4_kernel(DevOpt o, DevRef ref
 }
 
 
-void launch_side_sort(const ExtRound& r, int bin0, int nbins, int short_q) {
+void launch_side_sort(const ExtRound& r, int bin0, int nbins, int short_q, int short_fill) {
+  if (r.a.ung)
+    hipLaunchKernelGGL(spec_ungapped_kernel, dim3(1024, nbins), dim3(256), 0, r.st, r.o, r.ref, r.b, r.a, r.round, bin0,
+                       short_fill == 0 ? short_q : 0);
   hipLaunchKernelGGL(spec_sort2_count, dim3(256, nbins), dim3(256), 0, r.st, r.b, r.a, r.round, bin0);
   hipLaunchKernelGGL(spec_sort2_scan, dim3(2 * nbins), dim3(256), 0, r.st, r.a, r.round, bin0, nbins, short_q);
   hipLaunchKernelGGL(spec_sort2_scatter, dim3(256, nbins), dim3(256), 0, r.st, r.o, r.b, r.a, r.round, bin0);

@@ -370,6 +370,11 @@ class Engine:
         -1 = query; -> the previous setting"""
         return self.lib.bwagpu_ctx_light_pack(self.ctx, int(on))
 
+    def ungapped(self, on: int = -1) -> int:
+        """this context's ungapped certificate (bwagpu_ctx_ungapped, default
+        on; acts only while the row bound is on); -> the previous setting"""
+        return self.lib.bwagpu_ctx_ungapped(self.ctx, int(on))
+
     def row_bound(self, on: int = -1) -> int:
         """this context's row bound in the packed extension kernels
         (bwagpu_ctx_row_bound, default on); -> the previous setting"""

@@ -122,6 +122,22 @@ int bwagpu_ctx_light_pack(bwagpu_ctx_t *ctx, int on);
    A's first-bin side lists: left sides, of them longer than the threshold (0
    with the short phase off), right sides, of them longer; out[5..8] = round B's */
 int bwagpu_debug_spec_short(bwagpu_ctx_t *ctx, void *stream, int64_t *out);
+/* the ungapped certificate (default on; BWAGPU_UNGAPPED=0 starts contexts
+   with it off): a side of a phased extension task whose diagonal loses less
+   than the cheapest gap open is settled when the side lists are sorted, from
+   the diagonal's running sums alone, and never enters a list.
+   Regions are identical either way and the ksw_extend2 calls are counted as
+   before; a settled call counts no rows and no cells.  It acts only while the
+   row bound (below) is on, the switch under which calls may end early.  With
+   bwagpu_ctx_ext_short_fill at 0 (every short side takes the short phase) the
+   sides up to the short threshold are left to that phase.  on < 0 only
+   queries; returns the previous setting. */
+int bwagpu_ctx_ungapped(bwagpu_ctx_t *ctx, int on);
+/* diagnostics of the last device-entry batch on `stream` (waits for it), out:
+   12 entries, four per round A, B, C: the sides the certificate settled, the
+   sum of their query lengths, and the left and the right sides that stayed on
+   the phased lists */
+int bwagpu_debug_spec_ungapped(bwagpu_ctx_t *ctx, void *stream, int64_t *out);
 /* the packed extension kernels' row bound (default on): a ksw_extend2 call
    ends once no later target row can change its score, qle, tle, gtle, gscore
    or max_off (every later cell is bounded by a stored value plus max(mat) per
