@@ -182,6 +182,7 @@ int create_common(int device, const bwagpu_opt_t* opt, const bwagpu_bns_t* bns, 
   ctx->ext_short_fill = ext_short_fill_default();
   ctx->light_pack = light_pack_default();
   ctx->ungapped = ungapped_default();
+  ctx->emu_finish = emu_finish_default();
   *made = ctx;
   HIPC(hipSetDevice(device), "hipSetDevice");
   HIPC(hipMalloc(&ctx->d_ann_off, sizeof(int64_t) * bns->n_seqs), "hipMalloc(ann_offset)");
@@ -361,7 +362,9 @@ int enqueue_spec(bwagpu_ctx_t* ctx, Slot& s, const DevBatch& db, int lq_max, bwa
   HIPC(s.d_skipf.get(a.skipf, ns), "hipMalloc(skipf)");
   HIPC(s.d_heavy.get(a.heavy, nr), "hipMalloc(heavy)");
   HIPC(s.d_redo.get(a.redo, nr), "hipMalloc(redo)");
-  HIPC(s.d_rbits.get(a.rbits, nr / 32 + 1), "hipMalloc(rbits)");
+  HIPC(s.d_rbits.get(a.rbits, 2 * (nr / 32 + 1)), "hipMalloc(rbits)");
+  a.fbits = a.rbits + (nr / 32 + 1);  // the finished bits: a second plane
+  HIPC(s.d_rlist.get(a.rlist, nr), "hipMalloc(rlist)");
   HIPC(s.d_desc.get(a.rdesc, nr), "hipMalloc(desc)");
   HIPC(s.d_schain.get(a.seedchain, ns), "hipMalloc(seedchain)");
   HIPC(s.d_hinfo.get(a.hinfo, nr), "hipMalloc(hinfo)");
@@ -397,6 +400,7 @@ int enqueue_spec(bwagpu_ctx_t* ctx, Slot& s, const DevBatch& db, int lq_max, bwa
   }();
   a.emu_strict = emu_strict;
   a.light_pack = ctx->light_pack;
+  a.emu_finish = ctx->emu_finish;
   a.out = d_out;
   a.out_n = d_n;
   a.stats = d_stats;
@@ -980,6 +984,30 @@ int bwagpu_debug_spec_ungapped(bwagpu_ctx_t* ctx, void* stream, int64_t* out) {
       out[4 * r + 3] += c[SPC_RCNT + r * kSpecBins + bin];
     }
   }
+  return BWAGPU_OK;
+}
+
+int bwagpu_ctx_emu_finish(bwagpu_ctx_t* ctx, int on) {
+  if (!ctx) return BWAGPU_E_INVAL;
+  const int prev = ctx->emu_finish;
+  if (on >= 0) ctx->emu_finish = on ? 1 : 0;
+  return prev;
+}
+
+int bwagpu_debug_spec_finish(bwagpu_ctx_t* ctx, void* stream, int64_t* out) {
+  if (!ctx || !out) return BWAGPU_E_INVAL;
+  hipStream_t st = nullptr;
+  if (int rc = entry_stream(ctx, stream, &st)) return rc;
+  int k = 0;
+  while (k < BWAGPU_NUM_SLOTS && ctx->dev_stream[k] != st) ++k;
+  if (k == BWAGPU_NUM_SLOTS || !ctx->dev_scratch[k].d_ctr.p) return fail(ctx, BWAGPU_E_INVAL, "no device-entry batch on this stream");
+  HIPC(hipStreamSynchronize(st), "hipStreamSynchronize");
+  int32_t c[SPC_WORDS];
+  HIPC(hipMemcpy(c, ctx->dev_scratch[k].d_ctr.p, sizeof c, hipMemcpyDeviceToHost), "hipMemcpy(ctr)");
+  out[0] = c[SPC_FIN_NAR];
+  out[1] = c[SPC_FIN_WIDE];
+  out[2] = c[SPC_LIST_N];
+  out[3] = c[SPC_LIGHT_N];
   return BWAGPU_OK;
 }
 

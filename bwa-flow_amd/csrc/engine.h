@@ -142,6 +142,10 @@ enum {
   SPC_SHORT_N = 102,  // sides run in the short phase, sixteen per wave (diagnostic)
   SPC_UNG_N = 103,    // [round] sides the ungapped certificate settled at sort time (diagnostic)
   SPC_UNG_Q = 106,    // [round] ... and the sum of their query lengths (the DP rows they would have run)
+  SPC_FIN_NAR = 109,  // narrow light reads the emulate pass finished (emu_finish)
+  SPC_FIN_WIDE = 110, // ... wider light reads
+  SPC_LIST_N = 111,   // light reads the emulate pass left to the final pass: entries of SpecArgs::rlist
+  SPC_LIGHT_N = 112,  // light reads of the batch, as the emulate pass counts them (diagnostic)
   SPC_WORDS = 128
 };
 // sharded queue heads of the extension task lists (SpecArgs::qh, zeroed per
@@ -202,6 +206,8 @@ struct SpecArgs {
   int32_t* heavy;             // reads with > kSelLight seeds
   int32_t* redo;              // reads the final pass left to the redo pass
   uint32_t* rbits;            // per read, a bit: the emulate pass left it a round-B task (zeroed per batch)
+  uint32_t* fbits;            // per read, a bit: the emulate pass finished it — wrote its regions (zeroed per batch)
+  int32_t* rlist;             // the light reads the emulate pass did not finish, ctr[SPC_LIST_N] of them, in any order
   ReadDesc* rdesc;            // per read (spec_reads_kernel)
   int32_t* seedchain;         // per seed slot: its chain
   int4* hinfo;                // per heavy-list entry: rd, matrix word offset (-1: none), first column, ns
@@ -222,6 +228,8 @@ struct SpecArgs {
   int risky_first;            // spec_select_light<SEL_FINAL>: reads with a round-B task first (BWAGPU_LIGHT_RISKY_FIRST)
   int emu_strict;             // spec_select_light<SEL_EMULATE>: round-B tasks for uncertain skips too (BWAGPU_EMU_STRICT)
   int light_pack;             // spec_select_light: narrow reads eight per wave (bwagpu_ctx_light_pack)
+  int emu_finish;             // spec_select_light<SEL_EMULATE>: write the reads it leaves no round-B task and list
+                              // the others; <SEL_FINAL>: take only those (bwagpu_ctx_emu_finish)
   int ext_prefetch;           // spec_ext4_kernel: claim next tasks a generation ahead while more than
                               // ext_prefetch x 8 x (waves per XCD) remain (0: on demand)
   bwagpu_alnreg_t* out;
@@ -250,6 +258,8 @@ struct SpecStreams {
 };
 // the ungapped certificate new contexts start with (BWAGPU_UNGAPPED, else on)
 int ungapped_default();
+// the emulate pass's finishing of decided light reads new contexts start with (BWAGPU_EMU_FINISH, else on)
+int emu_finish_default();
 // the form new contexts start with (bwagpu_debug_ext_form; process-wide default)
 int set_ext_form(int form);
 // the short-side threshold new contexts start with (BWAGPU_EXT_SHORT_Q, else

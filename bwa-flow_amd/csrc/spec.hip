@@ -1292,11 +1292,12 @@ __global__ void __launch_bounds__(64) spec_select_kernel(DevOpt o, DevRef ref, D
 // seeds extended so far (their regions) and the seeds skipped so far — so:
 //   1. pairs: for every seed k, the 64-bit masks of earlier seeds j whose
 //      region would hold it (bwamem.c:678-697: C) and of earlier seeds of its
-//      chain that overlap it (698-707, before the skip filter: O), and its
-//      seedcov if extended (784-788) — lane-parallel, no loop-carried state;
+//      chain that overlap it (698-707, before the skip filter: O) —
+//      lane-parallel, no loop-carried state;
 //   2. scan: the sequential logic on scalar masks only:
 //        hit = C[k] & extended;  skipped = hit && !(O[k] & ~skipped);
-//   3. output: every extended seed's record lane-parallel at its rank.
+//   3. output: every extended seed's seedcov (784-788) and its record,
+//      lane-parallel at its rank.
 // A seed that must be extended but has no result: SEL_EMULATE marks it a
 // round-B task (pending: neither extended nor skipped, as in the per-seed
 // form); SEL_FINAL sends the read to the redo pass.
@@ -1316,14 +1317,18 @@ __global__ void __launch_bounds__(64) spec_select_kernel(DevOpt o, DevRef ref, D
 #define BWAGPU_LIGHT_INLINE 1
 #endif
 // One light read (1 <= ns <= kSelLight) by the whole wave; d is wave-uniform.
+// -> (emulate, SpecArgs::emu_finish) the read is finished: it has no round-B
+// task, so its regions are written here and the final pass leaves it out
+// (DESIGN.md §25); a read that is not finished is appended to rlist.
 template <int MODE>
-__device__ __forceinline__ void light_read(const DevOpt& o, const DevRef& ref, const DevBatch& b, const SpecArgs& a,
+__device__ __forceinline__ bool light_read(const DevOpt& o, const DevRef& ref, const DevBatch& b, const SpecArgs& a,
                                            const int32_t* MG, uint8_t* tbl, uint8_t* tbr, int rd, const ReadDesc& d,
                                            Tally& tl) {
   constexpr bool WRITE = MODE != SEL_EMULATE;
   const int r = (int)(threadIdx.x & 63);
   const uint64_t lt_mask = r ? (~0ull >> (64 - r)) : 0ull;  // lanes below r
   const uint64_t t_start = g_trace ? __builtin_amdgcn_s_memrealtime() : 0;
+  bool finished = false;
     // a miss of the final pass is computed inline and the read starts over
     // with it (a region changes only later decisions; light reads are cheap)
     for (;;) {
@@ -1407,20 +1412,6 @@ __device__ __forceinline__ void light_read(const DevOpt& o, const DevRef& ref, c
       c_hi = r == it ? (uint32_t)(cm >> 32) : c_hi;
       o_lo = r == it ? (uint32_t)om : o_lo;
       o_hi = r == it ? (uint32_t)(om >> 32) : o_hi;
-      if (WRITE) {  // seedcov of k's region over its chain's seeds (bwamem.c:784-788)
-        const int64_t krb = (int64_t)((uint64_t)(uint32_t)__builtin_amdgcn_ds_bpermute(kl, (int)(x.rb >> 32)) << 32 |
-                                      (uint32_t)__builtin_amdgcn_ds_bpermute(kl, (int)x.rb));
-        const int64_t kre = (int64_t)((uint64_t)(uint32_t)__builtin_amdgcn_ds_bpermute(kl, (int)(x.re >> 32)) << 32 |
-                                      (uint32_t)__builtin_amdgcn_ds_bpermute(kl, (int)x.re));
-        const int kqb = __builtin_amdgcn_ds_bpermute(kl, x.qb), kqe = __builtin_amdgcn_ds_bpermute(kl, x.qe);
-        int v = valid && j_cid == k_cid && j_qbeg >= kqb && j_qbeg + j_len <= kqe && j_rbeg >= krb &&
-                        j_rbeg + j_len <= kre ? j_len : 0;
-        for (int m = 1; m < S; m <<= 1) v += __shfl_xor(v, m, 64);
-        // lane k takes the sum of its group (lane (k - first k of the pass) * S)
-        const int src = (r - (it << (6 - lgS))) << lgS;
-        const int got = __builtin_amdgcn_ds_bpermute(min(max(src, 0), 63) << 2, v);
-        cov = (r >= (it << (6 - lgS)) && r < ((it + 1) << (6 - lgS))) ? got : cov;
-      }
     }
     // ---- 2. the sequential decisions, on scalar masks
     // (emulate) unc: the seeds whose decisions the final pass may take
@@ -1461,6 +1452,35 @@ __device__ __forceinline__ void light_read(const DevOpt& o, const DevRef& ref, c
       ext |= bit;
       if (MODE == SEL_EMULATE && pend) unc |= bit;  // a pending seed's region may hold it
     }
+    // no round-B task: no a.ext[] of the read changes before the final pass,
+    // which would load, decide and write what this pass does
+    finished = MODE == SEL_EMULATE && a.emu_finish && !(pend | spend);
+    // seedcov of an extended seed k's region over its chain's seeds
+    // (bwamem.c:784-788), lane-parallel like the pair masks: the passes that
+    // hold an extended seed, of a read this pass writes
+    if (WRITE ? miss < 0 : finished) {
+      const int kn = 1 << (6 - lgS);  // seeds per pass
+      for (int it = 0; it < npass; ++it) {
+        const uint64_t km = (kn == 64 ? ~0ull : (1ull << kn) - 1) << (it * kn);
+        if (!(ext & km)) continue;
+        const int k = it * kn + (r >> lgS);
+        const int kl = min(k, d.ns - 1) << 2;
+        const int k_cid = __builtin_amdgcn_ds_bpermute(kl, cid);
+        const bool valid = k < d.ns && j < d.ns;
+        const int64_t krb = (int64_t)((uint64_t)(uint32_t)__builtin_amdgcn_ds_bpermute(kl, (int)(x.rb >> 32)) << 32 |
+                                      (uint32_t)__builtin_amdgcn_ds_bpermute(kl, (int)x.rb));
+        const int64_t kre = (int64_t)((uint64_t)(uint32_t)__builtin_amdgcn_ds_bpermute(kl, (int)(x.re >> 32)) << 32 |
+                                      (uint32_t)__builtin_amdgcn_ds_bpermute(kl, (int)x.re));
+        const int kqb = __builtin_amdgcn_ds_bpermute(kl, x.qb), kqe = __builtin_amdgcn_ds_bpermute(kl, x.qe);
+        int v = valid && j_cid == k_cid && j_qbeg >= kqb && j_qbeg + j_len <= kqe && j_rbeg >= krb &&
+                        j_rbeg + j_len <= kre ? j_len : 0;
+        for (int m = 1; m < S; m <<= 1) v += __shfl_xor(v, m, 64);
+        // lane k takes the sum of its group (lane (k - first k of the pass) * S)
+        const int src = (r - it * kn) << lgS;
+        const int got = __builtin_amdgcn_ds_bpermute(min(max(src, 0), 63) << 2, v);
+        cov = (r >= it * kn && r < (it + 1) * kn) ? got : cov;
+      }
+    }
     // ---- 3. outputs
     if constexpr (MODE == SEL_EMULATE) {
       const int list = kSpecBins + spec_bin(d.lq);
@@ -1468,6 +1488,10 @@ __device__ __forceinline__ void light_read(const DevOpt& o, const DevRef& ref, c
       const int p = wave_append(&a.ctr[SPC_CNT + list], pnd);
       if (p >= 0) a.tasks[spec_list_off(list, b.n_chains, b.n_seeds) + p] = make_int2(d.s0 + r, d.c0 + cid);
       if (pend && r == 0) atomicOr(&a.rbits[rd >> 5], 1u << (rd & 31));  // the final pass takes it first
+      if (a.emu_finish && r == 0) {
+        if (finished) atomicOr(&a.fbits[rd >> 5], 1u << (rd & 31));
+        else a.rlist[atomicAdd(&a.ctr[SPC_LIST_N], 1)] = rd;
+      }
     } else {
       if (BWAGPU_LIGHT_INLINE && miss >= 0 && d.lq <= kSpecBinLen[0]) {  // extend seed `miss` here, then the read again
         const bwagpu_seed_t sm = uni_seed(a.prog[d.s0 + miss]);
@@ -1493,6 +1517,8 @@ __device__ __forceinline__ void light_read(const DevOpt& o, const DevRef& ref, c
         if (r == miss) a.redo[atomicAdd(&a.ctr[SPC_REDO_N], 1)] = rd;
         break;  // the redo pass writes this read
       }
+    }
+    if (WRITE || finished) {
       const bool mine = (ext >> r) & 1;
       if (mine) {  // the region of seed r, at its rank (bwamem.c:718-792 field by field; rest zero)
         const int slot = (int)__popcll(ext & lt_mask);
@@ -1517,6 +1543,7 @@ __device__ __forceinline__ void light_read(const DevOpt& o, const DevRef& ref, c
     trace_read(MODE, b.n_reads, rd, t_start, d.ns, (int)__popcll(ext), 1);
     break;
     }  // the read's attempts
+  return finished;
 }
 
 // NARROW light reads (<= kPackW seeds and chains: nine in ten C2 reads), eight
@@ -1524,19 +1551,20 @@ __device__ __forceinline__ void light_read(const DevOpt& o, const DevRef& ref, c
 // prog[] order) and its chain i.  The three steps of light_read, with every
 // set an 8-bit one held alike by the group's lanes:
 //   1. pairs: pass k gives seed k to its group; the group's byte of the two
-//      ballots is C[k] / O[k], kept as byte k of a 64-bit word; seedcov of k
-//      is summed over the group into lane k;
+//      ballots is C[k] / O[k], kept as byte k of a 64-bit word;
 //   2. scan: light_read's statements in their order, as selects on the sets,
 //      eight steps for the eight reads at once;
-//   3. output: every extended seed's record at its rank within the group.
+//   3. output: seedcov of every extended seed k, summed over the group into
+//      lane k, and its record at its rank within the group.
 // d, rd and nar (this lane's read is a narrow one of this wave) are the same
 // in a group's lanes.  -> the lanes whose read the final pass missed a result
-// for; nothing of such a read is written here, light_read takes it.
+// for; nothing of such a read is written here, light_read takes it.  The
+// emulate pass (SpecArgs::emu_finish) -> the lanes whose read it finished: no
+// round-B task, its regions written here as the final pass would.
 constexpr int kPackW = 8;
 template <int MODE>
 __device__ __forceinline__ uint64_t light_packed(const DevBatch& b, const SpecArgs& a, const int32_t* MG, int rd,
                                                  const ReadDesc& d, bool nar, Tally& tl) {
-  constexpr bool WRITE = MODE != SEL_EMULATE;
   const uint64_t t_start = g_trace ? __builtin_amdgcn_s_memrealtime() : 0;
   int r = (int)(threadIdx.x & 63);
   asm volatile("" : "+v"(r));  // per octet: what derives from it is not held in registers over light_read
@@ -1617,16 +1645,6 @@ __device__ __forceinline__ uint64_t light_packed(const DevBatch& b, const SpecAr
     const uint64_t om = __builtin_amdgcn_ballot_w64(valid && i < k && cid == k_cid && !j_pad && sd.len >= len95 && (a1 || b1));
     C |= (uint64_t)byte_of(cm) << (8 * k);
     O |= (uint64_t)byte_of(om) << (8 * k);
-    if (WRITE) {  // seedcov of k's region over its chain's seeds (bwamem.c:784-788)
-      const int64_t krb = grp64(x.rb, k), kre = grp64(x.re, k);
-      const int kqb = grp(x.qb, k), kqe = grp(x.qe, k);
-      int v = valid && cid == k_cid && sd.qbeg >= kqb && sd.qbeg + sd.len <= kqe && sd.rbeg >= krb &&
-                      sd.rbeg + sd.len <= kre ? sd.len : 0;
-      v += dpp<0xB1>(0, v);
-      v += dpp<0x4E>(0, v);
-      v += dpp<0x141>(0, v);
-      cov = i == k ? v : cov;
-    }
   }
   // ---- 2. the sequential decisions of the eight reads at once (light_read's, as selects)
   uint32_t ext = 0, skip = pad_m, pend = 0, spend = 0, unc = 0;
@@ -1661,28 +1679,44 @@ __device__ __forceinline__ uint64_t light_packed(const DevBatch& b, const SpecAr
       if (p >= 0) a.tasks[spec_list_off(list, b.n_chains, b.n_seeds) + p] = make_int2(d.s0 + i, d.c0 + cid);
     }
     if (nar && pend && i == 0) atomicOr(&a.rbits[rd >> 5], 1u << (rd & 31));  // the final pass takes it first
-  } else {
-    const bool wr = nar && !missed;
-    if (wr && ((ext >> i) & 1u)) {  // the region of seed i, at its rank (bwamem.c:718-792 field by field; rest zero)
-      const int slot = (int)__popc(ext & ((1u << i) - 1u));
-      uint2* dst = reinterpret_cast<uint2*>(a.out + d.s0 + slot);
-      dst[0] = make_uint2((uint32_t)x.rb, (uint32_t)((uint64_t)x.rb >> 32));
-      dst[1] = make_uint2((uint32_t)x.re, (uint32_t)((uint64_t)x.re >> 32));
-      dst[2] = make_uint2((uint32_t)x.qb, (uint32_t)x.qe);
-      dst[3] = make_uint2((uint32_t)rid, (uint32_t)x.score);
-      dst[4] = make_uint2((uint32_t)x.truesc, 0u);
-      dst[5] = make_uint2(0u, 0u);
-      dst[6] = make_uint2(0u, (uint32_t)x.w);
-      dst[7] = make_uint2((uint32_t)cov, 0u);
-      dst[8] = make_uint2(0u, (uint32_t)sd.len);
-      dst[9] = make_uint2(0u, __float_as_uint(frac));
-      dst[10] = make_uint2(0u, 0u);
-      tl.cells += x.cells;
-      tl.rows += x.rows;
-      tl.calls += x.calls - 1;
-    }
-    if (wr && i == 0) a.out_n[rd] = (int)__popc(ext);
   }
+  // (emulate) no round-B task: no a.ext[] of the read changes before the final
+  // pass, which would load, decide and write what this pass does
+  const bool wr = nar && (MODE == SEL_EMULATE ? a.emu_finish && !(pend | spend) : !missed);
+  // seedcov of an extended seed k's region over its chain's seeds (bwamem.c:784-788),
+  // summed over the group into lane k: the k some read this pass writes extended
+#pragma unroll 1
+  for (int k = 0; k < kPackW; ++k) {
+    if (__builtin_amdgcn_ballot_w64(wr && ((ext >> k) & 1u)) == 0) continue;
+    const int k_cid = grp(cid, k);
+    const int64_t krb = grp64(x.rb, k), kre = grp64(x.re, k);
+    const int kqb = grp(x.qb, k), kqe = grp(x.qe, k);
+    int v = has_s && k < d.ns && cid == k_cid && sd.qbeg >= kqb && sd.qbeg + sd.len <= kqe && sd.rbeg >= krb &&
+                    sd.rbeg + sd.len <= kre ? sd.len : 0;
+    v += dpp<0xB1>(0, v);
+    v += dpp<0x4E>(0, v);
+    v += dpp<0x141>(0, v);
+    cov = i == k ? v : cov;
+  }
+  if (wr && ((ext >> i) & 1u)) {  // the region of seed i, at its rank (bwamem.c:718-792 field by field; rest zero)
+    const int slot = (int)__popc(ext & ((1u << i) - 1u));
+    uint2* dst = reinterpret_cast<uint2*>(a.out + d.s0 + slot);
+    dst[0] = make_uint2((uint32_t)x.rb, (uint32_t)((uint64_t)x.rb >> 32));
+    dst[1] = make_uint2((uint32_t)x.re, (uint32_t)((uint64_t)x.re >> 32));
+    dst[2] = make_uint2((uint32_t)x.qb, (uint32_t)x.qe);
+    dst[3] = make_uint2((uint32_t)rid, (uint32_t)x.score);
+    dst[4] = make_uint2((uint32_t)x.truesc, 0u);
+    dst[5] = make_uint2(0u, 0u);
+    dst[6] = make_uint2(0u, (uint32_t)x.w);
+    dst[7] = make_uint2((uint32_t)cov, 0u);
+    dst[8] = make_uint2(0u, (uint32_t)sd.len);
+    dst[9] = make_uint2(0u, __float_as_uint(frac));
+    dst[10] = make_uint2(0u, 0u);
+    tl.cells += x.cells;
+    tl.rows += x.rows;
+    tl.calls += x.calls - 1;
+  }
+  if (wr && i == 0) a.out_n[rd] = (int)__popc(ext);
   if (uint32_t* const tr = g_trace) {  // trace_read's record, a group's lanes one word each
     const uint64_t t_end = __builtin_amdgcn_s_memrealtime();
     uint32_t v = 1u;  // shape: light
@@ -1695,7 +1729,7 @@ __device__ __forceinline__ uint64_t light_packed(const DevBatch& b, const SpecAr
     v = i == 6 ? __builtin_amdgcn_s_getreg((31 << 11) | 20) : v;
     if (nar && !missed) tr[((size_t)MODE * b.n_reads + rd) * 8 + i] = v;
   }
-  return __builtin_amdgcn_ballot_w64(nar && missed);
+  return __builtin_amdgcn_ballot_w64(MODE == SEL_EMULATE ? wr : nar && missed);
 }
 
 // The light reads of a batch.  With SpecArgs::light_pack (bwagpu_ctx_light_pack,
@@ -1704,6 +1738,15 @@ __device__ __forceinline__ uint64_t light_packed(const DevBatch& b, const SpecAr
 // wider ones and a narrow read the final pass missed a result for one after
 // another (light_read).  Without it, and with risky_first, every light read
 // of the wave's share goes through light_read.
+// SpecArgs::emu_finish: the emulate pass writes the reads it
+// leaves no round-B task (finished: a bit in fbits), and lists the others in
+// rlist; the final pass's units are then `per` entries of that list each,
+// group g < per of unit u the read rlist[per * u + g] — or, walking all reads
+// (risky_first, no light_pack), it leaves the finished ones out.  per = the
+// list's length over the grid's waves, rounded up, at most eight: the listed
+// reads are the batch's hard ones (most of them wider than eight seeds, which a
+// wave runs one after another), so a short list is spread one read per wave
+// rather than eight to a wave with most waves idle.
 template <int MODE>
 __global__ void __launch_bounds__(kBlock) spec_select_light(DevOpt o, DevRef ref, DevBatch b, SpecArgs a,
                                                             int tb_bytes) {
@@ -1765,12 +1808,22 @@ __global__ void __launch_bounds__(kBlock) spec_select_light(DevOpt o, DevRef ref
   };
   const bool dyn = MODE == SEL_FINAL && a.risky_first;
   const bool pack = a.light_pack && !dyn;
+  const bool fin = a.emu_finish != 0;
+  const bool listed = MODE == SEL_FINAL && fin && pack;  // the units are octets of rlist
+  const int n_list =
+      listed ? uni(__hip_atomic_load(&a.ctr[SPC_LIST_N], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) : b.n_reads;
   // a unit: an octet of reads (pack: a group of eight lanes per read), else 64
   // reads of the wave's share at once (a lane per read), or the one next_read() gives
-  const int n_units = pack ? (b.n_reads + kPackW - 1) / kPackW : b.n_reads;
+  const int per = listed ? min(max((n_list + NW - 1) / NW, 1), kPackW) : kPackW;  // a packed unit's reads
+  const int n_units = pack ? (n_list + per - 1) / per : b.n_reads;
   const int unit_reads = pack ? kPackW : dyn ? 1 : 64;
   const uint64_t first_lanes = pack ? 0x0101010101010101ull : dyn ? 1ull : ~0ull;  // a read's first lane
-  const auto lane_read = [&](int u) { return pack ? kPackW * u + (r >> 3) : dyn ? u : u + r * NW; };
+  const auto lane_read = [&](int u) {
+    const int x = pack ? per * u + (r >> 3) : dyn ? u : u + r * NW;
+    if (MODE == SEL_FINAL && listed) return (r >> 3) < per && x < n_list ? a.rlist[x] : b.n_reads;
+    return x;
+  };
+  int n_mine = 0, n_fin_nar = 0, n_fin_wide = 0;  // (emulate, fin) this wave's counts
   // A wave first goes through units — the narrow reads packed, the others
   // only listed (wl) — then through the list with light_read, and so on while
   // units are left: the units' per-lane descriptors are not held over
@@ -1780,18 +1833,47 @@ __global__ void __launch_bounds__(kBlock) spec_select_light(DevOpt o, DevRef ref
   while (un < n_units) {
     int nw = 0;
     ReadDesc dn{};
-    if (lane_read(un) < b.n_reads) dn = a.rdesc[lane_read(un)];
+    int rdn = lane_read(un);
+    if (rdn < b.n_reads) dn = a.rdesc[rdn];
     while (un < n_units && nw + unit_reads <= kLightList) {
       const ReadDesc d = dn;
-      const int rd = lane_read(un);
+      const int rd = rdn;
       un = dyn ? next_read() : pack ? un + NW : un + 64 * NW;
-      if (un < n_units && lane_read(un) < b.n_reads) dn = a.rdesc[lane_read(un)];
+      if (un < n_units) {
+        rdn = lane_read(un);
+        if (rdn < b.n_reads) dn = a.rdesc[rdn];
+      }
       // not the heavy kernel's read, nor one flagged by spec_reads_kernel
-      const bool mine = rd < b.n_reads && !(d.ns > kSelLight || d.nch > kSelLight) && !(d.lq > a.lq_bound);
+      bool mine = rd < b.n_reads && !(d.ns > kSelLight || d.nch > kSelLight) && !(d.lq > a.lq_bound);
+      // (walking all reads) nor one the emulate pass finished
+      if (MODE == SEL_FINAL && fin && !listed && mine) mine = !((a.fbits[rd >> 5] >> (rd & 31)) & 1u);
       const bool nar = pack && mine && d.ns <= kPackW && d.nch <= kPackW;
-      if (WRITE && mine && !nar && d.ns == 0) a.out_n[rd] = 0;
+      const bool empty = mine && !nar && d.ns == 0;
+      if ((WRITE || fin) && empty) a.out_n[rd] = 0;
       uint64_t wide = __builtin_amdgcn_ballot_w64(mine && !nar && d.ns != 0);
-      if (pack) wide |= light_packed<MODE>(b, a, MG, rd, d, nar, tl);
+      if constexpr (MODE == SEL_EMULATE) {
+        uint64_t done = __builtin_amdgcn_ballot_w64(empty);
+        if (pack) done |= light_packed<MODE>(b, a, MG, rd, d, nar, tl);
+        if (fin) {  // the finished reads' bits and counts; the other narrow reads listed
+          done &= first_lanes;
+          const bool first = (first_lanes >> r) & 1, fin_here = (done >> r) & 1;
+          const int p = wave_append(&a.ctr[SPC_LIST_N], first && nar && !fin_here);
+          if (p >= 0) a.rlist[p] = rd;
+          if (pack) {  // an octet's bits are one byte of a word: bit 8g of `done` to bit g
+            const uint32_t byte = (uint32_t)((done * 0x0102040810204080ull) >> 56);
+            const int rd0 = kPackW * (rd >> 3);  // (the octet's first read, in every lane)
+            if (r == 0 && byte) atomicOr(&a.fbits[rd0 >> 5], byte << (rd0 & 31));
+          } else if (fin_here) {
+            atomicOr(&a.fbits[rd >> 5], 1u << (rd & 31));
+          }
+          const bool narrow = d.ns <= kPackW && d.nch <= kPackW;
+          n_mine += (int)__popcll(__builtin_amdgcn_ballot_w64(mine) & first_lanes);
+          n_fin_nar += (int)__popcll(__builtin_amdgcn_ballot_w64(fin_here && narrow));
+          n_fin_wide += (int)__popcll(__builtin_amdgcn_ballot_w64(fin_here && !narrow));
+        }
+      } else {
+        if (pack) wide |= light_packed<MODE>(b, a, MG, rd, d, nar, tl);
+      }
       wide &= first_lanes;
       if ((wide >> r) & 1) wl[nw + (int)__popcll(wide & lt_mask)] = rd;
       nw += (int)__popcll(wide);
@@ -1806,13 +1888,19 @@ __global__ void __launch_bounds__(kBlock) spec_select_light(DevOpt o, DevRef ref
       const ReadDesc u = uniform_desc(wn);
       const int rd = uni(wl[k]);
       if (k + 1 < nw) wn = a.rdesc[uni(wl[k + 1])];
-      light_read<MODE>(o, ref, b, a, MG, tbl, tbr, rd, u, tl);
+      const bool done = light_read<MODE>(o, ref, b, a, MG, tbl, tbr, rd, u, tl);
+      if (MODE == SEL_EMULATE && done) ++(u.ns <= kPackW && u.nch <= kPackW ? n_fin_nar : n_fin_wide);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   }
-  if constexpr (WRITE) block_stats<64>(tl, a.stats);
+  if (WRITE || fin) block_stats<64>(tl, a.stats);
+  if (MODE == SEL_EMULATE && fin && r == 0) {
+    if (n_mine) atomicAdd(&a.ctr[SPC_LIGHT_N], n_mine);
+    if (n_fin_nar) atomicAdd(&a.ctr[SPC_FIN_NAR], n_fin_nar);
+    if (n_fin_wide) atomicAdd(&a.ctr[SPC_FIN_WIDE], n_fin_wide);
+  }
 }
 
 // HEAVY reads with pair matrices (<= kSelMatMaxSeeds seeds).  The same
@@ -2267,6 +2355,19 @@ static int light_pack_wgs() {
   }();
   return v;
 }
+// ... and the divisor of that grid for the final pass when it runs from the
+// emulate pass's list of unfinished reads (BWAGPU_LIGHT_LIST_DIV, an A/B knob;
+// DESIGN.md §25 has the sweep)
+#ifndef BWAGPU_LIGHT_LIST_DIV_DEFAULT
+#define BWAGPU_LIGHT_LIST_DIV_DEFAULT 4
+#endif
+static int light_list_div() {
+  static const int v = [] {
+    const char* e = getenv("BWAGPU_LIGHT_LIST_DIV");
+    return std::min(std::max(e && e[0] ? atoi(e) : BWAGPU_LIGHT_LIST_DIV_DEFAULT, 1), 64);
+  }();
+  return v;
+}
 static int device_cus() {
   int dev = 0, ncu = 0;
   if (hipGetDevice(&dev) != hipSuccess ||
@@ -2294,6 +2395,9 @@ static void launch_select(const DevOpt& o, const DevRef& ref, const DevBatch& b,
     if (a.light_pack && !(MODE == SEL_FINAL && a.risky_first)) {
       const int octets = (b.n_reads + kPackW - 1) / kPackW, per_wg = kBlock / 64;
       nb = std::min(nb, std::max(1, std::min((octets + per_wg - 1) / per_wg, light_pack_wgs() * device_cus())));
+      // the final pass over the emulate pass's list: its length is known on the
+      // device only, and the stride loop is right for any grid
+      if (MODE == SEL_FINAL && a.emu_finish) nb = std::max(1, nb / light_list_div());
     }
     hipLaunchKernelGGL((spec_select_light<MODE>), dim3(nb), dim3(kBlock), lds, st, o, ref, b, a, tb_bytes);
   }
@@ -2353,6 +2457,15 @@ int ext_short_default() {
 int ungapped_default() {
   static const int on = [] {
     const char* e = getenv("BWAGPU_UNGAPPED");
+    return !(e && e[0] == '0');
+  }();
+  return on;
+}
+// The emulate pass finishes the light reads it leaves no round-B task
+// (bwagpu_ctx_emu_finish).  BWAGPU_EMU_FINISH=0 starts contexts with it off.
+int emu_finish_default() {
+  static const int on = [] {
+    const char* e = getenv("BWAGPU_EMU_FINISH");
     return !(e && e[0] == '0');
   }();
   return on;
@@ -2433,7 +2546,10 @@ hipError_t launch_spec_chain2aln(const DevOpt& o, const DevRef& ref, const DevBa
     launch_select<SEL_EMULATE>(o, ref, b, a, tb_bytes, st, ss);
     launch_ext_round(o, ref, b, a, 1, tb_bytes, lq_max, st, ss);
   }
-  launch_select<SEL_FINAL>(o, ref, b, a, tb_bytes, st, ss);
+  // (no chains: no emulate pass ran, so nothing is finished or listed, and the final pass takes every read)
+  SpecArgs af = a;
+  if (!b.n_chains) af.emu_finish = 0;
+  launch_select<SEL_FINAL>(o, ref, b, af, tb_bytes, st, ss);
   if (b.n_chains && lq_max > kSpecBinLen[0] && !a.emu_strict) launch_ext_round(o, ref, b, a, 2, tb_bytes, lq_max, st, ss);
   if (b.n_chains) launch_select<SEL_REDO>(o, ref, b, a, tb_bytes, st, ss);
   return hipGetLastError();
@@ -2450,7 +2566,7 @@ __global__ void __launch_bounds__(256) spec_clear_kernel(SpecArgs a, int nr, int
       for (int i = t0; i < nr; i += nt) a.out_n[i] = 0;
       break;
     case 2:
-      for (int i = t0; i < nr / 32 + 1; i += nt) a.rbits[i] = 0;
+      for (int i = t0; i < nr / 32 + 1; i += nt) a.rbits[i] = a.fbits[i] = 0;
       break;
     case 3:
       for (int i = t0; i < kQHWords; i += nt) a.qh[i] = 0;

@@ -375,6 +375,11 @@ class Engine:
         on; acts only while the row bound is on); -> the previous setting"""
         return self.lib.bwagpu_ctx_ungapped(self.ctx, int(on))
 
+    def emu_finish(self, on: int = -1) -> int:
+        """this context's finishing of decided light reads in the emulate
+        selection pass (bwagpu_ctx_emu_finish, default on); -> the previous setting"""
+        return self.lib.bwagpu_ctx_emu_finish(self.ctx, int(on))
+
     def row_bound(self, on: int = -1) -> int:
         """this context's row bound in the packed extension kernels
         (bwagpu_ctx_row_bound, default on); -> the previous setting"""

@@ -37,6 +37,8 @@ int bwagpu_debug_sup_shift(bwagpu_ctx_t *ctx, int32_t shift);
    per-read kernels); the speculative path writes its selection passes
    (emulate, final, redo) at dev_ptr[8 (pass n_reads + r) ..]: start / end,
    seeds, regions, XCC_ID, shape — so the buffer needs 24 x n_reads words.
+   With bwagpu_ctx_emu_finish on, a light read the emulate pass finished has
+   its record under pass 0 (emulate) only.
    Not part of the reference interface (the reference logs stage wall times
    with getUs(), src/util.h:34-40). */
 int bwagpu_debug_set_trace(bwagpu_ctx_t *ctx, void *dev_ptr);
@@ -138,6 +140,21 @@ int bwagpu_ctx_ungapped(bwagpu_ctx_t *ctx, int on);
    sum of their query lengths, and the left and the right sides that stayed on
    the phased lists */
 int bwagpu_debug_spec_ungapped(bwagpu_ctx_t *ctx, void *stream, int64_t *out);
+/* the emulate pass finishes decided light reads (default on;
+   BWAGPU_EMU_FINISH=0 starts contexts with it off): a light read the emulate
+   selection pass leaves no round-B task has every extension result the final
+   pass would use, so that pass writes its regions itself and lists the other
+   light reads; the final light pass then takes only the listed reads
+   (DESIGN.md §25).  0: the final pass takes every light read.  Regions and the
+   cell, row and call counters are identical either way.  on < 0 only queries;
+   returns the previous setting. */
+int bwagpu_ctx_emu_finish(bwagpu_ctx_t *ctx, int on);
+/* diagnostics of the last device-entry batch on `stream` (waits for it), out:
+   4 entries: the narrow light reads (at most eight seeds and eight chains) the
+   emulate pass finished, the wider ones, the light reads it listed for the
+   final pass, and the batch's light reads as that pass counts them; all 0 with
+   the switch off or for a batch without chains */
+int bwagpu_debug_spec_finish(bwagpu_ctx_t *ctx, void *stream, int64_t *out);
 /* the packed extension kernels' row bound (default on): a ksw_extend2 call
    ends once no later target row can change its score, qle, tle, gtle, gscore
    or max_off (every later cell is bounded by a stored value plus max(mat) per
