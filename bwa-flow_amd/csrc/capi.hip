@@ -182,6 +182,7 @@ int create_common(int device, const bwagpu_opt_t* opt, const bwagpu_bns_t* bns, 
   ctx->ext_short_fill = ext_short_fill_default();
   ctx->light_pack = light_pack_default();
   ctx->ungapped = ungapped_default();
+  ctx->ungapped_right = ungapped_right_default();
   ctx->emu_finish = emu_finish_default();
   *made = ctx;
   HIPC(hipSetDevice(device), "hipSetDevice");
@@ -380,6 +381,8 @@ int enqueue_spec(bwagpu_ctx_t* ctx, Slot& s, const DevBatch& db, int lq_max, bwa
   // the certificate only moves work out of the DP, as the row bound does: it acts under that switch
   a.ung = nullptr;
   if (ctx->ungapped && ctx->opt.row_bound) HIPC(s.d_ung.get(a.ung, n_tasks), "hipMalloc(ung)");
+  a.ungt = nullptr;
+  if (a.ung && ctx->ungapped_right) HIPC(s.d_ungt.get(a.ungt, n_tasks), "hipMalloc(ungt)");
   // pair matrices of heavy reads: sum over them of 2 * ns * ceil(ns / 64) words,
   // <= 2 * ns_total * (1 + ns_max / 64); reads that do not fit take the per-seed kernel
   HIPC(s.d_mat.get(a.mat, (size_t)std::max<int64_t>(1 << 20, 16 * (int64_t)ns)), "hipMalloc(mat)");
@@ -846,16 +849,23 @@ int bwagpu_debug_live_buffers(int64_t* n, int64_t* bytes) {
   return BWAGPU_OK;
 }
 
-int bwagpu_debug_occupancy(bwagpu_ctx_t* ctx, void* stream, int64_t* out) {
-  if (!ctx || !out) return BWAGPU_E_INVAL;
+// the SPC_* counter words of the last device-entry batch on `stream` (waits for it): what the
+// bwagpu_debug_spec_* readers share
+static int spec_ctr_words(bwagpu_ctx_t* ctx, void* stream, int32_t* c) {
   hipStream_t st = nullptr;
   if (int rc = entry_stream(ctx, stream, &st)) return rc;
   int k = 0;
   while (k < BWAGPU_NUM_SLOTS && ctx->dev_stream[k] != st) ++k;
   if (k == BWAGPU_NUM_SLOTS || !ctx->dev_scratch[k].d_ctr.p) return fail(ctx, BWAGPU_E_INVAL, "no device-entry batch on this stream");
   HIPC(hipStreamSynchronize(st), "hipStreamSynchronize");
+  HIPC(hipMemcpy(c, ctx->dev_scratch[k].d_ctr.p, sizeof(int32_t) * SPC_WORDS, hipMemcpyDeviceToHost), "hipMemcpy(ctr)");
+  return BWAGPU_OK;
+}
+
+int bwagpu_debug_occupancy(bwagpu_ctx_t* ctx, void* stream, int64_t* out) {
+  if (!ctx || !out) return BWAGPU_E_INVAL;
   int32_t c[SPC_WORDS];
-  HIPC(hipMemcpy(c, ctx->dev_scratch[k].d_ctr.p, sizeof c, hipMemcpyDeviceToHost), "hipMemcpy(ctr)");
+  if (int rc = spec_ctr_words(ctx, stream, c)) return rc;
   memcpy(out, c + 32, 14 * sizeof(int64_t));
 #ifdef BWAGPU_OCC_DIAG
   return BWAGPU_OK;
@@ -866,14 +876,8 @@ int bwagpu_debug_occupancy(bwagpu_ctx_t* ctx, void* stream, int64_t* out) {
 
 int bwagpu_debug_spec_counters(bwagpu_ctx_t* ctx, void* stream, int64_t* out) {
   if (!ctx || !out) return BWAGPU_E_INVAL;
-  hipStream_t st = nullptr;
-  if (int rc = entry_stream(ctx, stream, &st)) return rc;
-  int k = 0;
-  while (k < BWAGPU_NUM_SLOTS && ctx->dev_stream[k] != st) ++k;
-  if (k == BWAGPU_NUM_SLOTS || !ctx->dev_scratch[k].d_ctr.p) return fail(ctx, BWAGPU_E_INVAL, "no device-entry batch on this stream");
-  HIPC(hipStreamSynchronize(st), "hipStreamSynchronize");
   int32_t c[SPC_WORDS];
-  HIPC(hipMemcpy(c, ctx->dev_scratch[k].d_ctr.p, sizeof c, hipMemcpyDeviceToHost), "hipMemcpy(ctr)");
+  if (int rc = spec_ctr_words(ctx, stream, c)) return rc;
   for (int r = 0; r < kSpecRounds; ++r) {
     out[r] = 0;
     for (int b = 0; b < kSpecBins; ++b) out[r] += c[SPC_CNT + r * kSpecBins + b];
@@ -939,14 +943,8 @@ int bwagpu_ctx_light_pack(bwagpu_ctx_t* ctx, int on) {
 
 int bwagpu_debug_spec_short(bwagpu_ctx_t* ctx, void* stream, int64_t* out) {
   if (!ctx || !out) return BWAGPU_E_INVAL;
-  hipStream_t st = nullptr;
-  if (int rc = entry_stream(ctx, stream, &st)) return rc;
-  int k = 0;
-  while (k < BWAGPU_NUM_SLOTS && ctx->dev_stream[k] != st) ++k;
-  if (k == BWAGPU_NUM_SLOTS || !ctx->dev_scratch[k].d_ctr.p) return fail(ctx, BWAGPU_E_INVAL, "no device-entry batch on this stream");
-  HIPC(hipStreamSynchronize(st), "hipStreamSynchronize");
   int32_t c[SPC_WORDS];
-  HIPC(hipMemcpy(c, ctx->dev_scratch[k].d_ctr.p, sizeof c, hipMemcpyDeviceToHost), "hipMemcpy(ctr)");
+  if (int rc = spec_ctr_words(ctx, stream, c)) return rc;
   out[0] = c[SPC_SHORT_N];
   for (int r = 0; r < 2; ++r) {  // rounds A and B, the first length bin's lists
     const int l = r * kSpecBins;
@@ -967,14 +965,8 @@ int bwagpu_ctx_ungapped(bwagpu_ctx_t* ctx, int on) {
 
 int bwagpu_debug_spec_ungapped(bwagpu_ctx_t* ctx, void* stream, int64_t* out) {
   if (!ctx || !out) return BWAGPU_E_INVAL;
-  hipStream_t st = nullptr;
-  if (int rc = entry_stream(ctx, stream, &st)) return rc;
-  int k = 0;
-  while (k < BWAGPU_NUM_SLOTS && ctx->dev_stream[k] != st) ++k;
-  if (k == BWAGPU_NUM_SLOTS || !ctx->dev_scratch[k].d_ctr.p) return fail(ctx, BWAGPU_E_INVAL, "no device-entry batch on this stream");
-  HIPC(hipStreamSynchronize(st), "hipStreamSynchronize");
   int32_t c[SPC_WORDS];
-  HIPC(hipMemcpy(c, ctx->dev_scratch[k].d_ctr.p, sizeof c, hipMemcpyDeviceToHost), "hipMemcpy(ctr)");
+  if (int rc = spec_ctr_words(ctx, stream, c)) return rc;
   for (int r = 0; r < kSpecRounds; ++r) {
     out[4 * r + 0] = c[SPC_UNG_N + r];
     out[4 * r + 1] = c[SPC_UNG_Q + r];
@@ -983,6 +975,24 @@ int bwagpu_debug_spec_ungapped(bwagpu_ctx_t* ctx, void* stream, int64_t* out) {
       out[4 * r + 2] += c[SPC_LCNT + r * kSpecBins + bin];
       out[4 * r + 3] += c[SPC_RCNT + r * kSpecBins + bin];
     }
+  }
+  return BWAGPU_OK;
+}
+
+int bwagpu_ctx_ungapped_right(bwagpu_ctx_t* ctx, int on) {
+  if (!ctx) return BWAGPU_E_INVAL;
+  const int prev = ctx->ungapped_right;
+  if (on >= 0) ctx->ungapped_right = on ? 1 : 0;
+  return prev;
+}
+
+int bwagpu_debug_spec_ungapped_right(bwagpu_ctx_t* ctx, void* stream, int64_t* out) {
+  if (!ctx || !out) return BWAGPU_E_INVAL;
+  int32_t c[SPC_WORDS];
+  if (int rc = spec_ctr_words(ctx, stream, c)) return rc;
+  for (int r = 0; r < kSpecRounds; ++r) {
+    out[2 * r + 0] = c[SPC_UNGR_N + r];
+    out[2 * r + 1] = c[SPC_UNGR_Q + r];
   }
   return BWAGPU_OK;
 }
@@ -996,14 +1006,8 @@ int bwagpu_ctx_emu_finish(bwagpu_ctx_t* ctx, int on) {
 
 int bwagpu_debug_spec_finish(bwagpu_ctx_t* ctx, void* stream, int64_t* out) {
   if (!ctx || !out) return BWAGPU_E_INVAL;
-  hipStream_t st = nullptr;
-  if (int rc = entry_stream(ctx, stream, &st)) return rc;
-  int k = 0;
-  while (k < BWAGPU_NUM_SLOTS && ctx->dev_stream[k] != st) ++k;
-  if (k == BWAGPU_NUM_SLOTS || !ctx->dev_scratch[k].d_ctr.p) return fail(ctx, BWAGPU_E_INVAL, "no device-entry batch on this stream");
-  HIPC(hipStreamSynchronize(st), "hipStreamSynchronize");
   int32_t c[SPC_WORDS];
-  HIPC(hipMemcpy(c, ctx->dev_scratch[k].d_ctr.p, sizeof c, hipMemcpyDeviceToHost), "hipMemcpy(ctr)");
+  if (int rc = spec_ctr_words(ctx, stream, c)) return rc;
   out[0] = c[SPC_FIN_NAR];
   out[1] = c[SPC_FIN_WIDE];
   out[2] = c[SPC_LIST_N];

@@ -87,7 +87,7 @@ struct Slot {
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
   DevBuf d_in, d_win, d_srt, d_prog, d_desc, d_out, d_n, d_stats, d_lists, d_counts;
   DevBuf d_cread, d_ext, d_tasks, d_ctr, d_regpos, d_skipf, d_heavy, d_redo, d_rbits, d_rlist;  // speculative path
-  DevBuf d_schain, d_hinfo, d_mat, d_cov, d_hflag, d_colent, d_qh, d_longc, d_sorth, d_stasks, d_ftask, d_ftaskR, d_ung;
+  DevBuf d_schain, d_hinfo, d_mat, d_cov, d_hflag, d_colent, d_qh, d_longc, d_sorth, d_stasks, d_ftask, d_ftaskR, d_ung, d_ungt;
   SpecStreams spec;  // created on first use (choose_side)
   bool side_chosen = false;
   HostBuf h_in, h_out, h_n, h_stats;
@@ -169,6 +169,7 @@ struct bwagpu_ctx {
   int light_pack = 0;  // bwagpu_ctx_light_pack (BWAGPU_LIGHT_PACK or the compiled default when made)
   int ext_short_fill = 0;  // bwagpu_ctx_ext_short_fill (BWAGPU_EXT_SHORT_FILL or the compiled default when made)
   int ungapped = 1;  // bwagpu_ctx_ungapped (BWAGPU_UNGAPPED or on when made); acts only while opt.row_bound is on
+  int ungapped_right = 1;  // bwagpu_ctx_ungapped_right (BWAGPU_UNGAPPED_RIGHT or on when made); acts only while ungapped does
   int emu_finish = 1;  // bwagpu_ctx_emu_finish (BWAGPU_EMU_FINISH or on when made)
   Slot slot[BWAGPU_NUM_SLOTS];
   // bwagpu_chain2aln_device: the caller's streams, one per slot's scratch (a

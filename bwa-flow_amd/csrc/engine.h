@@ -146,6 +146,9 @@ enum {
   SPC_FIN_WIDE = 110, // ... wider light reads
   SPC_LIST_N = 111,   // light reads the emulate pass left to the final pass: entries of SpecArgs::rlist
   SPC_LIGHT_N = 112,  // light reads of the batch, as the emulate pass counts them (diagnostic)
+  SPC_UNGR_N = 113,   // [round] certified right sides behind a left side that needs the DP, settled after the
+                      // left launch by spec_settle_right_kernel (diagnostic)
+  SPC_UNGR_Q = 116,   // [round] ... and the sum of their query lengths
   SPC_WORDS = 128
 };
 // sharded queue heads of the extension task lists (SpecArgs::qh, zeroed per
@@ -193,6 +196,15 @@ struct UngRec {
   } side[2];  // left, right
 };
 static_assert(sizeof(UngRec) == 32, "UngRec layout");
+// What spec_settle_right_kernel needs of a task besides its UngRec (DESIGN.md
+// §26): spec_ungapped_kernel writes it beside the record, so the kernel that
+// finishes the late right sides reads two coalesced arrays and no task list
+struct UngTask {
+  int64_t rbeg;
+  int32_t pos;   // the seed's slot (SeedExt)
+  uint32_t qls;  // as FatTask
+};
+static_assert(sizeof(UngTask) == 16, "UngTask layout");
 struct SpecArgs {
   int lq_bound;               // reads longer than this set ERR_LEN and are skipped
   ChainWin* win;              // per chain
@@ -225,6 +237,9 @@ struct SpecArgs {
                               // extension: the tasks with a left side, by that side's length
   FatTask* ftaskR;            // the phased extension: the tasks with a right side, by its length
   UngRec* ung;                // per task of a phased list (same offsets as tasks); null: the certificate is off
+  UngTask* ungt;              // per task as ung; null: a certified right side behind a left side that needs the DP
+                              // runs the DP on the right list, else spec_settle_right_kernel settles it after the
+                              // left launch (bwagpu_ctx_ungapped_right)
   int risky_first;            // spec_select_light<SEL_FINAL>: reads with a round-B task first (BWAGPU_LIGHT_RISKY_FIRST)
   int emu_strict;             // spec_select_light<SEL_EMULATE>: round-B tasks for uncertain skips too (BWAGPU_EMU_STRICT)
   int light_pack;             // spec_select_light: narrow reads eight per wave (bwagpu_ctx_light_pack)
@@ -258,6 +273,8 @@ struct SpecStreams {
 };
 // the ungapped certificate new contexts start with (BWAGPU_UNGAPPED, else on)
 int ungapped_default();
+// ... and its late settling of right sides (BWAGPU_UNGAPPED_RIGHT, else on)
+int ungapped_right_default();
 // the emulate pass's finishing of decided light reads new contexts start with (BWAGPU_EMU_FINISH, else on)
 int emu_finish_default();
 // the form new contexts start with (bwagpu_debug_ext_form; process-wide default)

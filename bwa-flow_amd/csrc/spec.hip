@@ -2461,6 +2461,16 @@ int ungapped_default() {
   }();
   return on;
 }
+// Certified right sides behind a DP left side are settled after the left
+// launch (bwagpu_ctx_ungapped_right).  BWAGPU_UNGAPPED_RIGHT=0
+// starts contexts with that off.
+int ungapped_right_default() {
+  static const int on = [] {
+    const char* e = getenv("BWAGPU_UNGAPPED_RIGHT");
+    return !(e && e[0] == '0');
+  }();
+  return on;
+}
 // The emulate pass finishes the light reads it leaves no round-B task
 // (bwagpu_ctx_emu_finish).  BWAGPU_EMU_FINISH=0 starts contexts with it off.
 int emu_finish_default() {

@@ -19,80 +19,134 @@ namespace bwagpu {
 __device__ __forceinline__ int side_key(int qlen) { return 255 - min(qlen, 255); }  // descending
 
 
-// ------------------------------------------- the ungapped certificate (§24)
+// ------------------------------------- the ungapped certificate (§24, §26)
 // A side whose diagonal loses less than the cheapest gap open needs no DP
 // (ungapped.h).  spec_ungapped_kernel decides that once per side, ahead of the
 // sort, and stores the decision with what the side leaves; the count and the
-// scatter read the stored record, so both see the same lists.  One thread per
-// (task, side).  The query bytes come from the read (a left side runs down
-// from the seed), the target bases from the pac at the 2-strand coordinates
-// that fill_side_run reads, sixteen of each per pass from two loads; P never
-// falls, so a pass is abandoned at its end.
+// scatter read the stored record, so both see the same lists.  The query bytes
+// come from the read (a left side runs down from the seed), the target bases
+// from the pac at the 2-strand coordinates that fill_side_run reads.
 // keep_short > 0 (the first bin's lists with bwagpu_ctx_ext_short_fill at 0:
 // every side up to the short threshold takes the short phase) leaves those
 // sides to the lists.
+//
+// The unit of work is a pass, sixteen bases of a side, summarised as an UngSeg
+// and folded per side in order (ungapped.h).  A block takes 128 tasks at a
+// time, one thread per side: the thread runs the side's first pass itself,
+// and a side that this pass leaves alive lists its later passes in LDS, where
+// the block's threads take them densely, whichever side they belong to; the
+// side's thread then folds the summaries.  (One thread per whole side ran a
+// wave until its longest side was through: ten passes for an average of two.)
 struct UngSide {
   const uint8_t* rd;  // the read; the side's query base j is rd[p0 + d j]
   int64_t x0;         // ... against the 2-strand coordinate x0 + d j
   int p0, d, qlen, lq;
 };
-// one pass: the side's bases [base, last].  Sixteen bases are sixteen bytes of
-// the read and at most five of the pac: one unaligned load of each (fast), from
-// a window pushed back inside the read / the pac where the sixteen would leave
-// it.  A read under 16 bases, a pac under 8 bytes or a pass over both strands
-// (a chain window never is) takes the bases one by one.
-struct UngPass {
-  uint64_t qw[2], tw;
-  int64_t fa, b0;
-  int base, last, ws;
-  bool fast, rev;
-};
-__device__ __forceinline__ UngPass ung_load(const UngSide& s, const DevRef& ref, int base) {
-  UngPass p;
-  p.base = base;
-  p.last = min(base + 15, s.qlen - 1);  // rows j < qlen <= tlen lie in the chain's window
-  p.fast = false;
-  if (base >= s.qlen) return p;
+// one pass: the side's bases [base, min(base + 15, qlen - 1)].  Sixteen bases
+// are sixteen bytes of the read and at most five of the pac: one unaligned load
+// of each (fast), from a window pushed back inside the read / the pac where the
+// sixteen would leave it.  Strand, direction and the window's offsets are
+// resolved once: the query bytes are brought into the pass's order, clamped to
+// 4 and set to 5 past the side's end (a column of zeros in mat8), the target
+// bases into one word at two bits each, complemented on the reverse strand;
+// a base is then two constant bit-field extracts and the mat8 lookup.  P is
+// the count times max_mat less the score sum; M and am are one running
+// maximum of (c, earliest index).  A read under 16 bases, a pac under 8 bytes
+// or a pass over both strands (a chain window never is) takes the bases one by
+// one.  mat: o.mat's 25 scores; mat8[t * 8 + q]: the same for target bases 0-3.
+__device__ __forceinline__ UngSeg ung_pass(const UngSide& s, const DevRef& ref, int base, const int8_t* mat,
+                                           const int8_t* mat8, int max_mat) {
+  const int last = min(base + 15, s.qlen - 1), cnt = last - base + 1;  // rows j < qlen <= tlen lie in the chain's window
   const int64_t two1 = (ref.l_pac << 1) - 1, pac_bytes = (ref.l_pac >> 2) + 1;  // bwa.c:281-282
-  const int64_t xa = s.x0 + (int64_t)s.d * base, xb = s.x0 + (int64_t)s.d * p.last;
-  p.rev = xa >= ref.l_pac;
-  p.fa = p.rev ? two1 - xa : xa;
-  const int64_t fb = p.rev ? two1 - xb : xb;
-  p.fast = s.lq >= 16 && pac_bytes >= 8 && (xb >= ref.l_pac) == p.rev;
-  if (p.fast) {
-    p.ws = min(max(min(s.p0 + s.d * base, s.p0 + s.d * (base + 15)), 0), s.lq - 16);
-    p.b0 = min(min(p.fa, fb) >> 2, pac_bytes - 8);
-    __builtin_memcpy(p.qw, s.rd + p.ws, 16);
-    __builtin_memcpy(&p.tw, ref.pac + p.b0, 8);
-  }
-  return p;
-}
-__device__ __forceinline__ void ung_eat(const UngSide& s, const DevRef& ref, const UngPass& p, const int8_t* mat,
-                                        int max_mat, UngappedScan& sc) {
-  if (p.base >= s.qlen) return;
-  if (p.fast) {
+  const int64_t xa = s.x0 + (int64_t)s.d * base, xb = s.x0 + (int64_t)s.d * last;
+  const bool rev = xa >= ref.l_pac;
+  const int64_t fa = rev ? two1 - xa : xa, fb = rev ? two1 - xb : xb;
+  UngSeg g;
+  if (s.lq >= 16 && pac_bytes >= 8 && (xb >= ref.l_pac) == rev) {
+    const int qa = s.p0 + s.d * base;  // the read's byte of the pass's first base
+    const int ws = min(max(min(qa, qa + 15 * s.d), 0), s.lq - 16);
+    const int64_t b0 = min(min(fa, fb) >> 2, pac_bytes - 8);
+    uint64_t q[2], tw;
+    __builtin_memcpy(q, s.rd + ws, 16);
+    __builtin_memcpy(&tw, ref.pac + b0, 8);
+    // the query: byte m of (hi, lo) = base m
+    uint64_t lo = q[0], hi = q[1];
+    int sh = qa - ws;  // 0 .. 15
+    if (s.d < 0) {
+      lo = __builtin_bswap64(q[1]);
+      hi = __builtin_bswap64(q[0]);
+      sh = 15 - sh;
+    }
+    if (sh >= 8) {
+      lo = hi;
+      hi = 0;
+    }
+    const int sb = (sh & 7) * 8;
+    if (sb) {
+      lo = (lo >> sb) | (hi << (64 - sb));
+      hi >>= sb;
+    }
+    constexpr uint64_t k7f = 0x7f7f7f7f7f7f7f7full, k80 = 0x8080808080808080ull, k04 = 0x0404040404040404ull,
+                       k05 = 0x0505050505050505ull;
+    uint64_t ge = ((((lo & k7f) + (k7f - k04)) | lo) & k80) >> 7;  // 1 in a byte of 5 or more
+    lo = (lo & ~(ge * 255)) | (ge * 4);
+    ge = ((((hi & k7f) + (k7f - k04)) | hi) & k80) >> 7;
+    hi = (hi & ~(ge * 255)) | (ge * 4);
+    if (cnt < 8) lo = (lo & ~(~0ull << (8 * cnt))) | (k05 << (8 * cnt));
+    if (cnt <= 8) hi = k05;
+    else if (cnt < 16) hi = (hi & ~(~0ull << (8 * (cnt - 8)))) | (k05 << (8 * (cnt - 8)));
+    // the target: bits 2m + 1 : 2m of w = base m.  The pac holds base f of a byte at bits 7 - 2 (f & 3)
+    // and up, so the eight bytes read as one big-endian number hold base f0 + k at bits 63 - 2 (f0 + k)
+    const uint64_t T = __builtin_bswap64(tw);
+    const int f0 = (int)(fa - (b0 << 2));  // 0 .. 31: the first base among the 32 loaded
+    uint32_t w;
+    if ((s.d > 0) != rev) {  // f rises along the pass
+      w = __builtin_bitreverse32((uint32_t)((T << (2 * f0)) >> 32));
+      w = ((w & 0x55555555u) << 1) | ((w >> 1) & 0x55555555u);
+    } else {
+      w = (uint32_t)(T >> (62 - 2 * f0));
+    }
+    if (rev) w = ~w;
+    const uint32_t qw[4] = {(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};
+    int c = 0, key = 31;  // key = 32 c + 31 - am: the largest c, and of equal ones the first
 #pragma unroll
-    for (int m = 0; m < 16; ++m)
-      if (p.base + m <= p.last) {
-        const int k = s.p0 + s.d * (p.base + m) - p.ws;  // 0 .. 15
-        const int qv = (int)(p.qw[k >> 3] >> ((k & 7) * 8)) & 255;
-        const int64_t fm = p.fa + (p.rev ? -s.d : s.d) * m;
-        const int byte = (int)(p.tw >> (((fm >> 2) - p.b0) * 8)) & 255;
-        const int bse = (byte >> ((~fm & 3) << 1)) & 3;
-        sc.step(p.base + m, mat[(p.rev ? 3 - bse : bse) * 5 + min(qv, 4)], max_mat);
-      }
+    for (int m = 0; m < 16; ++m) {
+      const uint32_t qv = (qw[m >> 2] >> ((m & 3) * 8)) & 255u, tv = (w >> (2 * m)) & 3u;
+      c += mat8[(tv << 3) | qv];
+      key = max(key, c * 32 + 30 - m);
+    }
+    g.n = cnt;
+    g.c = c;
+    g.P = cnt * max_mat - c;
+    g.M = key >> 5;
+    g.am = 31 - (key & 31);
   } else {
-    for (int j = p.base; j <= p.last; ++j)
-      sc.step(j, mat[pac_base2(ref.pac, ref.l_pac, s.x0 + (int64_t)s.d * j) * 5 + min((int)s.rd[s.p0 + s.d * j], 4)],
-              max_mat);
+    for (int j = base; j <= last; ++j)
+      g = ungseg_combine(g, ungseg_base(mat[pac_base2(ref.pac, ref.l_pac, s.x0 + (int64_t)s.d * j) * 5 +
+                                            min((int)s.rd[s.p0 + s.d * j], 4)], max_mat));
   }
+  return g;
 }
+
+constexpr int kUngTasks = 128;      // tasks of one block pass: a thread per side
+constexpr int kUngPassCap = 256 * 9;  // later passes listed per block pass (a side of 160 bases has nine); a side
+                                      // whose passes do not fit runs them itself
+struct UngSeg16 {  // a pass's summary in LDS (sixteen scores of an int8 each)
+  int16_t c, P, M, am;
+};
 
 __global__ void __launch_bounds__(256) spec_ungapped_kernel(DevOpt o, DevRef ref, DevBatch b, SpecArgs a, int round,
                                                             int bin0, int keep_short) {
   sel_prio();
-  __shared__ int8_t mat[25];  // the scores by (target, query) base: a lookup per base, kept out of global memory
-  if (threadIdx.x < 25) mat[threadIdx.x] = o.mat[threadIdx.x];
+  __shared__ int8_t mat[25], mat8[32];  // the scores by (target, query) base: a lookup per base, kept out of global memory
+  __shared__ UngSide sd[256];
+  __shared__ uint32_t plist[kUngPassCap];  // side's thread << 8 | pass
+  __shared__ UngSeg16 seg[kUngPassCap];
+  __shared__ int wsum[4], listed;
+  const int tid = (int)threadIdx.x;
+  if (tid < 25) mat[tid] = o.mat[tid];
+  if (tid < 32) mat8[tid] = (tid & 7) < 5 ? o.mat[(tid >> 3) * 5 + (tid & 7)] : 0;
+  if (tid == 0) listed = 0;
   __syncthreads();
   const int bin = bin0 + (int)blockIdx.y;
   const int list = round * kSpecBins + bin;
@@ -101,51 +155,117 @@ __global__ void __launch_bounds__(256) spec_ungapped_kernel(DevOpt o, DevRef ref
   const int2* tl = a.tasks + off;
   const int oe_min = ungapped_oe_min(o.o_del, o.e_del, o.o_ins, o.e_ins);
   const int keep = bin == 0 ? keep_short : 0;
-  const int chunk = (n + (int)gridDim.x - 1) / (int)gridDim.x;
-  const int i0 = (int)blockIdx.x * chunk, i1 = min(n, i0 + chunk);
-  for (int k = 2 * i0 + (int)threadIdx.x; k < 2 * i1; k += 256) {
-    const int i = k >> 1, right = k & 1;
-    const FatTask f = fat_task(b, a, tl[i]);
-    const int qb = (int)(f.qls & 1023u), ln = (int)((f.qls >> 10) & 1023u), lq = (int)(f.qls >> 20);
-    const int64_t xr = f.rbeg + ln;
-    const int qlen = right ? lq - qb - ln : qb;
-    const int tlen = right ? (int)(f.rbeg + f.dhi - xr) : f.dlo;
-    UngRec::Side rec{0, {0, 0, 0}};
-    // a right side starts from the left score, which is at least the seed's (ln * a)
-    if (qlen > keep && ungapped_band_ok(o.w) &&
-        ungapped_call_ok(qlen, tlen, ln * o.a, o.w, o.zdrop, o.max_mat, oe_min)) {
-      UngSide sd;
-      sd.rd = b.seq + f.qoff;
-      sd.p0 = right ? qb + ln : qb - 1;
-      sd.d = right ? 1 : -1;
-      sd.x0 = right ? xr : f.rbeg - 1;
-      sd.qlen = qlen;
-      sd.lq = lq;
-      UngappedScan sc;
-      for (int base = 0; base < qlen && !sc.dead(oe_min); base += 16)
-        ung_eat(sd, ref, ung_load(sd, ref, base), mat, o.max_mat, sc);
-      if (!sc.dead(oe_min)) rec = UngRec::Side{1, sc.side()};
+  for (int t0 = (int)blockIdx.x * kUngTasks; t0 < n; t0 += (int)gridDim.x * kUngTasks) {
+    const int i = t0 + (tid >> 1), right = tid & 1;
+    UngSide s{};
+    UngSeg g;
+    bool ok = false;
+    int extra = 0;  // the passes after the first, if that leaves the side alive
+    if (i < n) {
+      const FatTask f = fat_task(b, a, tl[i]);
+      if (right && a.ungt) a.ungt[off + i] = UngTask{f.rbeg, f.pos, f.qls};
+      const int qb = (int)(f.qls & 1023u), ln = (int)((f.qls >> 10) & 1023u), lq = (int)(f.qls >> 20);
+      const int64_t xr = f.rbeg + ln;
+      const int qlen = right ? lq - qb - ln : qb;
+      const int tlen = right ? (int)(f.rbeg + f.dhi - xr) : f.dlo;
+      // a right side starts from the left score, which is at least the seed's (ln * a)
+      ok = qlen > keep && ungapped_band_ok(o.w) &&
+           ungapped_call_ok(qlen, tlen, ln * o.a, o.w, o.zdrop, o.max_mat, oe_min);
+      if (ok) {
+        s.rd = b.seq + f.qoff;
+        s.p0 = right ? qb + ln : qb - 1;
+        s.d = right ? 1 : -1;
+        s.x0 = right ? xr : f.rbeg - 1;
+        s.qlen = qlen;
+        s.lq = lq;
+        g = ung_pass(s, ref, 0, mat, mat8, o.max_mat);
+        if (!g.dead(oe_min)) extra = (qlen - 1) >> 4;
+      }
     }
-    a.ung[off + i].side[right] = rec;
+    // the block's exclusive prefix sum of `extra`: the side's place in the pass list
+    int inc = extra;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int y = __shfl_up(inc, d, 64);
+      if ((tid & 63) >= d) inc += y;
+    }
+    if ((tid & 63) == 63) wsum[tid >> 6] = inc;
+    __syncthreads();
+    int pos = inc - extra;
+    for (int w = 0; w < (tid >> 6); ++w) pos += wsum[w];
+    const bool fits = pos + extra <= kUngPassCap;  // (the sides that fit are a prefix of those with later passes)
+    if (extra > 0 && fits) {
+      sd[tid] = s;
+      for (int k = 1; k <= extra; ++k) plist[pos + k - 1] = (uint32_t)tid << 8 | (uint32_t)k;  // k <= 63
+      atomicMax(&listed, pos + extra);
+    }
+    __syncthreads();
+    const int np = listed;
+    for (int p = tid; p < np; p += 256) {
+      const uint32_t e = plist[p];
+      const UngSeg x = ung_pass(sd[e >> 8], ref, (int)(e & 255u) * 16, mat, mat8, o.max_mat);
+      seg[p] = UngSeg16{(int16_t)x.c, (int16_t)x.P, (int16_t)x.M, (int16_t)x.am};
+    }
+    __syncthreads();
+    UngRec::Side rec{0, {0, 0, 0}};
+    if (ok) {
+      for (int k = 1; k <= extra && !g.dead(oe_min); ++k) {
+        UngSeg x;
+        if (fits) {
+          const UngSeg16 y = seg[pos + k - 1];
+          x.n = min(16, s.qlen - 16 * k);
+          x.c = y.c;
+          x.P = y.P;
+          x.M = y.M;
+          x.am = y.am;
+        } else {
+          x = ung_pass(s, ref, 16 * k, mat, mat8, o.max_mat);
+        }
+        g = ungseg_combine(g, x);
+      }
+      if (!g.dead(oe_min)) rec = UngRec::Side{1, g.side()};
+    }
+    if (i < n) a.ung[off + i].side[right] = rec;
+    if (tid == 0) listed = 0;
+    __syncthreads();
   }
 }
 
 // the stored decision of the task at `slot` of its list: which of its sides
 // (query lengths qb, qr) are settled here (cl, cr) and which enter a list.  A
-// certified right side behind a left side that needs the DP stays on the
-// right list: its h0 is the left call's score.
+// certified right side behind a left side that needs the DP has the left
+// call's score for its h0, which the certificate does not depend on: it is a
+// late right side, on no list and settled by
+// spec_settle_right_kernel after the left launch; without SpecArgs::ungt it
+// stays on the right list.
 struct SideLists {
-  bool cl, cr, in_l, in_r;
+  bool cl, cr, in_l, in_r, late;
 };
 __device__ __forceinline__ SideLists side_lists(const SpecArgs& a, size_t slot, int qb, int qr) {
-  SideLists s{false, false, qb > 0, qr > 0};
+  SideLists s{false, false, qb > 0, qr > 0, false};
   if (a.ung) {
     s.cl = qb > 0 && a.ung[slot].side[0].ok;
     s.in_l = qb > 0 && !s.cl;
-    s.cr = qr > 0 && a.ung[slot].side[1].ok && !s.in_l;
-    s.in_r = qr > 0 && !s.cr;
+    const bool okr = qr > 0 && a.ung[slot].side[1].ok;
+    s.cr = okr && !s.in_l;
+    s.late = okr && s.in_l && a.ungt;
+    s.in_r = qr > 0 && !s.cr && !s.late;
   }
   return s;
+}
+
+// a certified right side's result on top of the slot `e` that the left side
+// left (score, truesc) or that a task without a left side starts from, as
+// side_advance<G, true> with tt = 0 and x = ungapped_result: bwamem.c:761-792
+__device__ __forceinline__ void settle_right(const DevOpt& o, SeedExt& e, int64_t rbeg, int qb, int ln, int lq,
+                                             const UngappedSide& u) {
+  const int h0 = e.score;  // sc0 (bwamem.c:761)
+  const UngappedOut x = ungapped_result(h0, lq - qb - ln, u);
+  const bool local = x.gscore <= 0 || x.gscore <= x.score - o.pen_clip3;
+  e.qe = local ? qb + ln + x.qle : lq;
+  e.re = rbeg + ln + (local ? x.tle : x.gtle);
+  e.score = x.score;
+  e.truesc += (local ? x.score : x.gscore) - h0;
 }
 
 // The SeedExt of a task whose left side is absent or certified, as the side
@@ -173,13 +293,7 @@ __device__ __forceinline__ SeedExt settle_sides(const DevOpt& o, const FatTask& 
   e.re = f.rbeg + ln;
   e.qe = lq;
   if (right) {
-    const int h0 = e.score;  // sc0 (bwamem.c:761)
-    const UngappedOut x = ungapped_result(h0, qr, u.side[1].s);
-    const bool local = x.gscore <= 0 || x.gscore <= x.score - o.pen_clip3;
-    e.qe = local ? qb + ln + x.qle : lq;
-    e.re = f.rbeg + ln + (local ? x.tle : x.gtle);
-    e.score = x.score;
-    e.truesc += (local ? x.score : x.gscore) - h0;
+    settle_right(o, e, f.rbeg, qb, ln, lq, u.side[1].s);
     ++calls;
   } else if (qr > 0) {
     e.re = 0;
@@ -322,6 +436,51 @@ __global__ void __launch_bounds__(256) spec_sort2_scatter(DevOpt o, DevBatch b, 
   }
   if (threadIdx.x < 2 && ung[threadIdx.x])
     atomicAdd(&a.ctr[(threadIdx.x ? SPC_UNG_Q : SPC_UNG_N) + round], ung[threadIdx.x]);
+}
+
+// The late right sides of a round's phased lists, after the
+// lists' left launches: a thread per task of the list re-derives the class from
+// the stored record, as side_lists does.  The seed's slot holds what its left
+// side left (side_advance<G, false>'s partial slot), and the right call's
+// result follows from the stored certificate with h0 = that score, as
+// side_start / side_advance<G, true> would leave it after one call without a
+// band retry (max_off = 0) that ran no row.  (A compact list of the class,
+// written by the scatter, made that kernel longer than this pass over the
+// records takes: DESIGN.md §26.)
+__global__ void __launch_bounds__(256) spec_settle_right_kernel(DevOpt o, DevBatch b, SpecArgs a, int round, int bin0) {
+  sel_prio();
+  __shared__ int tot[2];              // sides, their query lengths
+  __shared__ unsigned long long cel;  // the finished tasks' cells
+  if (threadIdx.x < 2) tot[threadIdx.x] = 0;
+  if (threadIdx.x == 0) cel = 0;
+  __syncthreads();
+  const int list = round * kSpecBins + bin0 + (int)blockIdx.y;
+  const int n = __hip_atomic_load(&a.ctr[SPC_CNT + list], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const size_t off = spec_list_off(list, b.n_chains, b.n_seeds);
+  int sides = 0, bases = 0;
+  unsigned long long cells = 0;
+  for (int i = (int)(blockIdx.x * 256 + threadIdx.x); i < n; i += (int)gridDim.x * 256) {
+    const UngTask t = a.ungt[off + i];
+    const int qb = (int)(t.qls & 1023u), ln = (int)((t.qls >> 10) & 1023u), lq = (int)(t.qls >> 20);
+    if (!side_lists(a, off + i, qb, lq - qb - ln).late) continue;
+    SeedExt e = a.ext[t.pos];
+    settle_right(o, e, t.rbeg, qb, ln, lq, a.ung[off + i].side[1].s);
+    e.w = max(e.w, o.w);
+    e.calls += 2;  // the right call, and + 1 on a final slot
+    a.ext[t.pos] = e;
+    ++sides;
+    bases += lq - qb - ln;
+    cells += (unsigned long long)e.cells;
+  }
+  if (sides) {
+    atomicAdd(&tot[0], sides);
+    atomicAdd(&tot[1], bases);
+    atomicAdd(&cel, cells);
+  }
+  __syncthreads();
+  if (threadIdx.x < 2 && tot[threadIdx.x])
+    atomicAdd(&a.ctr[(threadIdx.x ? SPC_UNGR_Q : SPC_UNGR_N) + round], tot[threadIdx.x]);
+  if (threadIdx.x == 0 && cel) atomicAdd(reinterpret_cast<unsigned long long*>(a.ctr + SPC_SPEC64), cel);
 }
 
 // One side of a task in flight (LDS, per sub-slot, between its calls).
@@ -689,7 +848,7 @@ __global__ void __launch_bounds__(kBlock) spec_side4_kernel(DevOpt o, DevRef ref
 
 void launch_side_sort(const ExtRound& r, int bin0, int nbins, int short_q, int short_fill) {
   if (r.a.ung)
-    hipLaunchKernelGGL(spec_ungapped_kernel, dim3(1024, nbins), dim3(256), 0, r.st, r.o, r.ref, r.b, r.a, r.round, bin0,
+    hipLaunchKernelGGL(spec_ungapped_kernel, dim3(512, nbins), dim3(256), 0, r.st, r.o, r.ref, r.b, r.a, r.round, bin0,
                        short_fill == 0 ? short_q : 0);
   hipLaunchKernelGGL(spec_sort2_count, dim3(256, nbins), dim3(256), 0, r.st, r.b, r.a, r.round, bin0);
   hipLaunchKernelGGL(spec_sort2_scan, dim3(2 * nbins), dim3(256), 0, r.st, r.a, r.round, bin0, nbins, short_q);
@@ -707,6 +866,12 @@ static void launch_side_pair(const ExtRound& r, int list, const ExtPlan& p, int 
   if (!(G == 16 && K8)) short_fill = 0;
   hipLaunchKernelGGL((spec_side4_kernel<G, PMAX, K8, false>), dim3(gr), dim3(kBlock), lds, r.st, r.o, r.ref, r.b, r.a,
                      list, r.tb_bytes, (int)p.wave_lds, p.short_q, p.tb_short, short_fill);
+  // the late right sides go on from the left launch's slots.  One launch per list, after that list's own left
+  // launch, not one per round with grid.y = bins: ext_plan phases only the first bin today, and with two
+  // phased bins a single launch would have to wait for the second list's left launch
+  if (r.a.ungt)
+    hipLaunchKernelGGL(spec_settle_right_kernel, dim3(256, 1), dim3(256), 0, r.st, r.o, r.b, r.a, r.round,
+                       list % kSpecBins);
   hipLaunchKernelGGL((spec_side4_kernel<G, PMAX, K8, true>), dim3(gr), dim3(kBlock), lds, r.st, r.o, r.ref, r.b, r.a,
                      list, r.tb_bytes, (int)p.wave_lds, p.short_q, p.tb_short, short_fill);
 }

@@ -80,6 +80,41 @@ BWAGPU_UNG_HD inline bool ungapped_scan(int qlen, int max_mat, int oe_min, Score
   return true;
 }
 
+// The same diagonal in pieces.  A segment is a run of n
+// consecutive bases: c their score sum, P their deficit, M = max(0, the
+// largest prefix sum inside the segment) and am the first index inside it that
+// reaches M, plus 1 (0 if M = 0).  combine(a, b) is the segment a followed by
+// b; it is associative and the empty segment is its identity, so a side's
+// bases may be summarised sixteen at a time by different lanes and folded in
+// order afterwards.  b's prefix sums start from a.c; its maximum replaces a's
+// only where it is strictly larger, so the first index wins a tie as it does
+// in UngappedScan::step.  A fold over the side's bases one at a time is that
+// scan.  P adds and never falls: a dead prefix makes the whole side dead.
+struct UngSeg {
+  int32_t n = 0, c = 0, P = 0, M = 0, am = 0;
+  BWAGPU_UNG_HD bool dead(int oe_min) const { return P >= oe_min; }
+  BWAGPU_UNG_HD UngappedSide side() const { return UngappedSide{M, am, c}; }
+};
+BWAGPU_UNG_HD inline UngSeg ungseg_base(int s, int max_mat) {
+  UngSeg g;
+  g.n = 1;
+  g.c = s;
+  g.P = max_mat - s;
+  g.M = s > 0 ? s : 0;
+  g.am = s > 0 ? 1 : 0;
+  return g;
+}
+BWAGPU_UNG_HD inline UngSeg ungseg_combine(const UngSeg& a, const UngSeg& b) {
+  UngSeg g;
+  g.n = a.n + b.n;
+  g.c = a.c + b.c;
+  g.P = a.P + b.P;
+  const bool later = a.c + b.M > a.M;
+  g.M = later ? a.c + b.M : a.M;
+  g.am = later ? a.n + b.am : a.am;
+  return g;
+}
+
 BWAGPU_UNG_HD inline UngappedOut ungapped_result(int h0, int qlen, const UngappedSide& u) {
   UngappedOut x;
   x.score = h0 + u.M;

@@ -375,6 +375,21 @@ class Engine:
         on; acts only while the row bound is on); -> the previous setting"""
         return self.lib.bwagpu_ctx_ungapped(self.ctx, int(on))
 
+    def ungapped_right(self, on: int = -1) -> int:
+        """this context's late settling of certified right sides behind a left
+        side that needs the DP (bwagpu_ctx_ungapped_right, default on; acts
+        only while the certificate does); -> the previous setting"""
+        return self.lib.bwagpu_ctx_ungapped_right(self.ctx, int(on))
+
+    def ungapped_right_counters(self, stream=None):
+        """bwagpu_debug_spec_ungapped_right for the last device-entry batch on
+        `stream` (a raw stream handle; None: the default stream) -> int64
+        [3 rounds][settled after the left launch, their bases]"""
+        out = np.zeros(6, np.int64)
+        self._check(self.lib.bwagpu_debug_spec_ungapped_right(self.ctx, C.c_void_p(stream), _ptr(out)),
+                    "debug_spec_ungapped_right")
+        return out.reshape(3, 2)
+
     def emu_finish(self, on: int = -1) -> int:
         """this context's finishing of decided light reads in the emulate
         selection pass (bwagpu_ctx_emu_finish, default on); -> the previous setting"""

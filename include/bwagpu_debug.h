@@ -140,6 +140,18 @@ int bwagpu_ctx_ungapped(bwagpu_ctx_t *ctx, int on);
    sum of their query lengths, and the left and the right sides that stayed on
    the phased lists */
 int bwagpu_debug_spec_ungapped(bwagpu_ctx_t *ctx, void *stream, int64_t *out);
+/* late-settled right sides (default on; BWAGPU_UNGAPPED_RIGHT=0 starts
+   contexts with it off; acts only while the certificate does): a right side
+   that holds the certificate behind a left side that needs the DP enters no
+   list either; a small kernel after the list's left launch finishes its seed
+   from the slot that launch wrote.  0: such a side runs the DP
+   on the right list.  Regions and call counts are identical either way.
+   on < 0 only queries; returns the previous setting. */
+int bwagpu_ctx_ungapped_right(bwagpu_ctx_t *ctx, int on);
+/* diagnostics of the last device-entry batch on `stream` (waits for it), out:
+   6 entries, two per round A, B, C: the right sides settled after the left
+   launch and the sum of their query lengths; all 0 with either switch off */
+int bwagpu_debug_spec_ungapped_right(bwagpu_ctx_t *ctx, void *stream, int64_t *out);
 /* the emulate pass finishes decided light reads (default on;
    BWAGPU_EMU_FINISH=0 starts contexts with it off): a light read the emulate
    selection pass leaves no round-B task has every extension result the final
