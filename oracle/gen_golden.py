@@ -288,7 +288,47 @@ def gen_align2_range():
     a2_limit_counts()
 
 
+def gen_cigar_edges():
+    """the families of tests/cigar_cases.py (the CIGAR kernel's band, segment and run-length boundaries)
+    through the reference's own mem_reg2aln (ref_reg2aln_batch_calls: its records, with the score and band
+    of its last bwa_gen_cigar2 call) -> tests/golden/cigar_edges.npz, keys "<family>__<array>" for the
+    inputs and "<family>__<call>__<array>" for each call's records, CIGAR ops and MD bytes (back to back,
+    n_cigar / md_len of each job in its record)"""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import cigar_cases
+    import golden_io
+    refd = golden_io.load_ref()
+    R = oracle.Ref(refd["l_pac"], refd["ann_offset"], refd["ann_len"], refd["pac"])
+    out, n = {}, 0
+    for name, f in cigar_cases.families().items():
+        k = name + "__"
+        out[k + "opt_int"] = np.array([f.opt[x] for x in ("a", "b", "o_del", "e_del", "o_ins", "e_ins", "pen_clip5",
+                                                          "pen_clip3", "w", "zdrop")], np.int32)
+        out[k + "opt_mat"] = np.asarray(f.opt["mat"], np.int8)
+        out[k + "tasks"], out[k + "qpool"] = f.tasks, f.qpool
+        out[k + "caps"] = np.array(f.calls, np.int32).reshape(-1, 2)
+        for c, (max_ops, max_md) in enumerate(f.calls):
+            exp, cig, md, tries = oracle.ref_reg2aln_calls(f.opt, R, f.tasks, f.qpool, max_ops, max_md)
+            if c == 0:
+                out[k + "tries"] = tries
+            out[f"{k}{c}__exp"] = exp
+            out[f"{k}{c}__ops"] = np.concatenate([cig[j, :exp["n_cigar"][j]] for j in range(len(exp))] +
+                                                 [np.zeros(0, np.uint32)])
+            out[f"{k}{c}__md"] = np.concatenate([md[j, :exp["md_len"][j]] for j in range(len(exp))] +
+                                                [np.zeros(0, np.uint8)])
+            n += len(f.tasks)
+    path = os.path.join(GOLD, "cigar_edges.npz")
+    np.savez_compressed(path, **out)
+    print(f"[gen_golden] cigar_edges: {len(cigar_cases.families())} families, {n} job runs, "
+          f"{os.path.getsize(path)} bytes")
+
+
 def main():
+    if "--only-cigar-edges" in sys.argv:
+        if oracle.ref_lib() is None:
+            sys.exit("build the reference first: make -C oracle")
+        gen_cigar_edges()
+        return
     if "--only-align2-range" in sys.argv:
         if oracle.ref_lib() is None:
             sys.exit("build the reference first: make -C oracle")
@@ -336,6 +376,7 @@ def main():
     gen_align2(np.random.default_rng(2025))
     gen_range()
     gen_align2_range()
+    gen_cigar_edges()
 
 
 if __name__ == "__main__":

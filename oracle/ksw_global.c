@@ -41,52 +41,103 @@ static void ops_push(ops_t *c, int op, int len)
   c->a[c->n++] = (uint32_t)len << 4 | (uint32_t)op;
 }
 
+/* What one job reaches (oracle_reg2aln_batch_extremes): one row of
+   ORACLE_R2X_WORDS int64 per job, filled by the loops below when x != NULL.
+   The same loops serve the plain entry (x == NULL), so this is no second
+   restatement.  flip (a bit set of ORACLE_R2X_FLIP_*) turns one of the four tie
+   comparisons of the cell update around: only for showing that a set of jobs
+   can tell the two orders apart. */
+enum {
+  X_TRIES = 0, X_W2 = 1, X_W = 4, X_NCOL = 7, X_UNGAPPED = 10, X_RUN_M = 11, X_RUN_I = 12, X_RUN_D = 13,
+  X_FIRST = 14, X_LAST = 15, X_OOB = 16, X_UNWRITTEN = 17, X_MIN_M = 18, X_MAX_M = 19, X_MIN_E = 20,
+  X_MAX_E = 21, X_MIN_F = 22, X_MAX_F = 23, X_MIN_H = 24, X_MAX_H = 25, X_HASH = 26, X_NRAW = 27, X_DIAG_MIN = 28, X_DIAG_MAX = 29
+};
+
+static void x_range(int64_t *x, int lo, int64_t v)
+{
+  if (v < x[lo]) x[lo] = v;
+  if (v > x[lo + 1]) x[lo + 1] = v;
+}
+
+/* the raw (unsqueezed) CIGAR of the last try: longest run per op, both ends, a hash */
+static void x_raw(int64_t *x, const ops_t *ops)
+{
+  static const int slot[3] = {X_RUN_M, X_RUN_I, X_RUN_D};
+  uint64_t h = 1469598103934665603ull;
+  x[X_RUN_M] = x[X_RUN_I] = x[X_RUN_D] = 0;
+  for (int k = 0; k < ops->n; ++k) {
+    const int op = ops->a[k] & 0xf, len = ops->a[k] >> 4;
+    if (len > x[slot[op]]) x[slot[op]] = len;
+    h = (h ^ ops->a[k]) * 1099511628211ull;
+  }
+  x[X_FIRST] = ops->n ? (int64_t)(ops->a[0] & 0xf) : -1;
+  x[X_LAST] = ops->n ? (int64_t)(ops->a[ops->n - 1] & 0xf) : -1;
+  x[X_HASH] = (int64_t)(h >> 1);
+  x[X_NRAW] = ops->n;
+}
+
 /* banded global alignment of q[0,ql) against t[0,tl) with band w; returns
-   H at (tl-1, ql-1) as ksw_global2 does; the CIGAR (M=0, I=1, D=2) in *ops */
+   H at (tl-1, ql-1) as ksw_global2 does; the CIGAR (M=0, I=1, D=2) in *ops.
+   The cell values are held in 64 bits, so that a value that would leave the
+   reference's int shows in x instead of wrapping; inside int32 (every job the
+   tests compare) the results are the reference's. */
 static int global2(int ql, const uint8_t *q, int tl, const uint8_t *t, const int8_t *mat, int o_del,
-                   int e_del, int o_ins, int e_ins, int w, ops_t *ops)
+                   int e_del, int o_ins, int e_ins, int w, ops_t *ops, int64_t *x, int flip)
 {
   const int ncol = ql < 2 * w + 1 ? ql : 2 * w + 1;
-  int *H = (int *)malloc(sizeof(int) * (ql + 1)), *E = (int *)malloc(sizeof(int) * (ql + 1));
-  uint8_t *dir = (uint8_t *)malloc((size_t)ncol * (tl > 0 ? tl : 1));
+  int64_t *H = (int64_t *)malloc(sizeof(int64_t) * (ql + 1)), *E = (int64_t *)malloc(sizeof(int64_t) * (ql + 1));
+  const size_t zn = (size_t)ncol * (tl > 0 ? tl : 1);
+  uint8_t *dir = (uint8_t *)malloc(zn);
+  uint8_t *wrote = x ? (uint8_t *)calloc(zn, 1) : 0; /* which cells some row wrote */
   /* H[j] holds H(i-1, j-1) when row i starts (row -1: the insertion border) */
   H[0] = 0;
   E[0] = NEG_INF;
   int j = 1;
-  for (; j <= ql && j <= w; ++j) H[j] = -(o_ins + e_ins * j), E[j] = NEG_INF;
+  for (; j <= ql && j <= w; ++j) H[j] = -((int64_t)o_ins + (int64_t)e_ins * j), E[j] = NEG_INF;
   for (; j <= ql; ++j) H[j] = E[j] = NEG_INF;
   for (int i = 0; i < tl; ++i) {
     const int lo = i > w ? i - w : 0, hi = i + w + 1 < ql ? i + w + 1 : ql;
     const int8_t *srow = mat + t[i] * 5;
-    int f = NEG_INF;
-    int left = lo == 0 ? -(o_del + e_del * (i + 1)) : NEG_INF; /* H(i, lo-1) */
+    int64_t f = NEG_INF;
+    int64_t left = lo == 0 ? -((int64_t)o_del + (int64_t)e_del * (i + 1)) : NEG_INF; /* H(i, lo-1) */
     uint8_t *drow = dir + (size_t)i * ncol;
     for (j = lo; j < hi; ++j) {
-      int m = H[j] + srow[q[j]];
-      int e = E[j];
-      uint8_t d = m >= e ? 0 : 1;
-      int h = m >= e ? m : e;
-      if (!(h >= f)) d = 2, h = f;
+      const int64_t m = H[j] + srow[q[j]];
+      int64_t e = E[j];
+      const int from_m = flip & ORACLE_R2X_FLIP_ME ? m > e : m >= e;
+      uint8_t d = from_m ? 0 : 1;
+      int64_t h = from_m ? m : e;
+      if (!(flip & ORACLE_R2X_FLIP_HF ? h > f : h >= f)) d = 2, h = f;
       H[j] = left;
       left = h;
-      const int od = m - (o_del + e_del), oi = m - (o_ins + e_ins);
+      const int64_t od = m - ((int64_t)o_del + e_del), oi = m - ((int64_t)o_ins + e_ins);
+      if (x) x_range(x, X_MIN_M, m), x_range(x, X_MIN_H, h), x_range(x, X_MIN_E, e), x_range(x, X_MIN_F, f),
+             x_range(x, X_MIN_E, od), x_range(x, X_MIN_F, oi);
       e -= e_del;
-      if (e > od) d |= 4; else e = od;
+      if (x) x_range(x, X_MIN_E, e), x_range(x, X_MIN_F, f - e_ins);
+      if (flip & ORACLE_R2X_FLIP_E ? e >= od : e > od) d |= 4; else e = od;
       E[j] = e;
       f -= e_ins;
-      if (f > oi) d |= 32; else f = oi;
+      if (flip & ORACLE_R2X_FLIP_F ? f >= oi : f > oi) d |= 32; else f = oi;
       drow[j - lo] = d;
+      if (wrote) wrote[(size_t)i * ncol + (j - lo)] = 1;
     }
     H[hi] = left;
     E[hi] = NEG_INF;
   }
-  const int score = H[ql];
+  const int score = (int)H[ql];
   /* backtrack from the last cell of the last row */
   int i = tl - 1, k = (i + w + 1 < ql ? i + w + 1 : ql) - 1, st = 0;
   ops->n = 0;
+  if (x) x[X_DIAG_MIN] = INT64_MAX, x[X_DIAG_MAX] = INT64_MIN; /* of this call's walk */
   while (i >= 0 && k >= 0) {
-    const int lo = i > w ? i - w : 0;
-    st = dir[(size_t)i * ncol + (k - lo)] >> (st << 1) & 3;
+    const int lo = i > w ? i - w : 0, hi = i + w + 1 < ql ? i + w + 1 : ql;
+    /* a walk that leaves the row's [lo, hi) reads a neighbouring row's byte in the
+       reference, or past the matrix (undefined there); the index stays inside here */
+    int64_t zi = (int64_t)i * ncol + (k - lo);
+    zi = zi < 0 ? 0 : (zi >= (int64_t)zn ? (int64_t)zn - 1 : zi);
+    if (x) x[X_OOB] += k < lo || k >= hi, x[X_UNWRITTEN] += !wrote[zi], x_range(x, X_DIAG_MIN, k - i);
+    st = dir[zi] >> (st << 1) & 3;
     if (st == 0) ops_push(ops, 0, 1), --i, --k;
     else if (st == 1) ops_push(ops, 2, 1), --i;
     else ops_push(ops, 1, 1), --k;
@@ -101,6 +152,7 @@ static int global2(int ql, const uint8_t *q, int tl, const uint8_t *t, const int
   free(H);
   free(E);
   free(dir);
+  free(wrote);
   return score;
 }
 
@@ -128,7 +180,7 @@ static void s_putw(str_t *s, int v)
 /* bwa_gen_cigar2: returns 1 with a CIGAR, 0 when the reference returns none */
 static int gen_cigar2(const bwagpu_opt_t *o, const int8_t *mat, int w_, int64_t l_pac, const uint8_t *pac,
                       int ql, const uint8_t *query_in, int64_t rb, int64_t re, int *score, ops_t *ops, int *NM,
-                      str_t *md)
+                      str_t *md, int64_t *xs, int flip)
 {
   ops->n = 0;
   *NM = -1;
@@ -155,6 +207,7 @@ static int gen_cigar2(const bwagpu_opt_t *o, const int8_t *mat, int w_, int64_t 
     int s = 0;
     for (int x = 0; x < ql; ++x) s += mat[r[x] * 5 + q[x]];
     *score = s;
+    if (xs) xs[X_UNGAPPED] = 1, xs[X_DIAG_MIN] = xs[X_DIAG_MAX] = 0, x_raw(xs, ops);
   } else {
     const int half = (ql + 1) >> 1;
     int mi = (int)((double)(half * mat[0] - o->o_ins) / o->e_ins + 1.);
@@ -165,7 +218,12 @@ static int gen_cigar2(const bwagpu_opt_t *o, const int8_t *mat, int w_, int64_t 
     int w = (mg + dl + 1) >> 1;
     w = w < w_ ? w : w_;
     w = w > dl + 3 ? w : dl + 3;
-    *score = global2(ql, q, (int)rlen, r, mat, o->o_del, o->e_del, o->o_ins, o->e_ins, w, ops);
+    *score = global2(ql, q, (int)rlen, r, mat, o->o_del, o->e_del, o->o_ins, o->e_ins, w, ops, xs, flip);
+    if (xs) {
+      const int t = (int)xs[X_TRIES];
+      xs[X_W + t] = w, xs[X_NCOL + t] = ql < 2 * w + 1 ? ql : 2 * w + 1, xs[X_UNGAPPED] = 0;
+      x_raw(xs, ops);
+    }
   }
   /* NM and MD (deletions at either end of the CIGAR are not reported) */
   const char *b2c = rb < l_pac ? "ACGTN" : "TGCAN";
@@ -213,12 +271,19 @@ static int infer_bw(int l1, int l2, int score, int a, int q, int r)
   return w;
 }
 
-int oracle_reg2aln(const bwagpu_opt_t *o, const bwagpu_bns_t *bns, const uint8_t *pac, const uint8_t *read,
+static int reg2aln(const bwagpu_opt_t *o, const bwagpu_bns_t *bns, const uint8_t *pac, const uint8_t *read,
                    const bwagpu_reg2aln_task_t *t, int max_ops, int max_md, bwagpu_aln_t *out, uint32_t *cigar,
-                   char *md_out)
+                   char *md_out, int64_t *x, int flip)
 {
   int8_t mat[25];
   memset(out, 0, sizeof *out);
+  if (x) {
+    memset(x, 0, sizeof(int64_t) * ORACLE_R2X_WORDS);
+    for (int k = X_W2; k < X_UNGAPPED; ++k) x[k] = -1;
+    x[X_FIRST] = x[X_LAST] = -1;
+    x[X_MIN_M] = x[X_MIN_E] = x[X_MIN_F] = x[X_MIN_H] = INT64_MAX;
+    x[X_MAX_M] = x[X_MAX_E] = x[X_MAX_F] = x[X_MAX_H] = INT64_MIN;
+  }
   if (t->rb < 0 || t->re < 0) { /* unmapped record */
     out->rid = -1;
     out->pos = -1;
@@ -245,8 +310,9 @@ int oracle_reg2aln(const bwagpu_opt_t *o, const bwagpu_bns_t *bns, const uint8_t
   do {
     w2 = w2 < wmax ? w2 : wmax;
     wcall = w2;
-    ok = gen_cigar2(o, mat, w2, bns->l_pac, pac, lq, read + t->qb, t->rb, t->re, &score, &ops, &NM, &md);
+    ok = gen_cigar2(o, mat, w2, bns->l_pac, pac, lq, read + t->qb, t->rb, t->re, &score, &ops, &NM, &md, x, flip);
     if (!ok) break;
+    if (x) x[X_W2 + x[X_TRIES]++] = w2;
     if (score == last || w2 == wmax) break;
     last = score;
     w2 <<= 1;
@@ -311,6 +377,23 @@ int oracle_reg2aln(const bwagpu_opt_t *o, const bwagpu_bns_t *bns, const uint8_t
   out->pos = mid >= 0 ? pos - bns->ann_offset[mid] : pos;
   free(ops.a);
   free(md.s);
+  return 0;
+}
+
+int oracle_reg2aln(const bwagpu_opt_t *o, const bwagpu_bns_t *bns, const uint8_t *pac, const uint8_t *read,
+                   const bwagpu_reg2aln_task_t *t, int max_ops, int max_md, bwagpu_aln_t *out, uint32_t *cigar,
+                   char *md_out)
+{
+  return reg2aln(o, bns, pac, read, t, max_ops, max_md, out, cigar, md_out, 0, 0);
+}
+
+int oracle_reg2aln_batch_extremes(const bwagpu_opt_t *opt, const bwagpu_bns_t *bns, const uint8_t *pac, int32_t n,
+                                  const bwagpu_reg2aln_task_t *tasks, const uint8_t *qpool, int max_ops, int max_md,
+                                  bwagpu_aln_t *out, uint32_t *cigar, char *md, int64_t *ext, int flip)
+{
+  for (int32_t k = 0; k < n; ++k)
+    reg2aln(opt, bns, pac, qpool + tasks[k].qoff, &tasks[k], max_ops, max_md, &out[k],
+            cigar + (size_t)k * max_ops, md + (size_t)k * max_md, ext + (size_t)k * ORACLE_R2X_WORDS, flip);
   return 0;
 }
 

@@ -56,6 +56,9 @@ def oracle_lib():
     lib.oracle_reg2aln_batch.argtypes = [C.POINTER(abi.Opt), C.POINTER(abi.Bns), _VP, C.c_int32, _VP, _VP,
                                          C.c_int, C.c_int, _VP, _VP, _VP]
     lib.oracle_reg2aln_batch.restype = C.c_int
+    lib.oracle_reg2aln_batch_extremes.argtypes = [C.POINTER(abi.Opt), C.POINTER(abi.Bns), _VP, C.c_int32, _VP, _VP,
+                                                  C.c_int, C.c_int, _VP, _VP, _VP, _VP, C.c_int]
+    lib.oracle_reg2aln_batch_extremes.restype = C.c_int
     lib.oracle_collect_intv.argtypes = [_VP, _VP, _VP, C.c_float, C.c_int, _VP, _VP, C.c_int]
     lib.oracle_collect_intv.restype = C.c_int
     lib.oracle_bwt_sa.argtypes = [_VP, _VP, _VP, C.c_int, C.c_uint64]
@@ -86,6 +89,10 @@ def ref_lib():
         lib.ref_reg2aln_batch.argtypes = [C.POINTER(abi.Opt), C.POINTER(abi.Bns), _VP, C.c_int32, _VP, _VP,
                                           C.c_int, C.c_int, _VP, _VP, _VP]
         lib.ref_reg2aln_batch.restype = C.c_int
+    if hasattr(lib, "ref_reg2aln_batch_calls"):
+        lib.ref_reg2aln_batch_calls.argtypes = [C.POINTER(abi.Opt), C.POINTER(abi.Bns), _VP, C.c_int32, _VP, _VP,
+                                                C.c_int, C.c_int, _VP, _VP, _VP, _VP]
+        lib.ref_reg2aln_batch_calls.restype = C.c_int
     if hasattr(lib, "ref_align2_batch"):
         lib.ref_align2_batch.argtypes = [C.POINTER(abi.Opt), C.c_int32, _VP, _VP, _VP, _VP]
         lib.ref_align2_batch.restype = C.c_int
@@ -253,6 +260,51 @@ def reg2aln(which: str, opt: dict, ref: Ref, tasks, qpool, max_ops: int = 64, ma
     f(C.byref(o), C.byref(ref.bns), _ptr(ref.pac), n, _ptr(tasks), _ptr(qpool), max_ops, max_md, _ptr(out),
       _ptr(cig), _ptr(md))
     return out[:n], cig[:n], md[:n]
+
+
+# columns of reg2aln_extremes' table (oracle.h: oracle_reg2aln_batch_extremes)
+R2X = dict(tries=0, w2=1, w=4, ncol=7, ungapped=10, run_m=11, run_i=12, run_d=13, first=14, last=15, oob=16,
+           unwritten=17, min_m=18, max_m=19, min_e=20, max_e=21, min_f=22, max_f=23, min_h=24, max_h=25, hash=26,
+           n_raw=27, diag_min=28, diag_max=29)
+R2X_WORDS = 30
+FLIP_ME, FLIP_HF, FLIP_E, FLIP_F = 1, 2, 4, 8
+
+
+def reg2aln_extremes(opt: dict, ref: Ref, tasks, qpool, max_ops: int = 64, max_md: int = 512, flip: int = 0):
+    """oracle_reg2aln_batch with what each job reaches -> (records, cigar, md, int64[n, R2X_WORDS]); R2X names
+    the columns (w2, w and ncol: three slots each, one per bwa_gen_cigar2 call, -1 unused).  flip: FLIP_* bits,
+    a tie comparison of the cell update turned around (not the reference's results)"""
+    o = abi.opt_from_dict(opt)
+    tasks = np.ascontiguousarray(tasks, abi.REG2ALN_TASK_DTYPE)
+    qpool = np.ascontiguousarray(qpool, np.uint8)
+    n = len(tasks)
+    out = np.zeros(max(n, 1), abi.ALN_DTYPE)
+    cig = np.zeros((max(n, 1), max_ops), np.uint32)
+    md = np.zeros((max(n, 1), max_md), np.uint8)
+    ext = np.zeros((max(n, 1), R2X_WORDS), np.int64)
+    oracle_lib().oracle_reg2aln_batch_extremes(C.byref(o), C.byref(ref.bns), _ptr(ref.pac), n, _ptr(tasks),
+                                               _ptr(qpool), max_ops, max_md, _ptr(out), _ptr(cig), _ptr(md),
+                                               _ptr(ext), int(flip))
+    return out[:n], cig[:n], md[:n], ext[:n]
+
+
+def ref_reg2aln_calls(opt: dict, ref: Ref, tasks, qpool, max_ops: int = 64, max_md: int = 512):
+    """the compiled reference's mem_reg2aln per job, with the score and band of its last bwa_gen_cigar2 call
+    in the record -> (records, cigar, md, int32[n]: the number of bwa_gen_cigar2 calls)"""
+    lib = ref_lib()
+    if lib is None or not hasattr(lib, "ref_reg2aln_batch_calls"):
+        raise RuntimeError("oracle/_ref/libbwaref.so (with ref_reg2aln_batch_calls) not available")
+    o = abi.opt_from_dict(opt)
+    tasks = np.ascontiguousarray(tasks, abi.REG2ALN_TASK_DTYPE)
+    qpool = np.ascontiguousarray(qpool, np.uint8)
+    n = len(tasks)
+    out = np.zeros(max(n, 1), abi.ALN_DTYPE)
+    cig = np.zeros((max(n, 1), max_ops), np.uint32)
+    md = np.zeros((max(n, 1), max_md), np.uint8)
+    calls = np.zeros(max(n, 1), np.int32)
+    lib.ref_reg2aln_batch_calls(C.byref(o), C.byref(ref.bns), _ptr(ref.pac), n, _ptr(tasks), _ptr(qpool), max_ops,
+                                max_md, _ptr(out), _ptr(cig), _ptr(md), _ptr(calls))
+    return out[:n], cig[:n], md[:n], calls[:n]
 
 
 def collect_intv(bwt_hdr, bwt_words, opt_i32, split_factor, seq_off, seq, cap: int = 512):

@@ -166,9 +166,30 @@ int ref_align2_batch(const bwagpu_opt_t *o, int32_t n_tasks, const bwagpu_align2
    clips), MD, NM, strand, contig and position; ar->rid is set to the contig
    of the region's first base so that mem_reg2aln's assert(a.rid == ar->rid)
    holds for jobs inside one contig */
-int ref_reg2aln_batch(const bwagpu_opt_t *o, const bwagpu_bns_t *gb, const uint8_t *pac, int32_t n,
-                      const bwagpu_reg2aln_task_t *tasks, const uint8_t *qpool, int max_ops, int max_md,
-                      bwagpu_aln_t *out, uint32_t *cigar, char *md)
+/* The link of libbwaref.so wraps bwa_gen_cigar2 (Makefile), so that the calls
+   mem_reg2aln makes can be counted and the last one's band and score read: the
+   reference's mem_aln_t keeps neither.  The wrapper changes nothing. */
+static __thread int g_cig_calls, g_cig_w, g_cig_score;
+uint32_t *__real_bwa_gen_cigar2(const int8_t mat[25], int o_del, int e_del, int o_ins, int e_ins, int w_,
+                                int64_t l_pac, const uint8_t *pac, int l_query, uint8_t *query, int64_t rb,
+                                int64_t re, int *score, int *n_cigar, int *NM);
+uint32_t *__wrap_bwa_gen_cigar2(const int8_t mat[25], int o_del, int e_del, int o_ins, int e_ins, int w_,
+                                int64_t l_pac, const uint8_t *pac, int l_query, uint8_t *query, int64_t rb,
+                                int64_t re, int *score, int *n_cigar, int *NM)
+{
+  uint32_t *c = __real_bwa_gen_cigar2(mat, o_del, e_del, o_ins, e_ins, w_, l_pac, pac, l_query, query, rb, re,
+                                      score, n_cigar, NM);
+  ++g_cig_calls;
+  g_cig_w = w_;
+  g_cig_score = *score;
+  return c;
+}
+
+/* calls (may be NULL): per job the number of bwa_gen_cigar2 calls; with it the
+   records also carry the last call's score and band */
+static int reg2aln_batch(const bwagpu_opt_t *o, const bwagpu_bns_t *gb, const uint8_t *pac, int32_t n,
+                         const bwagpu_reg2aln_task_t *tasks, const uint8_t *qpool, int max_ops, int max_md,
+                         bwagpu_aln_t *out, uint32_t *cigar, char *md, int32_t *calls)
 {
   mem_opt_t opt;
   bntseq_t bns;
@@ -190,10 +211,15 @@ int ref_reg2aln_batch(const bwagpu_opt_t *o, const bwagpu_bns_t *gb, const uint8
     ar.rb = t->rb; ar.re = t->re; ar.qb = t->qb; ar.qe = t->qe;
     ar.truesc = ar.score = t->truesc; ar.w = t->w;
     ar.rid = t->rb >= 0 ? bns_pos2rid(&bns, bns_depos(&bns, t->rb < bns.l_pac ? t->rb : t->re - 1, &is_rev)) : -1;
+    g_cig_calls = 0;
     mem_aln_t a = mem_reg2aln(&opt, &bns, pac, t->l_seq, (const char *)(qpool + t->qoff), &ar);
     bwagpu_aln_t *r = &out[k];
     memset(r, 0, sizeof(*r));
     r->pos = a.pos; r->rid = a.rid; r->is_rev = a.is_rev; r->NM = a.NM;
+    if (calls) {
+      calls[k] = g_cig_calls;
+      if (g_cig_calls) r->score = g_cig_score, r->w = g_cig_w;
+    }
     if (a.rid < 0) {
       r->status = BWAGPU_ALN_UNMAPPED;
       continue;
@@ -202,6 +228,7 @@ int ref_reg2aln_batch(const bwagpu_opt_t *o, const bwagpu_bns_t *gb, const uint8
     const int ml = (int)strlen(m);
     if (a.n_cigar > max_ops || ml + 1 > max_md) {
       r->status = BWAGPU_ALN_OVERFLOW;
+      if (calls) r->pos = 0, r->rid = 0, r->is_rev = 0; /* bwagpu_aln_t of an overflow: score, w, NM and status alone */
     } else {
       r->n_cigar = a.n_cigar;
       r->md_len = ml;
@@ -212,6 +239,20 @@ int ref_reg2aln_batch(const bwagpu_opt_t *o, const bwagpu_bns_t *gb, const uint8
   }
   free(bns.anns);
   return 0;
+}
+
+int ref_reg2aln_batch(const bwagpu_opt_t *o, const bwagpu_bns_t *gb, const uint8_t *pac, int32_t n,
+                      const bwagpu_reg2aln_task_t *tasks, const uint8_t *qpool, int max_ops, int max_md,
+                      bwagpu_aln_t *out, uint32_t *cigar, char *md)
+{
+  return reg2aln_batch(o, gb, pac, n, tasks, qpool, max_ops, max_md, out, cigar, md, NULL);
+}
+
+int ref_reg2aln_batch_calls(const bwagpu_opt_t *o, const bwagpu_bns_t *gb, const uint8_t *pac, int32_t n,
+                            const bwagpu_reg2aln_task_t *tasks, const uint8_t *qpool, int max_ops, int max_md,
+                            bwagpu_aln_t *out, uint32_t *cigar, char *md, int32_t *calls)
+{
+  return reg2aln_batch(o, gb, pac, n, tasks, qpool, max_ops, max_md, out, cigar, md, calls);
 }
 
 /* ---- seeding on the host with the reference's own code (cpu baselines of

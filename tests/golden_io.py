@@ -136,6 +136,31 @@ def load_cigar_set(name):
     return opt_of(z), z["tasks"].astype(abi.REG2ALN_TASK_DTYPE), z["seq"], exp, ops, mds
 
 
+def load_cigar_edges():
+    """tests/golden/cigar_edges.npz (oracle/gen_golden.py --only-cigar-edges: the families of
+    tests/cigar_cases.py through the reference's mem_reg2aln) -> {family: dict(opt, tasks, qpool, caps
+    int32[c, 2] (max_ops, max_md per call), tries int32[n] (bwa_gen_cigar2 calls per job), calls: per call
+    (records with the last bwa_gen_cigar2 call's score and band, ops per job, MD bytes per job))}"""
+    z = _npz("cigar_edges")
+    out = {}
+    for key in z.files:
+        if not key.endswith("__tasks"):
+            continue
+        k = key[:-len("tasks")]
+        opt = dict(zip(OPT_KEYS, z[k + "opt_int"].tolist()))
+        opt["mat"] = z[k + "opt_mat"].astype(np.int8)
+        calls = []
+        for c in range(len(z[k + "caps"])):
+            exp = z[f"{k}{c}__exp"].astype(abi.ALN_DTYPE)
+            co, mo = offsets(exp["n_cigar"]), offsets(exp["md_len"])
+            ops = [z[f"{k}{c}__ops"][o:o + n] for o, n in zip(co, exp["n_cigar"])]
+            mds = [bytes(z[f"{k}{c}__md"][o:o + n]) for o, n in zip(mo, exp["md_len"])]
+            calls.append((exp, ops, mds))
+        out[k[:-2]] = dict(opt=opt, tasks=z[k + "tasks"].astype(abi.REG2ALN_TASK_DTYPE), qpool=z[k + "qpool"],
+                           caps=z[k + "caps"], tries=z[k + "tries"], calls=calls)
+    return out
+
+
 def aln_mismatch(tasks, got, cig, md, exp, ops, mds, fields=("pos", "rid", "is_rev", "n_cigar", "NM", "md_len",
                                                                 "score", "w", "status")) -> str | None:
     """bit-exact comparison of reg2aln outputs (records + CIGAR + MD) with expected ones"""
