@@ -184,6 +184,7 @@ int create_common(int device, const bwagpu_opt_t* opt, const bwagpu_bns_t* bns, 
   ctx->ungapped = ungapped_default();
   ctx->ungapped_right = ungapped_right_default();
   ctx->emu_finish = emu_finish_default();
+  ctx->fused_launches = fused_launches_default();
   *made = ctx;
   HIPC(hipSetDevice(device), "hipSetDevice");
   HIPC(hipMalloc(&ctx->d_ann_off, sizeof(int64_t) * bns->n_seqs), "hipMalloc(ann_offset)");
@@ -414,6 +415,7 @@ int enqueue_spec(bwagpu_ctx_t* ctx, Slot& s, const DevBatch& db, int lq_max, bwa
   ss.form = ctx->ext_form;
   ss.short_q = ctx->ext_short;
   ss.short_fill = ctx->ext_short_fill;
+  ss.fused = ctx->fused_launches;
   ss.pool = ctx->prof_ev.empty() ? nullptr : ctx->prof_ev.data();
   ss.pool_n = (int)ctx->prof_ev.size();
   ss.pool_used = &ctx->prof_used;
@@ -1001,6 +1003,13 @@ int bwagpu_ctx_emu_finish(bwagpu_ctx_t* ctx, int on) {
   if (!ctx) return BWAGPU_E_INVAL;
   const int prev = ctx->emu_finish;
   if (on >= 0) ctx->emu_finish = on ? 1 : 0;
+  return prev;
+}
+
+int bwagpu_ctx_fused_launches(bwagpu_ctx_t* ctx, int mask) {
+  if (!ctx) return BWAGPU_E_INVAL;
+  const int prev = ctx->fused_launches;
+  if (mask >= 0) ctx->fused_launches = mask & 7;
   return prev;
 }
 

@@ -171,6 +171,7 @@ struct bwagpu_ctx {
   int ungapped = 1;  // bwagpu_ctx_ungapped (BWAGPU_UNGAPPED or on when made); acts only while opt.row_bound is on
   int ungapped_right = 1;  // bwagpu_ctx_ungapped_right (BWAGPU_UNGAPPED_RIGHT or on when made); acts only while ungapped does
   int emu_finish = 1;  // bwagpu_ctx_emu_finish (BWAGPU_EMU_FINISH or on when made)
+  int fused_launches = 5;  // bwagpu_ctx_fused_launches (BWAGPU_FUSED_LAUNCHES or 5 when made)
   Slot slot[BWAGPU_NUM_SLOTS];
   // bwagpu_chain2aln_device: the caller's streams, one per slot's scratch (a
   // stream always reuses the same scratch, so its launches never race)

@@ -165,7 +165,10 @@ constexpr int kSortKeys = 1024;
 // (the phased extension sorts each list twice, by the left and by the right
 // side's query length: its second histograms follow at kSortWordsR)
 constexpr int kSortWordsR = kSpecRounds * 2 * kSortKeys;
-constexpr int kSortWords = 2 * kSortWordsR;
+// (the phased sort with the scan folded into the scatter keeps those histograms
+// read-only: its cursors are a second array of the same shape at kSortCursor)
+constexpr int kSortCursor = 2 * kSortWordsR;
+constexpr int kSortWords = 2 * kSortCursor;
 // task list `list` (= round * kSpecBins + bin) starts at this entry of SpecArgs::tasks
 __host__ __device__ inline size_t spec_list_off(int list, int n_chains, int n_seeds) {
   const int round = list / kSpecBins, bin = list % kSpecBins;
@@ -232,6 +235,7 @@ struct SpecArgs {
                               // processed, bit 1 it has a result, bit 2 pad_ != 0
   int32_t* qh;                // kQHWords: sharded queue heads of the extension task lists
   int32_t* sorth;             // kSortWords, zeroed per batch: per (round, bin < 2) key histograms / cursors
+                              // (fused sort: the cursors apart, from kSortCursor)
   int2* stasks;               // the C = 3 / 4 lists sorted by key (same offsets as tasks), for the pair kernel
   FatTask* ftask;             // the same lists as FatTask records (the packed kernels); the phased
                               // extension: the tasks with a left side, by that side's length
@@ -270,7 +274,18 @@ struct SpecStreams {
   // ... for a short run of at least short_fill percent of the grid's
   // sixteen-per-wave slots (bwagpu_ctx_ext_short_fill)
   int short_fill = 0;
+  // the context's fused launches (bwagpu_ctx_fused_launches), a
+  // mask of kFuse*: 0 = every step a launch of its own on the batch's chain
+  int fused = 0;
 };
+// SpecStreams::fused
+enum {
+  kFuseSort = 1,    // the side lists' sort in two launches: the certificate kernel counts, the scatter scans
+  kFuseSettle = 2,  // spec_settle_right_kernel on the side stream, beside the list's right launch
+  kFuseHeavy = 4,   // heavy reads without a pair matrix in spec_scan_kernel's launch (emulate and final pass)
+};
+// the mask new contexts start with (BWAGPU_FUSED_LAUNCHES, else 5: bits 1 and 4)
+int fused_launches_default();
 // the ungapped certificate new contexts start with (BWAGPU_UNGAPPED, else on)
 int ungapped_default();
 // ... and its late settling of right sides (BWAGPU_UNGAPPED_RIGHT, else on)

@@ -1083,15 +1083,19 @@ __device__ __forceinline__ void trace_read(int pass, int n_reads, int rd, uint64
   if (r < 8) tr[((size_t)pass * n_reads + rd) * 8 + d] = v;
 }
 
-template <int MODE, bool HEAVY>
-__global__ void __launch_bounds__(64) spec_select_kernel(DevOpt o, DevRef ref, DevBatch b, SpecArgs a, int tb_bytes) {
-  sel_prio();
-  static_assert(HEAVY, "one-wave heavy shape only");
+// One heavy read `rd` by the whole wave, seed by seed: the reads without a
+// pair matrix and the redo list.  lds: kSelHeavyLds bytes (+ the redo pass's
+// target rows): max_gap_len table | chain seeds (pad_ = skip flag | 2 *
+// pending) | their SeedExt records | region records | (redo) target rows.
+// fill_mg: the table is not there yet (a caller that runs one read after another
+// with nothing else in that LDS fills it once itself).  tl: the finished read's
+// work, wave-uniform.
+template <int MODE>
+__device__ __forceinline__ void select_heavy_read(const DevOpt& o, const DevRef& ref, const DevBatch& b,
+                                                  const SpecArgs& a, int rd, uint8_t* lds, int tb_bytes, bool fill_mg,
+                                                  Tally& tl) {
   constexpr bool WRITE = MODE != SEL_EMULATE;
-  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   const int r = (int)(threadIdx.x & 63);
-  // LDS: max_gap_len table | chain seeds (pad_ = skip flag | 2 * pending) |
-  // their SeedExt records | region records | (redo) target rows
   int32_t* const MG = reinterpret_cast<int32_t*>(lds);
   bwagpu_seed_t* const SC = reinterpret_cast<bwagpu_seed_t*>(lds + 4 * kMglN);
   SeedExt* const EC = reinterpret_cast<SeedExt*>(SC + kSelExtCache);
@@ -1099,7 +1103,185 @@ __global__ void __launch_bounds__(64) spec_select_kernel(DevOpt o, DevRef ref, D
   const int cap_reg = sel_heavy_cap(MODE, tb_bytes);
   uint8_t* const tbl = reinterpret_cast<uint8_t*>(R + cap_reg);
   uint8_t* const tbr = tbl + tb_bytes;
-  for (int x = r; x < kMglN; x += 64) MG[x] = max_gap_len(o, x);
+  if (fill_mg)
+    for (int x = r; x < kMglN; x += 64) MG[x] = max_gap_len(o, x);
+  const uint64_t t_start = g_trace ? __builtin_amdgcn_s_memrealtime() : 0;
+  const ReadDesc d = uniform_desc(a.rdesc[rd]);
+  if (d.lq > a.lq_bound) return;  // flagged by spec_reads_kernel
+  const uint8_t* const q = b.seq + d.qoff;
+  const int rep_lim = (int)floor(.1 * d.lq) + 1;  // s->len - p->seedlen0 > .1 * l_query, bwamem.c:685
+  bool redo = false;
+  Tally rt{0, 0, 0};
+  int nreg = 0, n_inline = 0;
+  for (int c = d.c0; c < d.c0 + d.nch && !redo; ++c) {
+    const int s0 = uni(b.chain_seed_off[c]), ns = uni(b.chain_seed_off[c + 1]) - s0;
+    if (ns == 0) continue;
+    ChainWin cw = a.win[c];
+    cw.lo = uni64(cw.lo);
+    cw.hi = uni64(cw.hi);
+    if (cw.hi < cw.lo) continue;  // flagged by spec_chain_kernel (the reference would assert)
+    const int rid = uni(b.chain_rid[c]);
+    const float frac = __int_as_float(uni(__float_as_int(b.chain_frac_rep[c])));
+    // the chain's seeds (processing order) and their extension results, staged
+    // in LDS (chains of more than kSelExtCache seeds: prog[] / ext[] / skipf[])
+    const bool big = ns > kSelExtCache;
+    for (int i = r; i < min(ns, kSelExtCache); i += 64) {
+      bwagpu_seed_t v = a.prog[s0 + i];
+      v.pad_ = v.pad_ != 0 ? 1 : 0;
+      SC[i] = v;
+      const uint32_t* src = reinterpret_cast<const uint32_t*>(a.ext + s0 + i);
+      uint32_t* dst = reinterpret_cast<uint32_t*>(EC + i);
+#pragma unroll
+      for (int w = 0; w < 12; ++w) dst[w] = __hip_atomic_load(src + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    if (big)
+      for (int i = r; i < ns; i += 64)
+        __hip_atomic_store(&a.skipf[s0 + i], a.prog[s0 + i].pad_ != 0 ? 1 : 0, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_WORKGROUP);
+    mem_fence_group();
+    auto seed_at = [&](int i) -> bwagpu_seed_t { return i < kSelExtCache ? SC[i] : a.prog[s0 + i]; };
+    auto flag_at = [&](int i) -> int {
+      return i < kSelExtCache ? SC[i].pad_
+                              : __hip_atomic_load(&a.skipf[s0 + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    };
+    auto set_flag = [&](int i, int f) {
+      if (r == 0) {
+        if (i < kSelExtCache) SC[i].pad_ |= f;
+        else __hip_atomic_store(&a.skipf[s0 + i], f | 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+      mem_fence_group();
+    };
+    for (int k = 0; k < ns; ++k) {
+      const bwagpu_seed_t s = uni_seed(seed_at(k));
+      // containment in a region so far (bwamem.c:678-697), one region per lane
+      bool hit = false;
+      for (int base = 0; base < nreg && !hit; base += 64) {
+        const int i = min(base + r, nreg - 1);
+        RegRec p;
+        if (i < cap_reg) {
+          p = R[i];
+        } else {
+          const int pp = __hip_atomic_load(&a.regpos[d.s0 + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          const SeedExt* pe = a.ext + pp;
+          p.rb = __hip_atomic_load(&pe->rb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          p.re = __hip_atomic_load(&pe->re, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          p.qb = __hip_atomic_load(&pe->qb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          p.qe = __hip_atomic_load(&pe->qe, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          p.w = __hip_atomic_load(&pe->w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          p.seedlen0 = a.prog[pp].len;
+        }
+        const bool inside = base + r < nreg &&
+                            !(s.rbeg < p.rb || s.rbeg + s.len > p.re || s.qbeg < p.qb || s.qbeg + s.len > p.qe) &&
+                            !(s.len - p.seedlen0 >= rep_lim);
+        if (__builtin_amdgcn_ballot_w64(inside) == 0) continue;
+        hit = __builtin_amdgcn_ballot_w64(inside && seed_near(MG, s, p)) != 0;
+      }
+      if (hit) {
+        // a long overlapping seed of this chain already visited (bwamem.c:698-707)
+        const int len95 = uni((int)ceil(s.len * .95));  // t->len < s->len * .95 <=> t->len < ceil(...)
+        bool ov = false;
+        for (int base = 0; base < k && !ov; base += 64) {
+          const int i = min(base + r, k - 1);
+          const bwagpu_seed_t t = seed_at(i);
+          const bool tsk = (flag_at(i) & 1) != 0;
+          const bool a1 = s.qbeg <= t.qbeg && s.qbeg + s.len - t.qbeg >= s.len >> 2 && (int64_t)(t.qbeg - s.qbeg) != t.rbeg - s.rbeg;
+          const bool b1 = t.qbeg <= s.qbeg && t.qbeg + t.len - s.qbeg >= s.len >> 2 && (int64_t)(s.qbeg - t.qbeg) != s.rbeg - t.rbeg;
+          ov = __builtin_amdgcn_ballot_w64(base + r < k && !tsk && t.len >= len95 && (a1 || b1)) != 0;
+        }
+        if (!ov) {  // skipped: srt[k] = 0 (bwamem.c:709)
+          set_flag(k, 1);
+          continue;
+        }
+      }
+      // ---- this seed is extended (bwamem.c:717-792)
+      const int pos = s0 + k;
+      const SeedExt* const pe = k < kSelExtCache ? EC + k : a.ext + pos;
+      SeedExt e;
+      e.calls = uni(__hip_atomic_load(&pe->calls, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+      if (e.calls == 0) {  // no result yet
+        if constexpr (MODE == SEL_REDO) {
+          e = extend_seed<16>(o, ref, s, d.lq, q, cw, tbl, tbr);
+          store_ext(a.ext + pos, e);
+          mem_fence_group();
+          if (r == 0) atomicAdd(&a.ctr[SPC_MISS], 1);
+          ++n_inline;
+        } else if constexpr (MODE == SEL_EMULATE) {
+          set_flag(k, 2);  // pending: collected per chain below
+          continue;        // its region stays unknown in this pass
+        } else {
+          const int list = 2 * kSpecBins + spec_bin(d.lq);
+          if (r == 0) {
+            const int p = atomicAdd(&a.ctr[SPC_CNT + list], 1);
+            a.tasks[spec_list_off(list, b.n_chains, b.n_seeds) + p] = make_int2(pos, c);
+            a.redo[atomicAdd(&a.ctr[SPC_REDO_N], 1)] = rd;
+          }
+          redo = true;  // the rest of this read waits for the redo pass
+          break;
+        }
+      } else {
+        e.rb = uni64(__hip_atomic_load(&pe->rb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+        e.re = uni64(__hip_atomic_load(&pe->re, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+        e.qb = uni(__hip_atomic_load(&pe->qb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+        e.qe = uni(__hip_atomic_load(&pe->qe, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+        e.score = uni(__hip_atomic_load(&pe->score, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+        e.truesc = uni(__hip_atomic_load(&pe->truesc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+        e.w = uni(__hip_atomic_load(&pe->w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+        e.cells = uni(__hip_atomic_load(&pe->cells, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+        e.rows = uni(__hip_atomic_load(&pe->rows, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+      }
+      if constexpr (WRITE) {
+        // seedcov over the chain's seeds (bwamem.c:784-788)
+        long long cov = 0;
+        for (int base = 0; base < ns; base += 64) {
+          const int i = base + r;
+          const bwagpu_seed_t t = seed_at(min(i, ns - 1));
+          const bool in = i < ns && t.qbeg >= e.qb && t.qbeg + t.len <= e.qe && t.rbeg >= e.rb && t.rbeg + t.len <= e.re;
+          cov += in ? t.len : 0;
+        }
+        cov = grp_sum64(cov, 64);
+        write_region(a.out + d.s0 + nreg, e, rid, (int)cov, s.len, frac);
+        rt.cells += e.cells;
+        rt.rows += e.rows;
+        rt.calls += e.calls - 1;
+      }
+      if (nreg < cap_reg) {
+        put_regrec(R + nreg, e, s.len);
+      } else {
+        if (r == 0) __hip_atomic_store(&a.regpos[d.s0 + nreg], pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        mem_fence_group();
+      }
+      ++nreg;
+    }
+    if constexpr (MODE == SEL_EMULATE) {  // this chain's round-B tasks
+      const int list = kSpecBins + spec_bin(d.lq);
+      for (int base = 0; base < ns; base += 64) {
+        const int i = base + r;
+        const bool pnd = i < ns && (flag_at(min(i, ns - 1)) & 2) != 0;
+        const int p = wave_append(&a.ctr[SPC_CNT + list], pnd);
+        if (p >= 0) a.tasks[spec_list_off(list, b.n_chains, b.n_seeds) + p] = make_int2(s0 + i, c);
+      }
+    }
+  }
+  // (the redo pass as pass 2, its inline extensions in the shape word's upper bits)
+  trace_read(MODE, b.n_reads, rd, t_start, d.ns, nreg, 2 | (MODE == SEL_REDO ? n_inline << 4 : 0));
+  if constexpr (WRITE) {
+    if (!redo) {
+      a.out_n[rd] = nreg;
+      tl.cells += rt.cells;
+      tl.rows += rt.rows;
+      tl.calls += rt.calls;
+    }
+  }
+}
+
+template <int MODE, bool HEAVY>
+__global__ void __launch_bounds__(64) spec_select_kernel(DevOpt o, DevRef ref, DevBatch b, SpecArgs a, int tb_bytes) {
+  sel_prio();
+  static_assert(HEAVY, "one-wave heavy shape only");
+  constexpr bool WRITE = MODE != SEL_EMULATE;
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+  const int r = (int)(threadIdx.x & 63);
+  for (int x = r; x < kMglN; x += 64) reinterpret_cast<int32_t*>(lds)[x] = max_gap_len(o, x);
   Tally tl{0, 0, 0};
   const int n_list = uni(__hip_atomic_load(&a.ctr[MODE == SEL_REDO ? SPC_REDO_N : SPC_HEAVY_N], __ATOMIC_RELAXED,
                                            __HIP_MEMORY_SCOPE_AGENT));
@@ -1110,174 +1292,7 @@ __global__ void __launch_bounds__(64) spec_select_kernel(DevOpt o, DevRef ref, D
     t = uni(__shfl(t, 0, 64));
     if (t >= n_list) break;
     if (MODE != SEL_REDO && uni(a.hinfo[t].y) >= 0) continue;  // the pair-matrix kernels' read
-    const int rd = uni(hlist[t]);
-    const uint64_t t_start = g_trace ? __builtin_amdgcn_s_memrealtime() : 0;
-    const ReadDesc d = uniform_desc(a.rdesc[rd]);
-    if (d.lq > a.lq_bound) continue;  // flagged by spec_reads_kernel
-    const uint8_t* const q = b.seq + d.qoff;
-    const int rep_lim = (int)floor(.1 * d.lq) + 1;  // s->len - p->seedlen0 > .1 * l_query, bwamem.c:685
-    bool redo = false;
-    Tally rt{0, 0, 0};
-    int nreg = 0, n_inline = 0;
-    for (int c = d.c0; c < d.c0 + d.nch && !redo; ++c) {
-      const int s0 = uni(b.chain_seed_off[c]), ns = uni(b.chain_seed_off[c + 1]) - s0;
-      if (ns == 0) continue;
-      ChainWin cw = a.win[c];
-      cw.lo = uni64(cw.lo);
-      cw.hi = uni64(cw.hi);
-      if (cw.hi < cw.lo) continue;  // flagged by spec_chain_kernel (the reference would assert)
-      const int rid = uni(b.chain_rid[c]);
-      const float frac = __int_as_float(uni(__float_as_int(b.chain_frac_rep[c])));
-      // the chain's seeds (processing order) and their extension results, staged
-      // in LDS (chains of more than kSelExtCache seeds: prog[] / ext[] / skipf[])
-      const bool big = ns > kSelExtCache;
-      for (int i = r; i < min(ns, kSelExtCache); i += 64) {
-        bwagpu_seed_t v = a.prog[s0 + i];
-        v.pad_ = v.pad_ != 0 ? 1 : 0;
-        SC[i] = v;
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(a.ext + s0 + i);
-        uint32_t* dst = reinterpret_cast<uint32_t*>(EC + i);
-#pragma unroll
-        for (int w = 0; w < 12; ++w) dst[w] = __hip_atomic_load(src + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      }
-      if (big)
-        for (int i = r; i < ns; i += 64)
-          __hip_atomic_store(&a.skipf[s0 + i], a.prog[s0 + i].pad_ != 0 ? 1 : 0, __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_WORKGROUP);
-      mem_fence_group();
-      auto seed_at = [&](int i) -> bwagpu_seed_t { return i < kSelExtCache ? SC[i] : a.prog[s0 + i]; };
-      auto flag_at = [&](int i) -> int {
-        return i < kSelExtCache ? SC[i].pad_
-                                : __hip_atomic_load(&a.skipf[s0 + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      };
-      auto set_flag = [&](int i, int f) {
-        if (r == 0) {
-          if (i < kSelExtCache) SC[i].pad_ |= f;
-          else __hip_atomic_store(&a.skipf[s0 + i], f | 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-        mem_fence_group();
-      };
-      for (int k = 0; k < ns; ++k) {
-        const bwagpu_seed_t s = uni_seed(seed_at(k));
-        // containment in a region so far (bwamem.c:678-697), one region per lane
-        bool hit = false;
-        for (int base = 0; base < nreg && !hit; base += 64) {
-          const int i = min(base + r, nreg - 1);
-          RegRec p;
-          if (i < cap_reg) {
-            p = R[i];
-          } else {
-            const int pp = __hip_atomic_load(&a.regpos[d.s0 + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            const SeedExt* pe = a.ext + pp;
-            p.rb = __hip_atomic_load(&pe->rb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            p.re = __hip_atomic_load(&pe->re, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            p.qb = __hip_atomic_load(&pe->qb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            p.qe = __hip_atomic_load(&pe->qe, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            p.w = __hip_atomic_load(&pe->w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            p.seedlen0 = a.prog[pp].len;
-          }
-          const bool inside = base + r < nreg &&
-                              !(s.rbeg < p.rb || s.rbeg + s.len > p.re || s.qbeg < p.qb || s.qbeg + s.len > p.qe) &&
-                              !(s.len - p.seedlen0 >= rep_lim);
-          if (__builtin_amdgcn_ballot_w64(inside) == 0) continue;
-          hit = __builtin_amdgcn_ballot_w64(inside && seed_near(MG, s, p)) != 0;
-        }
-        if (hit) {
-          // a long overlapping seed of this chain already visited (bwamem.c:698-707)
-          const int len95 = uni((int)ceil(s.len * .95));  // t->len < s->len * .95 <=> t->len < ceil(...)
-          bool ov = false;
-          for (int base = 0; base < k && !ov; base += 64) {
-            const int i = min(base + r, k - 1);
-            const bwagpu_seed_t t = seed_at(i);
-            const bool tsk = (flag_at(i) & 1) != 0;
-            const bool a1 = s.qbeg <= t.qbeg && s.qbeg + s.len - t.qbeg >= s.len >> 2 && (int64_t)(t.qbeg - s.qbeg) != t.rbeg - s.rbeg;
-            const bool b1 = t.qbeg <= s.qbeg && t.qbeg + t.len - s.qbeg >= s.len >> 2 && (int64_t)(s.qbeg - t.qbeg) != s.rbeg - t.rbeg;
-            ov = __builtin_amdgcn_ballot_w64(base + r < k && !tsk && t.len >= len95 && (a1 || b1)) != 0;
-          }
-          if (!ov) {  // skipped: srt[k] = 0 (bwamem.c:709)
-            set_flag(k, 1);
-            continue;
-          }
-        }
-        // ---- this seed is extended (bwamem.c:717-792)
-        const int pos = s0 + k;
-        const SeedExt* const pe = k < kSelExtCache ? EC + k : a.ext + pos;
-        SeedExt e;
-        e.calls = uni(__hip_atomic_load(&pe->calls, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-        if (e.calls == 0) {  // no result yet
-          if constexpr (MODE == SEL_REDO) {
-            e = extend_seed<16>(o, ref, s, d.lq, q, cw, tbl, tbr);
-            store_ext(a.ext + pos, e);
-            mem_fence_group();
-            if (r == 0) atomicAdd(&a.ctr[SPC_MISS], 1);
-            ++n_inline;
-          } else if constexpr (MODE == SEL_EMULATE) {
-            set_flag(k, 2);  // pending: collected per chain below
-            continue;        // its region stays unknown in this pass
-          } else {
-            const int list = 2 * kSpecBins + spec_bin(d.lq);
-            if (r == 0) {
-              const int p = atomicAdd(&a.ctr[SPC_CNT + list], 1);
-              a.tasks[spec_list_off(list, b.n_chains, b.n_seeds) + p] = make_int2(pos, c);
-              a.redo[atomicAdd(&a.ctr[SPC_REDO_N], 1)] = rd;
-            }
-            redo = true;  // the rest of this read waits for the redo pass
-            break;
-          }
-        } else {
-          e.rb = uni64(__hip_atomic_load(&pe->rb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-          e.re = uni64(__hip_atomic_load(&pe->re, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-          e.qb = uni(__hip_atomic_load(&pe->qb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-          e.qe = uni(__hip_atomic_load(&pe->qe, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-          e.score = uni(__hip_atomic_load(&pe->score, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-          e.truesc = uni(__hip_atomic_load(&pe->truesc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-          e.w = uni(__hip_atomic_load(&pe->w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-          e.cells = uni(__hip_atomic_load(&pe->cells, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-          e.rows = uni(__hip_atomic_load(&pe->rows, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-        }
-        if constexpr (WRITE) {
-          // seedcov over the chain's seeds (bwamem.c:784-788)
-          long long cov = 0;
-          for (int base = 0; base < ns; base += 64) {
-            const int i = base + r;
-            const bwagpu_seed_t t = seed_at(min(i, ns - 1));
-            const bool in = i < ns && t.qbeg >= e.qb && t.qbeg + t.len <= e.qe && t.rbeg >= e.rb && t.rbeg + t.len <= e.re;
-            cov += in ? t.len : 0;
-          }
-          cov = grp_sum64(cov, 64);
-          write_region(a.out + d.s0 + nreg, e, rid, (int)cov, s.len, frac);
-          rt.cells += e.cells;
-          rt.rows += e.rows;
-          rt.calls += e.calls - 1;
-        }
-        if (nreg < cap_reg) {
-          put_regrec(R + nreg, e, s.len);
-        } else {
-          if (r == 0) __hip_atomic_store(&a.regpos[d.s0 + nreg], pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          mem_fence_group();
-        }
-        ++nreg;
-      }
-      if constexpr (MODE == SEL_EMULATE) {  // this chain's round-B tasks
-        const int list = kSpecBins + spec_bin(d.lq);
-        for (int base = 0; base < ns; base += 64) {
-          const int i = base + r;
-          const bool pnd = i < ns && (flag_at(min(i, ns - 1)) & 2) != 0;
-          const int p = wave_append(&a.ctr[SPC_CNT + list], pnd);
-          if (p >= 0) a.tasks[spec_list_off(list, b.n_chains, b.n_seeds) + p] = make_int2(s0 + i, c);
-        }
-      }
-    }
-    // (the redo pass as pass 2, its inline extensions in the shape word's upper bits)
-    trace_read(MODE, b.n_reads, rd, t_start, d.ns, nreg, 2 | (MODE == SEL_REDO ? n_inline << 4 : 0));
-    if constexpr (WRITE) {
-      if (!redo) {
-        a.out_n[rd] = nreg;
-        tl.cells += rt.cells;
-        tl.rows += rt.rows;
-        tl.calls += rt.calls;
-      }
-    }
+    select_heavy_read<MODE>(o, ref, b, a, uni(hlist[t]), lds, tb_bytes, false, tl);
   }
   if constexpr (WRITE) {
     if (r != 0) tl = Tally{0, 0, 0};
@@ -2077,7 +2092,16 @@ __device__ __forceinline__ void heavy_fill_missing(const DevOpt& o, const DevRef
   __builtin_amdgcn_wave_barrier();
 }
 
-template <int MODE>
+// FOLD (kFuseHeavy; a template argument, so that the kernel
+// without it is the one it was): the heavy reads without a matrix, the
+// per-seed kernel's, run here as well, each by the wave whose stride meets it
+// (select_heavy_read in this launch's LDS, in a loop ahead of the matrix
+// reads'), and spec_select_kernel<MODE> is not launched.  That loop's LDS use
+// ends with it.  (One wave's LDS operations are ordered by the hardware; the
+// fence after the loop only keeps the compiler from moving the matrix loop's
+// uint64 accesses across the differently typed ones of that layout.)
+static_assert(kScanLds >= kSelHeavyLds, "spec_scan_kernel's LDS holds select_heavy_read's layout");
+template <int MODE, bool FOLD>
 __global__ void __launch_bounds__(64) spec_scan_kernel(DevOpt o, DevRef ref, DevBatch b, SpecArgs a, int tb_bytes) {
   sel_prio();
   constexpr bool WRITE = MODE != SEL_EMULATE;
@@ -2088,10 +2112,25 @@ __global__ void __launch_bounds__(64) spec_scan_kernel(DevOpt o, DevRef ref, Dev
   const uint64_t lt_mask = r ? (~0ull >> (64 - r)) : 0ull;
   const int nh = uni(__hip_atomic_load(&a.ctr[SPC_HEAVY_N], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
   Tally tl{0, 0, 0};
+  if constexpr (MODE != SEL_REDO) {
+    if constexpr (FOLD) {  // a loop of its own, and first: these are the pass's longest reads, and nothing of it stays live below
+      Tally ts{0, 0, 0};
+      bool mg = true;  // the table survives from one such read to the next
+      for (int t = (int)blockIdx.x; t < nh; t += (int)gridDim.x) {
+        const int4 hi = a.hinfo[t];
+        if (uni(hi.y) >= 0) continue;
+        select_heavy_read<MODE>(o, ref, b, a, uni(hi.x), reinterpret_cast<uint8_t*>(M), tb_bytes, mg, ts);
+        mg = false;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+      __builtin_amdgcn_wave_barrier();
+      if (r == 0) tl = ts;  // wave-uniform sums: once
+    }
+  }
   for (int t = (int)blockIdx.x; t < nh; t += (int)gridDim.x) {
     const int4 hi = a.hinfo[t];
     const int rd = uni(hi.x), woff = uni(hi.y), ns = uni(hi.w);
-    if (woff < 0) continue;  // no matrix: the per-seed heavy kernel's read
+    if (woff < 0) continue;  // no matrix: the per-seed heavy kernel's read, or (fold) the loop above's
     const uint64_t t_start = g_trace ? __builtin_amdgcn_s_memrealtime() : 0;
     const int nw = (ns + 63) >> 6;
     const ReadDesc d = uniform_desc(a.rdesc[rd]);
@@ -2382,6 +2421,7 @@ template <int MODE>
 static void launch_select(const DevOpt& o, const DevRef& ref, const DevBatch& b, const SpecArgs& a, int tb_bytes,
                           hipStream_t st, const SpecStreams& ss) {
   hipStream_t hs = st;
+  const bool fold = MODE != SEL_REDO && (ss.fused & kFuseHeavy);
   if (MODE != SEL_REDO && ss.side) {
     (void)hipEventRecord(ss.fork, st);
     (void)hipStreamWaitEvent(ss.side, ss.fork, 0);
@@ -2404,12 +2444,17 @@ static void launch_select(const DevOpt& o, const DevRef& ref, const DevBatch& b,
   if (MODE != SEL_REDO) {  // heavy reads with pair matrices: all pairs at once, then one scan per read
     const int nb = resident_blocks(spec_pairs_kernel<MODE>, 0);
     hipLaunchKernelGGL((spec_pairs_kernel<MODE>), dim3(nb), dim3(kBlock), 0, hs, o, b, a);
-    hipLaunchKernelGGL((spec_scan_kernel<MODE>), dim3(kScanGrid), dim3(64), (size_t)kScanLds + 2 * (size_t)tb_bytes, hs, o,
-                       ref, b, a, tb_bytes);
+    if (fold)
+      hipLaunchKernelGGL((spec_scan_kernel<MODE, true>), dim3(kScanGrid), dim3(64),
+                         (size_t)kScanLds + 2 * (size_t)tb_bytes, hs, o, ref, b, a, tb_bytes);
+    else
+      hipLaunchKernelGGL((spec_scan_kernel<MODE, false>), dim3(kScanGrid), dim3(64),
+                         (size_t)kScanLds + 2 * (size_t)tb_bytes, hs, o, ref, b, a, tb_bytes);
   }
-  // the rest (no matrix; the redo list): one wave per read, per seed
-  hipLaunchKernelGGL((spec_select_kernel<MODE, true>), dim3(MODE == SEL_REDO ? 256 : 1024), dim3(64),
-                     (size_t)kSelHeavyLds, hs, o, ref, b, a, tb_bytes);
+  // the rest (no matrix, unless the scan's launch took them; the redo list): one wave per read, per seed
+  if (!fold)
+    hipLaunchKernelGGL((spec_select_kernel<MODE, true>), dim3(MODE == SEL_REDO ? 256 : 1024), dim3(64),
+                       (size_t)kSelHeavyLds, hs, o, ref, b, a, tb_bytes);
   if (hs != st) {
     (void)hipEventRecord(ss.join, hs);
     (void)hipStreamWaitEvent(st, ss.join, 0);
@@ -2480,6 +2525,15 @@ int emu_finish_default() {
   }();
   return on;
 }
+// The fused launches (bwagpu_ctx_fused_launches).
+// BWAGPU_FUSED_LAUNCHES sets the mask contexts start with.
+int fused_launches_default() {
+  static const int m = [] {
+    const char* e = getenv("BWAGPU_FUSED_LAUNCHES");
+    return (e && e[0] ? atoi(e) : 5) & 7;  // bit 2 measured no gain: off
+  }();
+  return m;
+}
 int ext_short_fill_default() {
   static const int f = [] {
     const char* e = getenv("BWAGPU_EXT_SHORT_FILL");
@@ -2510,7 +2564,7 @@ static void launch_ext_round(const DevOpt& o, const DevRef& ref, const DevBatch&
   const int l = round * kSpecBins;
   const bool bin1 = lq_max > kSpecBinLen[0], bin2 = lq_max > kSpecBinLen[1];
   const ExtPlan plan = ext_plan(o, ss.form, tb_bytes, ss.short_q);
-  const ExtRound r{o, ref, b, a, round, tb_bytes, st};
+  const ExtRound r{o, ref, b, a, round, tb_bytes, st, ss};
   if (!bin1 || plan.bin[0].phased == plan.bin[1].phased) {
     launch_sort(plan.bin[0], r, 0, bin1 ? 2 : 1, plan.short_q, ss.short_fill);
   } else {

@@ -210,6 +210,7 @@ struct ExtRound {
   const SpecArgs& a;
   int round, tb_bytes;
   hipStream_t st;
+  const SpecStreams& ss;
 };
 // the grid of an extension kernel on its persistent queue (spec.hip)
 int ext2_grid(int nb, bool packed);

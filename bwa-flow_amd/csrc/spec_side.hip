@@ -1,5 +1,6 @@
 // spec_side.hip — the phased extension of the speculative mem_chain2aln
 // (spec.hip has the design): its side lists' sort and spec_side4_kernel.
+#include "side_sort.h"
 #include "spec_dev.h"
 
 namespace bwagpu {
@@ -15,9 +16,8 @@ namespace bwagpu {
 // ones had ended (25 % of its call-slot cells) and set its columns by its
 // longest query (10 %), tools_dev/occ_diag.py.  Lists: the tasks with a left
 // side (FatTask, key = left query length) and those with a right side; a
-// whole-read seed (neither side) is written by the scatter itself.
-__device__ __forceinline__ int side_key(int qlen) { return 255 - min(qlen, 255); }  // descending
-
+// whole-read seed (neither side) is written by the scatter itself.  The key of
+// a side is side_key (side_sort.h) of its query length.
 
 // ------------------------------------- the ungapped certificate (§24, §26)
 // A side whose diagonal loses less than the cheapest gap open needs no DP
@@ -37,6 +37,11 @@ __device__ __forceinline__ int side_key(int qlen) { return 255 - min(qlen, 255);
 // the block's threads take them densely, whichever side they belong to; the
 // side's thread then folds the summaries.  (One thread per whole side ran a
 // wave until its longest side was through: ten passes for an average of two.)
+//
+// count (kFuseSort): the block holds both sides' decisions of
+// its tasks, so it also counts the sides that enter a list, as spec_sort2_count
+// does from the stored records: an LDS histogram of side_key per side, added to
+// the lists' global histograms and to SPC_LCNT / SPC_RCNT once at the end.
 struct UngSide {
   const uint8_t* rd;  // the read; the side's query base j is rd[p0 + d j]
   int64_t x0;         // ... against the 2-strand coordinate x0 + d j
@@ -128,6 +133,33 @@ __device__ __forceinline__ UngSeg ung_pass(const UngSide& s, const DevRef& ref, 
   return g;
 }
 
+// The decision record `u` of a task: which of its sides (query lengths qb, qr)
+// are settled at sort time (cl, cr) and which enter a list.  A certified right
+// side behind a left side that needs the DP has the left call's score for its
+// h0, which the certificate does not depend on: with `ungt` (SpecArgs::ungt is
+// there) it is a late right side, on no list and settled by
+// spec_settle_right_kernel after the left launch; without, it stays on the
+// right list.  The one copy of the rule: the certificate kernel's count, the
+// count kernel, the scatter and the late kernel all decide by it.
+struct SideLists {
+  bool cl, cr, in_l, in_r, late;
+};
+__device__ __forceinline__ SideLists side_lists(const UngRec& u, bool ungt, int qb, int qr) {
+  SideLists s;
+  s.cl = qb > 0 && u.side[0].ok;
+  s.in_l = qb > 0 && !s.cl;
+  const bool okr = qr > 0 && u.side[1].ok;
+  s.cr = okr && !s.in_l;
+  s.late = okr && s.in_l && ungt;
+  s.in_r = qr > 0 && !s.cr && !s.late;
+  return s;
+}
+// ... from the stored record of the task at `slot` of its list (certificate off: every side enters its list)
+__device__ __forceinline__ SideLists side_lists(const SpecArgs& a, size_t slot, int qb, int qr) {
+  if (!a.ung) return SideLists{false, false, qb > 0, qr > 0, false};
+  return side_lists(a.ung[slot], a.ungt != nullptr, qb, qr);
+}
+
 constexpr int kUngTasks = 128;      // tasks of one block pass: a thread per side
 constexpr int kUngPassCap = 256 * 9;  // later passes listed per block pass (a side of 160 bases has nine); a side
                                       // whose passes do not fit runs them itself
@@ -136,8 +168,10 @@ struct UngSeg16 {  // a pass's summary in LDS (sixteen scores of an int8 each)
 };
 
 __global__ void __launch_bounds__(256) spec_ungapped_kernel(DevOpt o, DevRef ref, DevBatch b, SpecArgs a, int round,
-                                                            int bin0, int keep_short) {
+                                                            int bin0, int keep_short, int count) {
   sel_prio();
+  __shared__ int hist[2][kSideKeys];
+  __shared__ int tot[2];
   __shared__ int8_t mat[25], mat8[32];  // the scores by (target, query) base: a lookup per base, kept out of global memory
   __shared__ UngSide sd[256];
   __shared__ uint32_t plist[kUngPassCap];  // side's thread << 8 | pass
@@ -147,6 +181,10 @@ __global__ void __launch_bounds__(256) spec_ungapped_kernel(DevOpt o, DevRef ref
   if (tid < 25) mat[tid] = o.mat[tid];
   if (tid < 32) mat8[tid] = (tid & 7) < 5 ? o.mat[(tid >> 3) * 5 + (tid & 7)] : 0;
   if (tid == 0) listed = 0;
+  if (count) {  // (untouched without: the kernel then costs what it did before the count)
+    for (int k = tid; k < 2 * kSideKeys; k += 256) hist[k >> 8][k & 255] = 0;
+    if (tid < 2) tot[tid] = 0;
+  }
   __syncthreads();
   const int bin = bin0 + (int)blockIdx.y;
   const int list = round * kSpecBins + bin;
@@ -161,6 +199,7 @@ __global__ void __launch_bounds__(256) spec_ungapped_kernel(DevOpt o, DevRef ref
     UngSeg g;
     bool ok = false;
     int extra = 0;  // the passes after the first, if that leaves the side alive
+    int qside = 0;  // this side's query length
     if (i < n) {
       const FatTask f = fat_task(b, a, tl[i]);
       if (right && a.ungt) a.ungt[off + i] = UngTask{f.rbeg, f.pos, f.qls};
@@ -168,6 +207,7 @@ __global__ void __launch_bounds__(256) spec_ungapped_kernel(DevOpt o, DevRef ref
       const int64_t xr = f.rbeg + ln;
       const int qlen = right ? lq - qb - ln : qb;
       const int tlen = right ? (int)(f.rbeg + f.dhi - xr) : f.dlo;
+      qside = qlen;
       // a right side starts from the left score, which is at least the seed's (ln * a)
       ok = qlen > keep && ungapped_band_ok(o.w) &&
            ungapped_call_ok(qlen, tlen, ln * o.a, o.w, o.zdrop, o.max_mat, oe_min);
@@ -226,32 +266,33 @@ __global__ void __launch_bounds__(256) spec_ungapped_kernel(DevOpt o, DevRef ref
       if (!g.dead(oe_min)) rec = UngRec::Side{1, g.side()};
     }
     if (i < n) a.ung[off + i].side[right] = rec;
+    // the task's other side is the neighbouring lane's: i = t0 + (tid >> 1) pairs the lanes 2k and 2k + 1, so a
+    // task's two sides never straddle a wave (a change of that mapping has to change this shuffle with it)
+    if (count) {
+      const int ok2 = __shfl_xor(rec.ok, 1, 64), q2 = __shfl_xor(qside, 1, 64);
+      if (i < n) {
+        UngRec u{};
+        u.side[0].ok = right ? ok2 : rec.ok;
+        u.side[1].ok = right ? rec.ok : ok2;
+        const SideLists sl = side_lists(u, a.ungt != nullptr, right ? q2 : qside, right ? qside : q2);
+        if (right ? sl.in_r : sl.in_l) atomicAdd(&hist[right][side_key(qside)], 1);
+      }
+    }
     if (tid == 0) listed = 0;
     __syncthreads();
   }
-}
-
-// the stored decision of the task at `slot` of its list: which of its sides
-// (query lengths qb, qr) are settled here (cl, cr) and which enter a list.  A
-// certified right side behind a left side that needs the DP has the left
-// call's score for its h0, which the certificate does not depend on: it is a
-// late right side, on no list and settled by
-// spec_settle_right_kernel after the left launch; without SpecArgs::ungt it
-// stays on the right list.
-struct SideLists {
-  bool cl, cr, in_l, in_r, late;
-};
-__device__ __forceinline__ SideLists side_lists(const SpecArgs& a, size_t slot, int qb, int qr) {
-  SideLists s{false, false, qb > 0, qr > 0, false};
-  if (a.ung) {
-    s.cl = qb > 0 && a.ung[slot].side[0].ok;
-    s.in_l = qb > 0 && !s.cl;
-    const bool okr = qr > 0 && a.ung[slot].side[1].ok;
-    s.cr = okr && !s.in_l;
-    s.late = okr && s.in_l && a.ungt;
-    s.in_r = qr > 0 && !s.cr && !s.late;
+  if (!count) return;
+  int32_t* ghL = a.sorth + (round * 2 + bin) * kSortKeys;
+  int32_t* ghR = ghL + kSortWordsR;
+  for (int k = tid; k < 2 * kSideKeys; k += 256) {
+    const int c = hist[k >> 8][k & 255];
+    if (c) {
+      atomicAdd((k >> 8) ? &ghR[k & 255] : &ghL[k & 255], c);
+      atomicAdd(&tot[k >> 8], c);
+    }
   }
-  return s;
+  __syncthreads();
+  if (tid < 2 && tot[tid]) atomicAdd(&a.ctr[(tid ? SPC_RCNT : SPC_LCNT) + list], tot[tid]);
 }
 
 // a certified right side's result on top of the slot `e` that the left side
@@ -368,9 +409,20 @@ __global__ void __launch_bounds__(256) spec_sort2_scan(SpecArgs a, int round, in
     a.ctr[(side ? SPC_RLONG : SPC_LLONG) + round * kSpecBins + bin] = part[t] - v;
 }
 
-__global__ void __launch_bounds__(256) spec_sort2_scatter(DevOpt o, DevBatch b, SpecArgs a, int round, int bin0) {
+// The scatter.  scan = 0: spec_sort2_scan has turned the lists' histograms into
+// cursors, and a pass's range for a key is what it claims there.  scan = 1
+// (kFuseSort): the histograms stay as counted and read-only;
+// every block computes their exclusive prefix itself at its start (a wave per
+// side, side_sort.h), and a pass's range for a key is that first position plus
+// what it claims from the key's cursor, a zeroed word kSortCursor further on.
+// Block 0 of the first bin then writes the lists' SPC_LLONG / SPC_RLONG words
+// (short_q > 0) as the scan kernel would: the side kernels read them after
+// this kernel's end.
+__global__ void __launch_bounds__(256) spec_sort2_scatter(DevOpt o, DevBatch b, SpecArgs a, int round, int bin0,
+                                                          int short_q, int scan) {
   sel_prio();
   __shared__ int cnt[2][256];
+  __shared__ int first[2][kSideKeys];  // scan: a key's first position
   __shared__ int ung[2];  // sides settled here, their query lengths
   const int bin = bin0 + (int)blockIdx.y;
   const int list = round * kSpecBins + bin;
@@ -378,7 +430,26 @@ __global__ void __launch_bounds__(256) spec_sort2_scatter(DevOpt o, DevBatch b, 
   int32_t* ghR = ghL + kSortWordsR;
   for (int k = threadIdx.x; k < 2 * 256; k += 256) cnt[k >> 8][k & 255] = 0;
   if (threadIdx.x < 2) ung[threadIdx.x] = 0;
+  if (scan) {
+    const int side = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+    if (side < 2) {
+      const int4 h4 = reinterpret_cast<const int4*>(side ? ghR : ghL)[lane];
+      const int32_t h[kSideLaneKeys] = {h4.x, h4.y, h4.z, h4.w};
+      const int32_t own = side_lane_total(h);
+      int32_t inc = own;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) inc = side_scan_step(inc, __shfl_up(inc, d, 64), lane, d);
+      int32_t f[kSideLaneKeys];
+      side_lane_prefix(h, inc - own, f);
+#pragma unroll
+      for (int j = 0; j < kSideLaneKeys; ++j) first[side][kSideLaneKeys * lane + j] = f[j];
+    }
+    ghL += kSortCursor;
+    ghR += kSortCursor;
+  }  // (scan = 0 leaves first[] untouched and unread: the kernel then costs what it did before)
   __syncthreads();
+  if (scan && short_q > 0 && bin == 0 && blockIdx.x == 0 && threadIdx.x < 2)
+    a.ctr[(threadIdx.x ? SPC_RLONG : SPC_LLONG) + list] = side_short_first(first[threadIdx.x], short_q);
   const int n = __hip_atomic_load(&a.ctr[SPC_CNT + list], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const size_t off = spec_list_off(list, b.n_chains, b.n_seeds);
   const int2* tl = a.tasks + off;
@@ -422,7 +493,8 @@ __global__ void __launch_bounds__(256) spec_sort2_scatter(DevOpt o, DevBatch b, 
     __syncthreads();
     for (int k = threadIdx.x; k < 2 * 256; k += 256) {
       const int c = cnt[k >> 8][k & 255];
-      cnt[k >> 8][k & 255] = c ? atomicAdd((k >> 8) ? &ghR[k & 255] : &ghL[k & 255], c) : 0;  // this pass's range
+      cnt[k >> 8][k & 255] =
+          c ? (scan ? first[k >> 8][k & 255] : 0) + atomicAdd((k >> 8) ? &ghR[k & 255] : &ghL[k & 255], c) : 0;  // this pass's range
     }
     __syncthreads();
 #pragma unroll
@@ -846,13 +918,18 @@ __global__ void __launch_bounds__(kBlock) spec_side4_kernel(DevOpt o, DevRef ref
 }
 
 
+// kFuseSort: two launches, certificate + count and scan +
+// scatter; a context without the certificate keeps the count kernel, three
 void launch_side_sort(const ExtRound& r, int bin0, int nbins, int short_q, int short_fill) {
+  const int fuse = (r.ss.fused & kFuseSort) ? 1 : 0;
   if (r.a.ung)
     hipLaunchKernelGGL(spec_ungapped_kernel, dim3(512, nbins), dim3(256), 0, r.st, r.o, r.ref, r.b, r.a, r.round, bin0,
-                       short_fill == 0 ? short_q : 0);
-  hipLaunchKernelGGL(spec_sort2_count, dim3(256, nbins), dim3(256), 0, r.st, r.b, r.a, r.round, bin0);
-  hipLaunchKernelGGL(spec_sort2_scan, dim3(2 * nbins), dim3(256), 0, r.st, r.a, r.round, bin0, nbins, short_q);
-  hipLaunchKernelGGL(spec_sort2_scatter, dim3(256, nbins), dim3(256), 0, r.st, r.o, r.b, r.a, r.round, bin0);
+                       short_fill == 0 ? short_q : 0, fuse);
+  if (!(fuse && r.a.ung)) hipLaunchKernelGGL(spec_sort2_count, dim3(256, nbins), dim3(256), 0, r.st, r.b, r.a, r.round, bin0);
+  if (!fuse)
+    hipLaunchKernelGGL(spec_sort2_scan, dim3(2 * nbins), dim3(256), 0, r.st, r.a, r.round, bin0, nbins, short_q);
+  hipLaunchKernelGGL(spec_sort2_scatter, dim3(256, nbins), dim3(256), 0, r.st, r.o, r.b, r.a, r.round, bin0, short_q,
+                     fuse);
 }
 
 // the two side launches of the phased extension for one list: every left
@@ -868,12 +945,26 @@ static void launch_side_pair(const ExtRound& r, int list, const ExtPlan& p, int 
                      list, r.tb_bytes, (int)p.wave_lds, p.short_q, p.tb_short, short_fill);
   // the late right sides go on from the left launch's slots.  One launch per list, after that list's own left
   // launch, not one per round with grid.y = bins: ext_plan phases only the first bin today, and with two
-  // phased bins a single launch would have to wait for the second list's left launch
-  if (r.a.ungt)
+  // phased bins a single launch would have to wait for the second list's left launch.
+  // kFuseSettle: on the side stream, idle during an extension round, beside the right launch
+  // and not ahead of it.  The two kernels never touch the same SeedExt slot: the right launch reads and
+  // writes the slots of the tasks on the right list alone, this kernel those of the late tasks, and side_lists
+  // puts a late task on no right list; both wait for the left launch, which wrote what either goes on from.
+  // Both add their cells to SPC_SPEC64 atomically, the late kernel its own counters (SPC_UNGR_*) too.
+  const bool beside = r.a.ungt && r.ss.side && (r.ss.fused & kFuseSettle);
+  if (beside) {
+    (void)hipEventRecord(r.ss.fork, r.st);
+    (void)hipStreamWaitEvent(r.ss.side, r.ss.fork, 0);
+    hipLaunchKernelGGL(spec_settle_right_kernel, dim3(256, 1), dim3(256), 0, r.ss.side, r.o, r.b, r.a, r.round,
+                       list % kSpecBins);
+    (void)hipEventRecord(r.ss.join, r.ss.side);
+  } else if (r.a.ungt) {
     hipLaunchKernelGGL(spec_settle_right_kernel, dim3(256, 1), dim3(256), 0, r.st, r.o, r.b, r.a, r.round,
                        list % kSpecBins);
+  }
   hipLaunchKernelGGL((spec_side4_kernel<G, PMAX, K8, true>), dim3(gr), dim3(kBlock), lds, r.st, r.o, r.ref, r.b, r.a,
                      list, r.tb_bytes, (int)p.wave_lds, p.short_q, p.tb_short, short_fill);
+  if (beside) (void)hipStreamWaitEvent(r.st, r.ss.join, 0);
 }
 
 // the side kernels compiled are exactly these cases

@@ -239,6 +239,7 @@ PROTOS = {
     "bwagpu_debug_spec_ungapped_right": (C.c_int, [_VP, _VP, _VP]),
     "bwagpu_ctx_emu_finish": (C.c_int, [_VP, C.c_int]),
     "bwagpu_debug_spec_finish": (C.c_int, [_VP, _VP, _VP]),
+    "bwagpu_ctx_fused_launches": (C.c_int, [_VP, C.c_int]),
     "bwagpu_debug_ext_kernel": (C.c_int, [_VP, C.c_int32]),
     "bwagpu_streams_concurrent": (C.c_int, [_VP, _VP]),
     "bwagpu_bwt_sa": (C.c_int, [_VP, C.c_int64, _VP, _VP]),
@@ -297,7 +298,7 @@ def load() -> C.CDLL:
         raise RuntimeError(f"bwagpu: HIP engine library missing at {p}; run __graft_entry__.build()")
     lib = C.CDLL(p)
     for name, (res, args) in PROTOS.items():
-        if (name.startswith("bwagpu_debug_") or name in ("bwagpu_ctx_light_pack", "bwagpu_ctx_ungapped", "bwagpu_ctx_ungapped_right", "bwagpu_ctx_emu_finish")) and not hasattr(lib, name):
+        if (name.startswith("bwagpu_debug_") or name in ("bwagpu_ctx_light_pack", "bwagpu_ctx_ungapped", "bwagpu_ctx_ungapped_right", "bwagpu_ctx_emu_finish", "bwagpu_ctx_fused_launches")) and not hasattr(lib, name):
             continue  # an A/B build of an older tree (BWAGPU_LIB) may lack a newer diagnostic or A/B switch
         fn = getattr(lib, name)
         fn.restype = res

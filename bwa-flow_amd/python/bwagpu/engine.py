@@ -390,6 +390,13 @@ class Engine:
                     "debug_spec_ungapped_right")
         return out.reshape(3, 2)
 
+    def fused_launches(self, mask: int = -1) -> int:
+        """this context's fused launches (bwagpu_ctx_fused_launches, default 5):
+        bit 1 the side lists' sort in two launches, bit 2 the late right sides
+        beside the right launch, bit 4 heavy reads without a pair matrix in the
+        scan's launch; 0 = every step a launch of its own; -> the previous mask"""
+        return self.lib.bwagpu_ctx_fused_launches(self.ctx, int(mask))
+
     def emu_finish(self, on: int = -1) -> int:
         """this context's finishing of decided light reads in the emulate
         selection pass (bwagpu_ctx_emu_finish, default on); -> the previous setting"""

@@ -398,6 +398,21 @@ int bwagpu_chain2aln_device(bwagpu_ctx_t *ctx, const bwagpu_batch_t *dev_batch,
    dev_stats[3] bit 2 (as a read over BWAGPU_MAX_READ_LEN does) and gets no
    regions.  The per-read path (BWAGPU_C2A_PATH=fast) ignores it. */
 int bwagpu_set_device_read_len(bwagpu_ctx_t *ctx, int32_t max_len);
+/* Which steps of a _device batch's chain2aln share a launch, a
+   bit mask; default 5 (bits 1 and 4; bit 2 measured no gain and starts off), or
+   BWAGPU_FUSED_LAUNCHES when the context is made.
+   1: the phased extension's side lists are sorted in two launches per round
+      (the ungapped certificate's kernel counts the sides, the scatter scans
+      the counts) instead of four;
+   2: the late right sides (bwagpu_ctx_ungapped_right) are settled on the
+      context's side stream beside a list's right launch, not ahead of it
+      (acts only where the caller's stream leaves the context a side stream);
+   4: heavy reads without a pair matrix are selected inside the matrix scan's
+      launch in the emulate and the final pass, not by a launch of their own.
+   0 is the launch sequence without any of them.  Regions, counters and list
+   contents do not depend on the mask.  mask < 0 only queries; returns the
+   previous mask. */
+int bwagpu_ctx_fused_launches(bwagpu_ctx_t *ctx, int mask);
 
 /* The blocking task-list entries below (host buffers) validate every task
    before anything is enqueued: a task outside its pools or a negative or
