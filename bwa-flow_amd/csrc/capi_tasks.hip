@@ -4,6 +4,7 @@
 // half way leaves through HostCall's destructor, which synchronises.  The
 // lists, counts, boff, starts and stats words are bookkeeping: plain copies.
 #include <hip/hip_runtime.h>
+#include <string.h>
 
 #include "align2.h"
 #include "ctx.h"
@@ -450,6 +451,90 @@ int bwagpu_xa_select_device(bwagpu_ctx_t* ctx, const bwagpu_samopt_t* xopt, int3
   a.reg_off = dev_reg_off, a.regs = dev_regs, a.n = dev_n, a.sel = dev_sel, a.out_mapq = dev_out_mapq;
   a.xa_of = dev_xa_of, a.job_select = dev_job_select;
   HIPC(launch_xa_select(a, st), "xa_select launch");
+  return BWAGPU_OK;
+}
+
+namespace {
+
+// the argument checks of bwagpu_sam_text_device -> BWAGPU_OK with *rg_len, or the code with *why
+int sam_text_check(const bwagpu_samtext_t* t, int32_t n_reads, int32_t* rg_len, const char** why) {
+  if (!t) return *why = "NULL bwagpu_samtext_t", BWAGPU_E_INVAL;
+  if (int rc = sel_flags_check(t->flags, why)) return rc;
+  if (t->flags & BWAGPU_MEM_F_REF_HDR) return *why = "MEM_F_REF_HDR is not implemented", BWAGPU_E_UNSUPPORTED;
+  if (n_reads < 0) return *why = "negative read count", BWAGPU_E_INVAL;
+  if (n_reads & 1) return *why = "odd read count: reads 2i and 2i+1 are a pair", BWAGPU_E_INVAL;
+  if (t->text_cap < 0 || t->n_contigs < 0 || t->job_cap < 0) return *why = "negative capacity", BWAGPU_E_INVAL;
+  if (t->max_ops < 1 || t->max_md < 1) return *why = "max_ops and max_md must be at least 1", BWAGPU_E_INVAL;
+  *rg_len = 0;
+  if (t->rg_id) {
+    const size_t l = strnlen(t->rg_id, BWAGPU_SAM_MAX_RG + 1);
+    if (l > BWAGPU_SAM_MAX_RG) return *why = "rg_id is longer than BWAGPU_SAM_MAX_RG", BWAGPU_E_INVAL;
+    *rg_len = (int32_t)l;
+  }
+  if (!t->dev_text_off || !t->dev_text_n || (t->text_cap && !t->dev_text))
+    return *why = "NULL output array", BWAGPU_E_INVAL;
+  if (n_reads &&
+      (!t->dev_reg_off || !t->dev_regs || !t->dev_n || !t->dev_sel || !t->dev_out_mapq || !t->dev_xa_of ||
+       !t->dev_job_of || !t->dev_aln || !t->dev_cigar || !t->dev_md || !t->dev_seq_off || !t->dev_seq ||
+       !t->dev_name_off || !t->dev_names || !t->dev_contig_off || !t->dev_contig_names || !t->dev_status ||
+       (t->dev_comment_off && !t->dev_comments)))
+    return *why = "NULL array", BWAGPU_E_INVAL;
+  return BWAGPU_OK;
+}
+
+// the scratch of bwagpu_sam_text_device on st, behind every earlier user of it
+int sam_text_scratch(bwagpu_ctx_t* ctx, int32_t n_reads, hipStream_t st, void** scratch) {
+  const size_t bytes = sam_text_scratch_bytes(n_reads);
+  if (!ctx->r2d_done) HIPC(hipEventCreateWithFlags(&ctx->r2d_done, hipEventDisableTiming), "event");
+  if (ctx->r2d_pending && bytes > ctx->sam_scratch.cap) HIPC(hipEventSynchronize(ctx->r2d_done), "event sync");
+  if (ctx->r2d_pending) HIPC(hipStreamWaitEvent(st, ctx->r2d_done, 0), "stream wait");
+  HIPC(ctx->sam_scratch.ensure(bytes), "hipMalloc");
+  *scratch = ctx->sam_scratch.p;
+  return BWAGPU_OK;
+}
+
+}  // namespace
+
+int bwagpu_sam_text_device(bwagpu_ctx_t* ctx, const bwagpu_samtext_t* t, int32_t n_reads, void* stream) {
+  if (!ctx) return BWAGPU_E_INVAL;
+  const char* why = "";
+  int32_t rg_len = 0;
+  if (int rc = sam_text_check(t, n_reads, &rg_len, &why)) return fail(ctx, rc, why);
+  hipStream_t st = nullptr;
+  TRY(entry_stream(ctx, stream, &st));
+  if (n_reads == 0) {
+    HIPC(hipMemsetAsync(t->dev_text_off, 0, sizeof(int64_t), st), "memset");
+    HIPC(hipMemsetAsync(t->dev_text_n, 0, 2 * sizeof(int64_t), st), "memset");
+    return BWAGPU_OK;
+  }
+  void* scratch = nullptr;
+  TRY(sam_text_scratch(ctx, n_reads, st, &scratch));
+  SamRgBytes rg{};
+  if (rg_len) memcpy(rg.c, t->rg_id, (size_t)rg_len);
+  const hipError_t e = launch_sam_text(*t, n_reads, rg, rg_len, scratch, st);
+  if (hipEventRecord(ctx->r2d_done, st) == hipSuccess) ctx->r2d_pending = true;
+  HIPC(e, "sam_text launch");
+  return BWAGPU_OK;
+}
+
+// one step of bwagpu_sam_text_device alone (0 count, 1 scan, 2 write), for tools_dev/sam_text_bench.py;
+// the steps of one call share the context's scratch, so they run in order on one stream
+int bwagpu_debug_sam_text_step(bwagpu_ctx_t* ctx, const bwagpu_samtext_t* t, int32_t n_reads, int32_t step,
+                               void* stream) {
+  if (!ctx || step < 0 || step > 2) return BWAGPU_E_INVAL;
+  const char* why = "";
+  int32_t rg_len = 0;
+  if (int rc = sam_text_check(t, n_reads, &rg_len, &why)) return fail(ctx, rc, why);
+  if (n_reads == 0) return fail(ctx, BWAGPU_E_INVAL, "no reads");
+  hipStream_t st = nullptr;
+  TRY(entry_stream(ctx, stream, &st));
+  void* scratch = nullptr;
+  TRY(sam_text_scratch(ctx, n_reads, st, &scratch));
+  SamRgBytes rg{};
+  if (rg_len) memcpy(rg.c, t->rg_id, (size_t)rg_len);
+  const hipError_t e = launch_sam_text_step(step, *t, n_reads, rg, rg_len, scratch, st);
+  if (hipEventRecord(ctx->r2d_done, st) == hipSuccess) ctx->r2d_pending = true;
+  HIPC(e, "sam_text step launch");
   return BWAGPU_OK;
 }
 

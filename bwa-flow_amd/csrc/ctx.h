@@ -194,6 +194,9 @@ struct bwagpu_ctx {
   // read-back and its whole call.
   DevBuf r2d_keys, r2d_lists, r2d_tab, r2d_z, r2d_sums;
   HostBuf r2d_htab;
+  // bwagpu_sam_text_device: the rg_id's bytes, the reads' text lengths and their block sums; ordered
+  // by r2d_done like the scratch above
+  DevBuf sam_scratch;
   hipEvent_t r2d_done = nullptr, r2d_ev[2] = {};
   bool r2d_pending = false, r2d_timing = false, r2d_timed = false;
   double r2d_wait_ms = 0, r2d_call_ms = 0;

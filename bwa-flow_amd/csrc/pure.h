@@ -270,4 +270,86 @@ BWAGPU_HD inline bool xa_over_cap(int cnt, bool has_alt, int max_hits, int max_h
   return cnt > max_hits_alt || (!has_alt && cnt > max_hits);
 }
 
+// ---- the arithmetic of mem_aln2sam (bwa/bwamem.c:824-961) behind bwagpu_sam_text_device ----
+
+// characters kputw / kputl print for v: its decimal digits and the sign
+BWAGPU_HD inline int dec_width_u64(uint64_t v) {
+  int w = 1;
+  while (v >= 10) v /= 10, ++w;
+  return w;
+}
+BWAGPU_HD inline uint64_t dec_mag(int64_t v) { return v < 0 ? 0 - (uint64_t)v : (uint64_t)v; }
+BWAGPU_HD inline int dec_width(int64_t v) { return dec_width_u64(dec_mag(v)) + (v < 0); }
+// the k-th digit of v from the right (k = 0: the ones)
+BWAGPU_HD inline int dec_digit(uint64_t v, int k) {
+  for (; k > 0; --k) v /= 10;
+  return (int)(v % 10);
+}
+
+// "pa:f:%.3f" of (double)score / alt_sc (bwamem.c:945): the thousandths that printf
+// prints, which rounds the quotient's exact binary value half-to-even, taken in
+// integers from the double's mantissa.  x = M * 2^-s with M < 2^53, so M * 1000
+// fits 63 bits; a quotient under 2^-11 (s > 63) rounds to zero.  *neg: the
+// quotient's sign bit, which printf prints in front of a zero as well.
+BWAGPU_HD inline uint64_t pa_thousandths(int score, int alt_sc, bool* neg) {
+  const double x = (double)score / alt_sc;
+  uint64_t b;
+  __builtin_memcpy(&b, &x, 8);
+  *neg = (b >> 63) != 0;
+  const int ex = (int)((b >> 52) & 0x7ff);
+  if (ex == 0) return 0;  // +-0 (two ints give no denormal)
+  const uint64_t p = ((b & ((1ull << 52) - 1)) | (1ull << 52)) * 1000;
+  const int s = 1075 - ex;  // x = mantissa * 2^-s
+  if (s <= 0) return p << -s;  // |x| >= 2^52: not a quotient of two ints
+  if (s > 63) return 0;
+  const uint64_t q = p >> s, rem = p & ((1ull << s) - 1), half = 1ull << (s - 1);
+  return q + (rem > half || (rem == half && (q & 1)));
+}
+
+// a record's or a mate's coordinates as mem_aln2sam rewrites them
+struct SamCoord {
+  int64_t pos;
+  int32_t rid, is_rev, n_cigar;
+};
+// bwamem.c:844-852 on copies p and m of the record and its mate (mem_sam_pe always
+// passes one): the line's flag bits, and the coordinates an unmapped end takes over
+BWAGPU_HD inline int sam_flag(int flag, SamCoord* p, SamCoord* m) {
+  flag |= 0x1;
+  flag |= p->rid < 0 ? 0x4 : 0;
+  flag |= m->rid < 0 ? 0x8 : 0;
+  if (p->rid < 0 && m->rid >= 0) p->rid = m->rid, p->pos = m->pos, p->is_rev = m->is_rev, p->n_cigar = 0;
+  if (m->rid < 0 && p->rid >= 0) m->rid = p->rid, m->pos = p->pos, m->is_rev = p->is_rev, m->n_cigar = 0;
+  flag |= p->is_rev ? 0x10 : 0;
+  flag |= m->is_rev ? 0x20 : 0;
+  return flag;
+}
+// TLEN where p->rid == m->rid (bwamem.c:874-877); rlen = get_rlen of each CIGAR
+BWAGPU_HD inline int64_t sam_tlen(const SamCoord& p, int p_rlen, const SamCoord& m, int m_rlen) {
+  if (m.n_cigar == 0 || p.n_cigar == 0) return 0;
+  const int64_t p0 = p.pos + (p.is_rev ? p_rlen - 1 : 0);
+  const int64_t p1 = m.pos + (m.is_rev ? m_rlen - 1 : 0);
+  return -(p0 - p1 + (p0 > p1 ? 1 : p0 < p1 ? -1 : 0));
+}
+// the clip rules.  Clips turn hard on a line with which > 0, without MEM_F_SOFTCLIP,
+// of a non-ALT record (bwamem.c:830, 887, 901); add_cigar then prints which ? 'H' : 'S'
+// for op 3 and 4 alike
+BWAGPU_HD inline bool sam_clip_rewrite(int opt_flag, int is_alt) { return !(opt_flag & 0x200) && !is_alt; }
+BWAGPU_HD inline int sam_cigar_op(int c, bool rewrite, int which) {
+  return rewrite && (c == 3 || c == 4) ? (which ? 4 : 3) : c;
+}
+// SEQ / QUAL of a line are the read's [qb, qe), cut by the first and last op when
+// they are clips and the line hard-clips (bwamem.c:886-890, 900-904); the two ends
+// swap on the reverse strand.  n_cigar > 0.
+BWAGPU_HD inline void sam_seq_range(int l_seq, bool cut, int is_rev, uint32_t first_op, uint32_t last_op, int* qb,
+                                    int* qe) {
+  int b = 0, e = l_seq;
+  if (cut) {
+    const int c5 = ((first_op & 0xf) == 4 || (first_op & 0xf) == 3) ? (int)(first_op >> 4) : 0;
+    const int c3 = ((last_op & 0xf) == 4 || (last_op & 0xf) == 3) ? (int)(last_op >> 4) : 0;
+    if (!is_rev) b += c5, e -= c3;
+    else e -= c5, b += c3;
+  }
+  *qb = b, *qe = e;
+}
+
 }  // namespace bwagpu

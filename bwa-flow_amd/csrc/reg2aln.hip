@@ -25,6 +25,7 @@
 //  * MD/NM: matched runs compared 64 bases per step, mismatches from a ballot.
 #include <hip/hip_runtime.h>
 
+#include "block_scan.h"
 #include "engine.h"
 #include "global_dp.h"
 #include "reg2aln.h"
@@ -446,27 +447,6 @@ __device__ __forceinline__ int r2j_count(int r, int n_reads, const int64_t* reg_
   int c = 0;
   for (int k = 0; k < n[r]; ++k) c += select[base + k] >= 0;
   return c;
-}
-
-// exclusive prefix of v over the workgroup's 256 threads; *total = the workgroup's sum
-__device__ __forceinline__ int block_excl_scan(int v, int* total) {
-  __shared__ int wsum[4];
-  const int lane = (int)(threadIdx.x & 63), w = (int)(threadIdx.x >> 6);
-  int incl = v;
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += y;
-  }
-  __syncthreads();  // wsum of an earlier call has been read
-  if (lane == 63) wsum[w] = incl;
-  __syncthreads();
-  int before = 0, all = 0;
-  for (int x = 0; x < 4; ++x) {
-    before += x < w ? wsum[x] : 0;
-    all += wsum[x];
-  }
-  *total = all;
-  return before + incl - v;
 }
 
 }  // namespace

@@ -180,6 +180,26 @@ def default_samopt(flags: int = 0) -> SamOpt:
     return SamOpt(int(flags), 0.80, 5, 200)
 
 
+MEM_F_REF_HDR, MEM_F_SOFTCLIP, MEM_F_XB = 0x100, 0x200, 0x2000
+SAM_DONE, SAM_SKIPPED, SAM_NEEDS_HOST, SAM_NO_ROOM = 0, 1, 2, 3
+SAM_MAX_RG = 255
+
+
+class SamText(C.Structure):
+    """bwagpu_samtext_t: the arguments of bwagpu_sam_text_device (device pointers but rg_id)"""
+    _fields_ = [(k, C.c_void_p) for k in (
+        "dev_reg_off", "dev_regs", "dev_n", "dev_sel", "dev_out_mapq", "dev_xa_of", "dev_job_of", "dev_aln",
+        "dev_cigar", "dev_md", "dev_seq_off", "dev_seq", "dev_qual", "dev_name_off", "dev_names", "dev_comment_off",
+        "dev_comments", "dev_contig_off", "dev_contig_names")] + [
+        ("rg_id", C.c_char_p), ("flags", C.c_int32), ("n_contigs", C.c_int32), ("job_cap", C.c_int32),
+        ("max_ops", C.c_int32), ("max_md", C.c_int32), ("pad_", C.c_int32), ("text_cap", C.c_int64),
+        ("dev_text", C.c_void_p), ("dev_text_off", C.c_void_p), ("dev_status", C.c_void_p),
+        ("dev_text_n", C.c_void_p)]
+
+
+assert C.sizeof(SamText) == 224
+
+
 def default_chainopt() -> dict:
     """mem_opt_init's chaining defaults (bwa/bwamem.c:62-72)"""
     return dict(max_occ=500, max_chain_gap=10000, min_chain_weight=0, max_chain_extend=1 << 30, mask_level=0.5,
@@ -211,6 +231,8 @@ PROTOS = {
                                         _VP, _VP]),
     "bwagpu_reg2aln_jobs_device": (C.c_int, [_VP, C.c_int32, _VP, _VP, _VP, _VP, _VP, C.c_int32, _VP, _VP, _VP, _VP]),
     "bwagpu_xa_select_device": (C.c_int, [_VP, C.POINTER(SamOpt), C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "bwagpu_sam_text_device": (C.c_int, [_VP, C.POINTER(SamText), C.c_int32, _VP]),
+    "bwagpu_debug_sam_text_step": (C.c_int, [_VP, C.POINTER(SamText), C.c_int32, C.c_int32, _VP]),
     "bwagpu_debug_reg2aln_times": (C.c_int, [_VP, _VP]),
     "bwagpu_last_stats": (C.c_int, [_VP, C.c_int, C.POINTER(Stats)]),
     "bwagpu_debug_set_trace": (C.c_int, [_VP, _VP]),

@@ -290,6 +290,17 @@ class Engine:
             C.c_void_p(dev_sel), C.c_void_p(dev_out_mapq), C.c_void_p(dev_xa_of), C.c_void_p(dev_job_select),
             C.c_void_p(stream) if stream else None), "xa_select_device")
 
+    def sam_text_device(self, t: abi.SamText, n_reads: int, stream: int | None = None, step: int | None = None):
+        """the XA strings and mem_aln2sam on what the device chain left, asynchronous on stream: read r's SAM
+        lines are dev_text[dev_text_off[r] : dev_text_off[r + 1]], dev_status per pair (abi.SAM_*),
+        dev_text_n = (written, needed).  step (0 count, 1 scan, 2 write) runs that step alone, for timing"""
+        st = C.c_void_p(stream) if stream else None
+        if step is None:
+            self._check(self.lib.bwagpu_sam_text_device(self.ctx, C.byref(t), int(n_reads), st), "sam_text_device")
+        else:
+            self._check(self.lib.bwagpu_debug_sam_text_step(self.ctx, C.byref(t), int(n_reads), int(step), st),
+                        "debug_sam_text_step")
+
     def debug_reg2aln_times(self) -> dict:
         """the last reg2aln_device call (waits for it): the host's wait at the read-back, the bin kernels'
         span by HIP events, the host time of the call.  The first use only switches the timing on"""

@@ -79,8 +79,11 @@
  *   bwagpu_xa_select_device
  *       the selection of mem_gen_alt (bwa/bwamem_extra.c:90-118): which regions
  *       are hits of which record's XA string, and so which regions need a
- *       CIGAR (bwagpu_reg2aln_jobs_device, bwagpu_reg2aln_device).  The XA
- *       strings themselves and the SAM text (mem_aln2sam) stay on the host.
+ *       CIGAR (bwagpu_reg2aln_jobs_device, bwagpu_reg2aln_device).
+ *   bwagpu_sam_text_device
+ *       the XA strings themselves (bwamem_extra.c:120-135) and mem_aln2sam
+ *       (bwa/bwamem.c:837-961) for every record of a batch of pairs: the text
+ *       of bseq1_t.sam, in device memory.
  *   bwagpu_last_error
  *       the what() of fpgaHangError / fpgaResultsError / std::runtime_error
  *       (src/util.h:16-32, OpenCLEnv.h:21-31).
@@ -847,7 +850,7 @@ typedef struct {
    untouched, its out_mapq entries are -1 and the caller keeps the CPU path for
    it.  mem_gen_alt's selection is bwagpu_xa_select_device, the CIGARs are
    bwagpu_reg2aln_jobs_device and bwagpu_reg2aln_device; the XA strings and the
-   SAM text stay on the host.
+   SAM text are bwagpu_sam_text_device.
    Before any launch: odd n_reads, negative counts, n_pri outside [0, n], a rid
    outside the reference, overlapping spans and NULLs return BWAGPU_E_INVAL;
    the refused flags and a live orientation with high - low over 2^20 return
@@ -910,6 +913,100 @@ int bwagpu_xa_select_device(bwagpu_ctx_t *ctx, const bwagpu_samopt_t *xopt, int3
                             const int64_t *dev_reg_off, const bwagpu_alnreg_t *dev_regs, const int32_t *dev_n,
                             const bwagpu_pairsel_t *dev_sel, const int32_t *dev_out_mapq, int32_t *dev_xa_of,
                             int32_t *dev_job_select, void *stream);
+
+/* ---- paired ends: the XA strings and mem_aln2sam on the device ---- */
+
+#define BWAGPU_MEM_F_REF_HDR  0x100  /* refused by bwagpu_sam_text_device (XR:Z needs bntann1_t.anno) */
+#define BWAGPU_MEM_F_SOFTCLIP 0x200
+#define BWAGPU_MEM_F_XB       0x2000
+
+/* bwagpu_sam_text_device's per-pair status */
+#define BWAGPU_SAM_DONE       0
+#define BWAGPU_SAM_SKIPPED    1 /* sel.status was not BWAGPU_SEL_DONE                                */
+#define BWAGPU_SAM_NEEDS_HOST 2 /* a needed region has no job (job_of == -1, or outside job_cap), a
+                                   needed record is not BWAGPU_ALN_OK or does not fit its slots, a
+                                   rid is outside [0, n_contigs), or an index of sel is outside its
+                                   read                                                             */
+#define BWAGPU_SAM_NO_ROOM    3 /* the pair's text would pass text_cap                               */
+
+#define BWAGPU_SAM_MAX_RG 255 /* longest bwa_rg_id taken */
+
+/* The arguments of bwagpu_sam_text_device.  Device memory unless said otherwise.
+   The regions, dev_sel, dev_out_mapq and dev_xa_of as bwagpu_pair_select_device and
+   bwagpu_xa_select_device leave them; dev_job_of as bwagpu_reg2aln_jobs_device and
+   dev_aln, dev_cigar (max_ops words per job), dev_md (max_md bytes per job) as
+   bwagpu_reg2aln_device leave them, job_cap their capacity in jobs.
+   Read r: nt4 bases dev_seq[dev_seq_off[r] .. dev_seq_off[r+1]) (the CIGAR stage's
+   pool), its qualities at the same offsets of dev_qual (NULL: "*"), its name
+   dev_names[dev_name_off[r] .. dev_name_off[r+1]) (each read of a pair carries its
+   own; they are not compared), its comment likewise (dev_comment_off NULL, or an
+   empty span: none).  Contig c's name is dev_contig_names[dev_contig_off[c] ..
+   dev_contig_off[c+1]), c < n_contigs.  rg_id is a host string, bwa_rg_id (NULL or
+   empty: no RG:Z), at most BWAGPU_SAM_MAX_RG bytes; it is read before the call
+   returns.  flags are mem_opt_t.flag's bits. */
+typedef struct {
+  const int64_t *dev_reg_off;
+  const bwagpu_alnreg_t *dev_regs;
+  const int32_t *dev_n;
+  const bwagpu_pairsel_t *dev_sel;
+  const int32_t *dev_out_mapq;
+  const int32_t *dev_xa_of;
+  const int32_t *dev_job_of;
+  const bwagpu_aln_t *dev_aln;
+  const uint32_t *dev_cigar;
+  const char *dev_md;
+  const int64_t *dev_seq_off;
+  const uint8_t *dev_seq;
+  const char *dev_qual;
+  const int64_t *dev_name_off;
+  const char *dev_names;
+  const int64_t *dev_comment_off;
+  const char *dev_comments;
+  const int64_t *dev_contig_off;
+  const char *dev_contig_names;
+  const char *rg_id; /* host */
+  int32_t flags;
+  int32_t n_contigs;
+  int32_t job_cap;
+  int32_t max_ops, max_md;
+  int32_t pad_;
+  int64_t text_cap;
+  char *dev_text;        /* [text_cap]                                   */
+  int64_t *dev_text_off; /* [n_reads + 1]                                */
+  int32_t *dev_status;   /* [n_reads / 2] BWAGPU_SAM_*                   */
+  int64_t *dev_text_n;   /* [2]: bytes written, bytes needed             */
+} bwagpu_samtext_t;
+
+/* The last step of mem_sam_pe for every pair of a batch, on device memory,
+   asynchronous on stream (hipStream_t, NULL = the context's slot-0 stream; no
+   host wait), directly after bwagpu_reg2aln_device on that stream: mem_gen_alt's
+   strings (bwa/bwamem_extra.c:120-135) and mem_aln2sam (bwa/bwamem.c:837-961) for
+   every record of bwamem_pair.c:342-362 and of mem_reg2sam (bwamem.c:1030-1058).
+   Read r's SAM lines are dev_text[dev_text_off[r] .. dev_text_off[r+1]), byte for
+   byte what the reference leaves in bseq1_t.sam without its NUL: the spans follow
+   one another without a gap, a non-empty one ends in '\n'.
+   For a pair with sel.status == BWAGPU_SEL_DONE the record lists are those of
+   bwagpu_pairsel_t's comment.  A record takes rid, pos, is_rev, n_cigar, NM, the
+   CIGAR and MD from the job of its region, score, sub = max(sub, csub), is_alt and
+   alt_sc from the region (bwamem.c:1170-1171; bwagpu_aln_t.score is not AS), its
+   mapq from sel.mapq (h[i]) or dev_out_mapq, printed as eight bits hold it.  A
+   record's XA (MEM_F_XB: XB) string is the regions with xa_of == its region, in
+   index order.  MEM_F_SOFTCLIP and MEM_F_XB are honoured.  The 0x100 branches of
+   mem_aln2sam ("*\t*" for SEQ and QUAL, records left out of SA:Z) are not built:
+   only MEM_F_ALL and MEM_F_NO_MULTI give a record that flag, and both are refused.
+   dev_status[i] is BWAGPU_SAM_DONE or the reason why both reads of pair i have
+   empty spans and the caller keeps the CPU path for it.  dev_text_n[1] is the
+   text of all BWAGPU_SAM_DONE and BWAGPU_SAM_NO_ROOM pairs; while it is over
+   text_cap, the pairs from the first one that would pass text_cap on are
+   BWAGPU_SAM_NO_ROOM and dev_text_n[0] < dev_text_n[1] is what was written
+   (text_cap = dev_text_n[1] of an earlier call always fits).
+   Before any launch: NULLs (dev_qual, dev_comment_off with dev_comments and rg_id
+   may be), negative or odd n_reads, negative text_cap, n_contigs or job_cap,
+   max_ops < 1, max_md < 1 and an rg_id over BWAGPU_SAM_MAX_RG bytes return
+   BWAGPU_E_INVAL; MEM_F_REF_HDR and the four flags bwagpu_selopt_t refuses return
+   BWAGPU_E_UNSUPPORTED; every other bit is ignored.  Nothing is validated on the
+   device except what keeps the kernels inside the arrays. */
+int bwagpu_sam_text_device(bwagpu_ctx_t *ctx, const bwagpu_samtext_t *t, int32_t n_reads, void *stream);
 
 /* Tuning, test and profiling entry points (bwagpu_debug_*, bwagpu_prof_*,
    bwagpu_ctx_ext_form / _row_bound, bwagpu_streams_concurrent) are declared

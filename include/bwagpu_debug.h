@@ -209,6 +209,12 @@ int bwagpu_debug_rescue_times(bwagpu_ctx_t *ctx, double *out);
    launch to after the last one's end, out[2] ms the host spent in the call,
    out[3] the call's job count */
 int bwagpu_debug_reg2aln_times(bwagpu_ctx_t *ctx, double *out);
+/* timing (tools_dev/sam_text_bench.py): one step of bwagpu_sam_text_device alone,
+   asynchronous on stream: 0 the count pass, 1 the scan, 2 the write pass.  The
+   steps share the context's scratch, so they only make sense as 0, 1, 2 in order
+   on one stream, each between the caller's events */
+int bwagpu_debug_sam_text_step(bwagpu_ctx_t *ctx, const bwagpu_samtext_t *t, int32_t n_reads, int32_t step,
+                               void *stream);
 int bwagpu_prof_intervals(bwagpu_ctx_t *ctx, double *start_ms, double *end_ms, int32_t max, int32_t *n);
 
 #ifdef __cplusplus
